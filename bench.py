@@ -2,7 +2,11 @@
 """bench.py — BASELINE.json's metric on MI355X: 32x32 patches/s for DSen2_20 (d=6, F=128, fp32) at
 batch 512 per GPU, synthetic inputs resident in HBM, random-init (he_uniform) weights.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the line can
+carry: the roofline of the dominant kernel (instrumented and sustained passes, each epilogue alone), the CPU baseline, the
+other BASELINE configs and, at N>1, the same K steps with the gather off.  --dump-outputs DIR writes what the last timed step
+computed (rank 0: its own output, or at N>1 with the gather what it received) as DIR/output.npy, float32.
 N>1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -102,6 +106,23 @@ def other_config(name, seconds, dev):
     return res
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def write_outputs(d, parts):
+    """DIR/output.npy: the patches of the last timed step in rank order, float32 [patch, band, 32, 32].  Above DUMP_LIMIT bytes
+    (N>1 with the gather: N x 12.6 MB) a fixed sample of whole patches, the same for every run of the same arguments, and its
+    patch indices beside it as DIR/output_patch_index.npy (float64)."""
+    y = np.concatenate([p.cpu().numpy() for p in parts], axis=0).astype(np.float32, copy=False)
+    os.makedirs(d, exist_ok=True)
+    if y.nbytes > DUMP_LIMIT:
+        n_keep = DUMP_LIMIT // (y[0].nbytes + 8)          # the patches and their float64 indices together
+        keep = np.sort(np.random.Generator(np.random.PCG64(0)).choice(y.shape[0], n_keep, replace=False))
+        y = y[keep]
+        np.save(os.path.join(d, 'output_patch_index.npy'), keep.astype(np.float64))
+    np.save(os.path.join(d, 'output.npy'), y)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -109,6 +130,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='dsen2_20_fp32', choices=sorted(CONFIGS))
     ap.add_argument('--batch', type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: roofline, sustained rate, '
+                    'epilogues alone, cpu_baseline, other_configs and (N>1) the no-gather control; --no-cpu-baseline, --cpu-budget, '
+                    '--roofline-seconds, --sustain-seconds and --other-seconds act only with it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the output of the last timed step as DIR/output.npy (float32, at most 64 MB: a fixed sample of '
+                         'patches beyond that)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-budget', type=float, default=15.0, help='seconds of CPU work for cpu_baseline')
     ap.add_argument('--roofline-seconds', type=float, default=1.5, help='GPU time of the instrumented passes behind `roofline` (right after the timed loop, same clock state), and again of their event-free replay')
@@ -180,7 +207,7 @@ def main():
     # (profiles/r04_ablation.md §2)
     bf = cfg['precision'] == 'bf16'
     rl_a = rl_r = rl_o = None
-    if rank == 0:
+    if rank == 0 and args.full:
         rl_a = torch.randn((args.batch, H, W, FEAT), dtype=torch.float32, device=dev)
         rl_r = torch.randn((args.batch, H, W, FEAT), dtype=torch.float32, device=dev)
         rl_o = torch.empty_like(rl_a)
@@ -257,6 +284,12 @@ def main():
     gw['on'] = do_gather
     elapsed, own_s = timed_steps(do_gather)
     gw['on'] = False
+    # what the last timed step computed, kept on the device for --dump-outputs: outs[] is overwritten by the passes below, and
+    # a copy to the host here would idle the GPU before them (the gather buffers are not written again)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        last = (args.steps - 1) & 1
+        dump = gather_list[last] if do_gather else [outs[last].clone()]
     diag = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -265,8 +298,8 @@ def main():
         # ---- after the timed region: what makes an N > 1 line explain itself ----
         # (a) every rank's own step, and how long its compute stream stood waiting for a gather
         stall_ms = sum(ea.elapsed_time(eb) for ea, eb in gw['events'])
-        # (b) the control: the same K steps, same bracket, with the gather OFF — compute alone on all N GPUs at once
-        elapsed_ng, own_ng = timed_steps(False)
+        # (b) the control (--full): the same K steps, same bracket, with the gather OFF — compute alone on all N GPUs at once
+        elapsed_ng, own_ng = timed_steps(False) if args.full else (float('nan'), float('nan'))
         mine = torch.tensor([own_s, stall_ms * 1e-3, gw['host_s'], elapsed_ng, own_ng], dtype=torch.float64, device=cdev)
         every = [torch.empty_like(mine) for _ in range(world)]
         td.all_gather(every, mine)
@@ -301,14 +334,17 @@ def main():
             # time the compute stream stood in `pending[b].wait()` for a gather still in flight (HIP events around the wait;
             # under gloo the host blocks instead: `host`), per step, per rank — rank 0 receives, the others send
             'gather_wait_ms_per_step': {'max': round(float(diag[:, 1].max()), 4), 'ranks': r4(1), 'host_max': round(float(diag[:, 2].max()), 4)} if do_gather else None,
-            # the control, same run, same bracket, gather off: what N GPUs computing side by side do without RCCL's kernels
-            # competing with two CU-filling persistent kernels.  ms_per_step - ms_per_step_no_gather = what the gather costs.
-            'ms_per_step_no_gather': round(float(diag[:, 3].max()), 4),
-            'per_rank_ms_per_step_no_gather': {'min': round(float(diag[:, 4].min()), 4), 'max': round(float(diag[:, 4].max()), 4)},
-            'value_no_gather': round(world * args.batch / (float(diag[:, 3].max()) * 1e-3), 1),
         })
+        if args.full:
+            result.update({
+                # the control, same run, same bracket, gather off: what N GPUs computing side by side do without RCCL's kernels
+                # competing with two CU-filling persistent kernels.  ms_per_step - ms_per_step_no_gather = what the gather costs.
+                'ms_per_step_no_gather': round(float(diag[:, 3].max()), 4),
+                'per_rank_ms_per_step_no_gather': {'min': round(float(diag[:, 4].min()), 4), 'max': round(float(diag[:, 4].max()), 4)},
+                'value_no_gather': round(world * args.batch / (float(diag[:, 3].max()) * 1e-3), 1),
+            })
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: the 3x3x128x128 body convolution (98.97 % of FLOPs) ----
         pix = args.batch * H * W
         a, r, o = rl_a, rl_r, rl_o
@@ -415,7 +451,7 @@ def main():
         del a, r, o
         rl_a = rl_r = rl_o = None
 
-    if rank == 0 and world == 1 and args.config == 'dsen2_20_fp32' and args.other_seconds > 0:
+    if rank == 0 and args.full and world == 1 and args.config == 'dsen2_20_fp32' and args.other_seconds > 0:
         # ---- the other single-GPU BASELINE configs, on the same box, AFTER everything the headline needs (its timed loop and
         # roofline legs are over; the chip is warm) — configs[2] DSen2_60 fp32 and configs[4] VDSen2_20 bf16, ~args.other_seconds
         # of GPU time each.  Not the headline, not `value`: they put two more BASELINE configs on the driver's record.
@@ -427,7 +463,7 @@ def main():
             except Exception as e:       # noqa: BLE001 — a rider must never cost the headline its line: reported in its place
                 result['other_configs'][name] = {'error': '%s: %s' % (type(e).__name__, e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 'dsen2_20_fp32':
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and args.config == 'dsen2_20_fp32':
         # ---- CPU baseline: the same graph on the host cores, bounded sample (oracle/ = checker code) ----
         from oracle import cpu_graph
         pps, sample, cores, y_cpu, gflops = cpu_graph.time_patches_per_s(flat, xs_np, NUM_LAYERS, FEAT, budget_s=args.cpu_budget)
@@ -441,6 +477,8 @@ def main():
         diff = out[:n].cpu().numpy().astype(np.float64) - y_cpu.astype(np.float64)
         result['rmse_vs_cpu_fp32'] = float(np.sqrt(np.mean(diff * diff)))
 
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     if rank == 0:
         print(json.dumps(result), flush=True)
     ddist.finalize()

@@ -23,7 +23,7 @@ def _free_port():
 def test_bench_two_ranks_gloo_rehearsal():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', _free_port(), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2',
-           '--warmup', '1', '--batch', '64', '--backend', 'gloo', '--roofline-seconds', '0.5', '--sustain-seconds', '0.3']
+           '--warmup', '1', '--batch', '64', '--backend', 'gloo', '--full', '--roofline-seconds', '0.5', '--sustain-seconds', '0.3']
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
@@ -46,7 +46,7 @@ def test_bench_two_ranks_gloo_rehearsal():
 def test_bench_two_ranks_without_gather_still_reports_the_ranks():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', _free_port(), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2',
-           '--warmup', '1', '--batch', '64', '--backend', 'gloo', '--roofline-seconds', '0.3', '--sustain-seconds', '0', '--no-gather']
+           '--warmup', '1', '--batch', '64', '--backend', 'gloo', '--full', '--roofline-seconds', '0.3', '--sustain-seconds', '0', '--no-gather']
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
@@ -67,7 +67,7 @@ def test_bench_with_a_missing_rank_exits_fast_and_names_the_step():
 
 
 def test_bench_single_gpu_line_has_contract_fields():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--cpu-budget', '2', '--roofline-seconds', '0.5', '--sustain-seconds', '0.3'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--cpu-budget', '2', '--roofline-seconds', '0.5', '--sustain-seconds', '0.3'],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
@@ -89,12 +89,34 @@ def test_bench_single_gpu_line_has_contract_fields():
     assert oc['dsen2_60_fp32']['launches_per_forward'] == 12 and oc['vdsen2_20_bf16']['launches_per_forward'] == 1
 
 
+def test_bench_plain_line_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes the last timed
+    step's output, which is the network on the bench's own inputs (PCG64(0), he_uniform seed 1) by the float64 C oracle."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from dsen2_amd import weights as dweights
+    from oracle import c_oracle, dsen2_oracle as do          # checker only
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    r = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
+    assert r['steps'] == 3 and r['warmup'] == 1 and r['dtype'] == 'f32' and r['higher_is_better'] is True and r['unit'] == 'patches/s'
+    assert abs(r['value'] * r['ms_per_step'] * 1e-3 - 512) < 1e-2 * 512
+    assert not ({'roofline', 'cpu_baseline', 'rmse_vs_cpu_fp32', 'other_configs'} & set(r))
+    assert sorted(os.listdir(str(tmp_path))) == ['output.npy']
+    y = np.load(str(tmp_path / 'output.npy'))
+    assert y.dtype == np.float32 and y.shape == (512, 6, 32, 32) and np.isfinite(y).all()
+    xs = [a[:4] for a in do.synthetic_inputs(512, 32, 32, (4, 6), seed=0)]      # rank 0's batch: same generator, same order
+    ref = c_oracle.forward(xs, dweights.random_he_uniform(10, 6, 6, 128, seed=1), 6, 128)
+    assert do.rmse(y[:4], ref) < 1e-4
+
+
 def test_bench_line_closes_on_itself_and_other_configs_run():
     """The roofline object of the default line: launches x ms_per_launch + first_ms + out_ms = forward_ms (same events), the
     traffic figure is quoted only with the ISA hash of this build; the bf16x3 config reports dtype "bf16x3" against the bf16
     peak with three MFMAs per product and never claims the headline metric."""
     def line(*extra):
-        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2', '--no-cpu-baseline', '--roofline-seconds', '0.5', '--sustain-seconds', '0.3'] + list(extra),
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2', '--full', '--no-cpu-baseline', '--roofline-seconds', '0.5', '--sustain-seconds', '0.3'] + list(extra),
                            capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert p.returncode == 0, p.stderr[-2000:]
         return json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])

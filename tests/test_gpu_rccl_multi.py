@@ -39,7 +39,7 @@ def _json_line(p):
 
 
 def test_bench_two_ranks_over_rccl():
-    r = _json_line(_launch(2, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '3',
+    r = _json_line(_launch(2, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '3', '--full',
                            '--roofline-seconds', '0.5', '--sustain-seconds', '0.5', cwd=ROOT))
     assert r['n_gpus'] == 2 and r['config']['backend'] == 'rccl' and r['config']['output_gather'] is True
     assert r['ranks_in_collective'] == 2 and len(r['per_rank_ms_per_step']['ranks']) == 2

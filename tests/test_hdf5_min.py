@@ -92,17 +92,22 @@ def test_matlab_v73_tile_reads_as_the_reference_readh5_does():
 
 @pytest.mark.parametrize('tile', ['T33UUB', 'T49JGM'])
 def test_the_reference_tiles_themselves(tile):
-    """The two tiles the reference ships, where its checkout is present (this container; never the GPU box): the reader's
-    arrays = the committed captures of them that h5py made (tests/golden/tile_*_600.npz)."""
-    import glob
-    hits = glob.glob('/root/reference/data/*%s.mat' % tile)
-    if not hits:
-        pytest.skip('no reference checkout here')
+    """The two tiles the reference ships, as tests/golden/tiles/<tile>.mat: a 390 x 12 crop of each written as MATLAB wrote the
+    originals (tests/golden/make_golden_tiles.py: their user block, chunk widths, gzip 3, a chunk index of two levels, partial
+    edge chunks).  The reader's arrays = the same window of the committed captures h5py made of the whole tiles
+    (tests/golden/tile_*_600.npz)."""
+    import re
     from dsen2_amd import cli
-    g = np.load(os.path.join(HERE, 'golden', 'tile_%s_600.npz' % tile))
-    got = cli._load(hits[0])
-    for a, key in zip(got, ('d10', 'd20', 'd60')):
-        assert a.shape == g[key].shape and np.array_equal(a.astype(g[key].dtype), g[key]), key
+    crops = json.load(open(os.path.join(HERE, 'golden', 'tiles', 'crops.json')))
+    p = os.path.join(HERE, 'golden', 'tiles', '%s.mat' % tile)
+    blob = open(p, 'rb').read()
+    assert (1, 1) in {(blob[m.start() + 4], blob[m.start() + 5]) for m in re.finditer(b'TREE', blob)}    # chunk index, level 1
+    g = np.load(os.path.join(HERE, 'golden', crops['tiles'][tile]['golden']))
+    r0, nr, c0, nc = crops['window10']
+    got = cli._load(p)
+    for a, key, s in zip(got, ('d10', 'd20', 'd60'), (1, 2, 6)):
+        want = g[key][r0 // s:(r0 + nr) // s, c0 // s:(c0 + nc) // s]
+        assert a.shape == want.shape and np.array_equal(a.astype(want.dtype), want), key
 
 
 @pytest.mark.parametrize('fname,path,word', [('unsupported_compound.h5', 'table', 'compound'),

@@ -3,6 +3,7 @@ checkpoint (training/supres_train.py:195-201: ModelCheckpoint(save_weights_only=
 /model_weights/<layer>/<layer>/...) and like the reference's MATLAB v7.3 tiles (testing/demoDSen2.py:14-28).
 Needs h5py, which the system python of the build image lacks: there tests/test_h5py_suite.py runs this file under
 /opt/conda/bin/python3.9 (which has h5py but no torch — nothing here may import torch)."""
+import json
 import os
 import sys
 
@@ -138,22 +139,32 @@ def test_cli_reads_matlab_v73_tiles(tmp_path):
     assert cli._load(p)[2] is None
 
 
-REFERENCE_DATA = '/root/reference/data'
+TILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tiles')   # crops of the reference's data/*.mat
+CROPS = json.load(open(os.path.join(TILES, 'crops.json')))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_DATA), reason='the reference checkout is only present in the build container')
 @pytest.mark.parametrize('mat, golden', [('S2A_MSIL1C_20170527_T33UUB.mat', 'tile_T33UUB_600.npz'),
                                          ('S2B_MSIL1C_20171022_T49JGM.mat', 'tile_T49JGM_600.npz')])
 def test_cli_reads_the_tiles_the_reference_ships(mat, golden):
-    """cli._load on the REAL data/*.mat files (what testing/demoDSen2.py:14-28,42,67 reads) gives the arrays committed
-    in tests/golden/ — which is what every GPU test on the bundled tiles runs on."""
+    """cli._load on tests/golden/tiles/<tile>.mat — a crop of the data/*.mat file the reference ships (what
+    testing/demoDSen2.py:14-28,42,67 reads), written as MATLAB wrote it (tests/golden/make_golden_tiles.py) — gives the same
+    window of the arrays committed in tests/golden/tile_*_600.npz, which is what every GPU test on the bundled tiles runs on;
+    h5py reads the crop the same."""
     from dsen2_amd import cli
-    d10, d20, d60 = cli._load(os.path.join(REFERENCE_DATA, mat))
+    tile = [t for t, m in CROPS['tiles'].items() if m['source'] == mat][0]
+    assert CROPS['tiles'][tile]['golden'] == golden
+    p = os.path.join(TILES, tile + '.mat')
+    d10, d20, d60 = cli._load(p)
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', golden))
-    assert d10.shape == (600, 600, 4) and d20.shape == (300, 300, 6) and d60.shape == (100, 100, 2)
+    r0, nr, c0, nc = CROPS['window10']
+    assert d10.shape == (nr, nc, 4) and d20.shape == (nr // 2, nc // 2, 6) and d60.shape == (nr // 6, nc // 6, 2)
     assert str(g['source']) == mat
-    for got, key in ((d10, 'd10'), (d20, 'd20'), (d60, 'd60')):
-        assert np.array_equal(got, g[key].astype(got.dtype)), key
+    with h5py.File(p, 'r') as f:
+        assert [f[k].attrs['MATLAB_class'] for k in ('im10', 'im20', 'im60')] == [b'single'] * 3
+        theirs = [f[k][()].transpose() for k in ('im10', 'im20', 'im60')]
+    for got, key, s, h in ((d10, 'd10', 1, theirs[0]), (d20, 'd20', 2, theirs[1]), (d60, 'd60', 6, theirs[2])):
+        assert np.array_equal(got, g[key][r0 // s:(r0 + nr) // s, c0 // s:(c0 + nc) // s].astype(got.dtype)), key
+        assert np.array_equal(got, h), key
 
 
 def _same_tree(mine, theirs, where=''):
@@ -204,46 +215,20 @@ def test_when_numbering_and_layer_names_order_both_fit_but_differ_keras_order_wi
     assert np.array_equal(got[n0 + 2 * nb:], flat[n0 + 2 * nb:])
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_DATA), reason='the reference checkout is only present in the build container')
-def test_the_reference_demo_readh5_runs_on_the_own_reader(monkeypatch):
-    """testing/demoDSen2.py:14-28 `readh5` — the reference's own function, imported from its unmodified file (its imports of
-    `supres` and matplotlib stubbed: neither is used by readh5) — gives the same arrays with this package's hdf5_min standing in
-    for h5py as with h5py itself, and they are what cli._load returns: a user without h5py can run the demo's reader as it is
-    (`sys.modules['h5py'] = dsen2_amd.hdf5_min`)."""
-    import importlib.util
-    import types
+def test_the_h5py_reading_idiom_of_the_reference_demo_runs_on_the_own_reader():
+    """testing/demoDSen2.py:14-28 reads a tile through h5py as `File(path, 'r')` used as a context manager, a dataset by name,
+    `[()]` for the whole array and `.transpose()`: the same calls on this package's hdf5_min give h5py's arrays (dtype, shape,
+    values) for both committed tiles, and they are what cli._load returns — a user without h5py can hand hdf5_min to such a
+    reader in h5py's place (`sys.modules['h5py'] = dsen2_amd.hdf5_min`)."""
     from dsen2_amd import cli, hdf5_min
 
-    def load_demo(h5):
-        stubs = {'supres': types.ModuleType('supres'), 'matplotlib': types.ModuleType('matplotlib'),
-                 'matplotlib.pyplot': types.ModuleType('matplotlib.pyplot'), 'h5py': h5}
-        stubs['supres'].DSen2_20 = stubs['supres'].DSen2_60 = None
-        stubs['matplotlib'].pyplot = stubs['matplotlib.pyplot']
-        saved = {k: sys.modules.get(k) for k in list(stubs) + ['utils', 'utils.imresize']}
-        sys.modules.update(stubs)
-        sys.path.insert(0, '/root/reference/testing')
-        sys.path.insert(0, '/root/reference')
-        try:
-            spec = importlib.util.spec_from_file_location('reference_demo_%s' % h5.__name__.replace('.', '_'),
-                                                          '/root/reference/testing/demoDSen2.py')
-            mod = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mod)         # `if __name__ == '__main__'` keeps the demo itself from running
-        finally:
-            sys.path.remove('/root/reference/testing')
-            sys.path.remove('/root/reference')
-            for k, v in saved.items():
-                if v is None:
-                    sys.modules.pop(k, None)
-                else:
-                    sys.modules[k] = v
-        mod.DATA_PATH = REFERENCE_DATA + '/'
-        return mod
-    with_h5py, with_own = load_demo(h5py), load_demo(hdf5_min)
-    for mat in ('S2A_MSIL1C_20170527_T33UUB.mat', 'S2B_MSIL1C_20171022_T49JGM.mat'):
-        a = with_h5py.readh5(mat, im60=True)
-        b = with_own.readh5(mat, im60=True)
-        c = cli._load(os.path.join(REFERENCE_DATA, mat))
-        assert len(a) == len(b) == 3
+    def read(h5, path, keys):
+        with h5.File(path, 'r') as f:
+            return [f[k][()].transpose() for k in keys]
+    keys = ('im10', 'im20', 'im60')
+    for tile in ('T33UUB', 'T49JGM'):
+        p = os.path.join(TILES, tile + '.mat')
+        a, b, c = read(h5py, p, keys), read(hdf5_min, p, keys), cli._load(p)
+        assert len(a) == len(b) == len(c) == 3
         for x, y, z in zip(a, b, c):
             assert x.dtype == y.dtype == z.dtype and x.shape == y.shape and np.array_equal(x, y) and np.array_equal(x, z)
-        assert len(with_own.readh5(mat)) == 2

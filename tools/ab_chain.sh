@@ -8,6 +8,6 @@ CFG=${1:-vdsen2_20_bf16}; N=${2:-3}; shift 2 2>/dev/null
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in $(seq $N); do
   for c in 4=1 4=0 "$@"; do
-    DSEN2_HIP_LIB=$R/build/libdsen2_hip_diag.so DSEN2_DIAG_SET=$c timeout -k 10 300 python3 $R/bench.py --config $CFG --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('diag $c', d['value'], d['ms_per_step'], r['ms_per_launch'], r['frac'])"
+    DSEN2_HIP_LIB=$R/build/libdsen2_hip_diag.so DSEN2_DIAG_SET=$c timeout -k 10 300 python3 $R/bench.py --config $CFG --full --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('diag $c', d['value'], d['ms_per_step'], r['ms_per_launch'], r['frac'])"
   done
 done

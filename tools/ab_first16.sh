@@ -9,7 +9,7 @@ for round in 1 2; do
 for l in "$@"; do
   [ -f "$R/$l" ] || { echo "skip $l"; continue; }
   for cfg in dsen2_20_bf16 dsen2_20_bf16x3; do
-    DSEN2_HIP_LIB=$R/$l python3 $R/bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --roofline-seconds 1 --sustain-seconds 0 2>/dev/null \
+    DSEN2_HIP_LIB=$R/$l python3 $R/bench.py --config $cfg --steps 20 --warmup 5 --full --no-cpu-baseline --roofline-seconds 1 --sustain-seconds 0 2>/dev/null \
       | python3 -c "import sys, json; r = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('round $round  %-28s %-16s first_ms %.4f  out_ms %.4f  step %.4f ms' % ('$l', '$cfg', r['roofline']['first_ms'], r['roofline']['out_ms'], r['ms_per_step']))"
   done
 done

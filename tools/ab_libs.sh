@@ -6,6 +6,6 @@ CFG=$1; A=$2; B=$3; N=${4:-3}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in $(seq $N); do
   for l in $A $B; do
-    DSEN2_HIP_LIB=$R/$l timeout -k 10 300 python3 $R/bench.py --config $CFG --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('$l', d['value'], d['ms_per_step'], r['ms_per_launch'], r['ms_relu_randn'], r['ms_residual_randn'])"
+    DSEN2_HIP_LIB=$R/$l timeout -k 10 300 python3 $R/bench.py --config $CFG --full --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('$l', d['value'], d['ms_per_step'], r['ms_per_launch'], r['ms_relu_randn'], r['ms_residual_randn'])"
   done
 done

@@ -24,7 +24,7 @@ keys = sys.argv[2:]
 print('   ' + '  '.join('%s=%s' % (k, r.get(k)) for k in keys))" "$@"; }
 {
 echo "first contact A/B — backend $B, $GPUS GPU(s) visible, $(date -u +%FT%TZ)"
-python3 $R/bench.py --no-cpu-baseline --other-seconds 0 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python3 $R/bench.py --full --no-cpu-baseline --other-seconds 0 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 echo "bench N=1:"; line $OUT/bench_n1.json value ms_per_step
 for n in "$@"; do
   if [ "$B" = nccl ] && [ $n -gt $GPUS ]; then echo "N=$n: skipped ($GPUS GPU(s) visible)"; continue; fi
@@ -32,7 +32,7 @@ for n in "$@"; do
   launch $n -m dsen2_amd.dist --backend $B > $OUT/preflight_n$n.json 2> $OUT/preflight_n$n.err; echo " pre-flight rc=$?"
   line $OUT/preflight_n$n.json world gather_12p6MB_ms gather_GBps_per_peer_link chunked_gather_s chunked_gather_GBps_per_peer_link gather_payload_ok chunked_payload_ok
   for hp in 0 1; do
-    DSEN2_RCCL_HIGH_PRIORITY=$hp launch $n $R/bench.py --gpus $n --backend $B > $OUT/bench_n${n}_hp$hp.json 2> $OUT/bench_n${n}_hp$hp.err; echo " bench high_priority=$hp rc=$?"
+    DSEN2_RCCL_HIGH_PRIORITY=$hp launch $n $R/bench.py --gpus $n --backend $B --full > $OUT/bench_n${n}_hp$hp.json 2> $OUT/bench_n${n}_hp$hp.err; echo " bench high_priority=$hp rc=$?"
     line $OUT/bench_n${n}_hp$hp.json value ms_per_step ms_per_step_no_gather value_no_gather ranks_in_collective per_rank_ms_per_step gather_wait_ms_per_step
   done
   for cg in 0 1; do

@@ -5,7 +5,7 @@ set -u
 TAG=${1:-sample}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in 1 2; do
-  python3 $R/bench.py 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full 2>/dev/null | python3 -c "
 import sys, json, socket
 r = json.loads(sys.stdin.read().strip().splitlines()[-1]); rl = r['roofline']; oc = r.get('other_configs', {})
 print('$TAG run $i  value %.1f  ms_per_step %.4f  frac %.4f  ms_per_launch %.4f  sustained %.4f  cpu %.1f  | dsen2_60 %.1f (%.4f)  vdsen2_bf16 %.1f (%.4f)' % (

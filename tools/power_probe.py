@@ -5,7 +5,7 @@ busy — evidence for HISTORY.md §3.2b / profiles/archive/r02_ablation.md §2 (
     python tools/power_probe.py [config ...]          # default: dsen2_20_fp32 vdsen2_20_bf16
     python tools/power_probe.py --mfma                # build/mfma_peak (tools/mfma_peak.hip): the bare matrix pipe
 
-The parent process never touches the GPU: it starts `bench.py --config C --steps K --no-cpu-baseline` as a child and
+The parent process never touches the GPU: it starts `bench.py --config C --steps K --full --no-cpu-baseline` as a child and
 reads /sys/class/drm/card*/device/hwmon/hwmon*/{power1_average,power1_input,power1_cap,freq1_input} every 50 ms.
 Prints one JSON line per config with the median / max over the child's steady phase for every card that has sensors
 (on a multi-GPU host the busy card is the one whose power rises)."""
@@ -117,7 +117,7 @@ def main():
         if cfg == 'vdsen2_20_fp32':
             steps = '40'
         child = subprocess.Popen([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', cfg, '--steps', steps,
-                                  '--warmup', '3', '--no-cpu-baseline'], stdout=subprocess.PIPE, text=True)
+                                  '--warmup', '3', '--full', '--no-cpu-baseline'], stdout=subprocess.PIPE, text=True)
         rows, t0 = [], time.time()
         while child.poll() is None:
             rows.append((time.time() - t0, sample(sens)))
