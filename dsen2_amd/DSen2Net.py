@@ -58,6 +58,8 @@ class S2Model(object):
         self._workspaces = {}
         self._ws_lock = threading.Lock()
         self.max_workspace_bytes = 6 << 30   # predict() and the tile path size their batches to stay below this
+        self.optimizer = None                # compile() (training)
+        self._train = None                   # device weights, gradient and optimizer state of a compiled model
 
     # -- keras.Model surface -------------------------------------------------------------------
     def count_params(self):
@@ -68,6 +70,8 @@ class S2Model(object):
         with torch.cuda.device(self.device):
             _lib.call('dsen2_model_load_weights', self._handle,
                       flat.ctypes.data_as(_lib.c_float_p), flat.size)
+            if self._train is not None:      # a model being trained continues from the new weights
+                self._train['flat'].copy_(torch.from_numpy(flat))
 
     def load_weights(self, path):
         self.set_weights_flat(_weights.load_flat(path, self.cin, self.cout, self.num_layers, self.feature_size))
@@ -277,6 +281,184 @@ class S2Model(object):
             _lib.call('dsen2_model_time_body_conv', self._handle, layer, _ptr(x_in), _ptr(aux), _ptr(out), n, h, w,
                       iters, _stream_ptr(self.device), ctypes.byref(ms))
         return ms.value
+
+    # -- training (fp32 models; include/dsen2_hip.h "training") ---------------------------------
+    def compile(self, optimizer='nadam', loss='mean_absolute_error', metrics=None):
+        """keras Model.compile for the reference's recipe: optimizer 'nadam' or a training.Nadam, loss
+        'mean_absolute_error' (MSE is always reported as the metric).  The optimizer state starts fresh."""
+        from . import training
+        if self.precision != 'fp32':
+            raise ValueError('training needs an fp32 model (this one is %r)' % self.precision)
+        if loss not in ('mean_absolute_error', 'mae'):
+            raise ValueError("loss must be 'mean_absolute_error', got %r" % (loss,))
+        if isinstance(optimizer, str):
+            if optimizer.lower() != 'nadam':
+                raise ValueError("optimizer must be 'nadam' or a dsen2_amd.training.Nadam, got %r" % optimizer)
+            optimizer = training.Nadam()
+        if not isinstance(optimizer, training.Nadam):
+            raise ValueError('optimizer must be a dsen2_amd.training.Nadam')
+        self.optimizer = optimizer
+        self.optimizer.reset()
+        self._train = None
+        self.stop_training = False
+
+    def _train_state(self):
+        if getattr(self, 'optimizer', None) is None:
+            raise RuntimeError('compile() the model before training it')
+        if self._train is None:
+            count = self.count_params()
+            kw = dict(dtype=torch.float32, device=self.device)
+            flat = torch.empty(count, **kw)
+            with torch.cuda.device(self.device):
+                _lib.call('dsen2_model_get_weights', self._handle, _ptr(flat), _stream_ptr(self.device))
+            self._train = dict(flat=flat, grad=torch.empty(count, **kw), m=torch.zeros(count, **kw),
+                               v=torch.zeros(count, **kw), loss2=torch.empty(2, **kw), ws=None)
+        return self._train
+
+    def train_workspace_bytes(self, n, h, w):
+        out = ctypes.c_size_t(0)
+        _lib.call('dsen2_model_train_workspace_bytes', self._handle, n, h, w, ctypes.byref(out))
+        return out.value
+
+    def gradients_device(self, xs, y, grad, loss2, out=None, workspace=None):
+        """dsen2_model_gradients on device tensors: xs as forward_device, y [n,cout,h,w]; grad [num_params] and loss2 [2]
+        receive the keras-flat gradient and (mae, mse); out (optional) the forward output."""
+        if self.precision != 'fp32':
+            raise ValueError('training needs an fp32 model (this one is %r)' % self.precision)
+        n, _, h, w = xs[0].shape
+        for x, c in zip(xs, self.bands):
+            if tuple(x.shape) != (n, c, h, w) or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
+                raise ValueError('input must be a contiguous float32 %s tensor of shape %r' % (self.device, (n, c, h, w)))
+        if len(xs) != len(self.bands):
+            raise ValueError('expected %d inputs, got %d' % (len(self.bands), len(xs)))
+        if tuple(y.shape) != (n, self.cout, h, w) or y.dtype != torch.float32 or not y.is_contiguous() or y.device != self.device:
+            raise ValueError('target must be a contiguous float32 %s tensor of shape %r, got %r'
+                             % (self.device, (n, self.cout, h, w), tuple(y.shape)))
+        if grad.numel() != self.count_params() or not grad.is_contiguous() or loss2.numel() < 2:
+            raise ValueError('grad must hold num_params floats, loss2 two')
+        if out is not None:
+            out = self._check_out(out, n, h, w)
+        if workspace is None:
+            need = self.train_workspace_bytes(n, h, w)
+            st = self._train if self._train is not None else {}
+            if st.get('ws') is None or st['ws'].numel() < need:
+                st['ws'] = None
+                st['ws'] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            workspace = st['ws']
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_model_gradients', self._handle, _ptr(xs[0]), _ptr(xs[1]),
+                      _ptr(xs[2]) if len(xs) == 3 else ctypes.c_void_p(0), _ptr(y), _ptr(out), _ptr(grad), _ptr(loss2),
+                      n, h, w, _ptr(workspace), workspace.numel(), _stream_ptr(self.device))
+        return out
+
+    def set_weights_device(self, flat):
+        """New keras-flat weights from a float32 device tensor, repacked on the device."""
+        if flat.numel() != self.count_params() or flat.dtype != torch.float32 or not flat.is_contiguous() or \
+                flat.device != self.device:
+            raise ValueError('flat must be a contiguous float32 %s tensor of %d values' % (self.device, self.count_params()))
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_model_set_weights_device', self._handle, _ptr(flat), _stream_ptr(self.device))
+
+    def nadam_update(self, grad):
+        """One optimizer step on the training weights with gradient `grad` (device tensor), then the device repack."""
+        st = self._train_state()
+        s = self.optimizer.next_step()
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_nadam_step', _ptr(st['flat']), _ptr(grad), _ptr(st['m']), _ptr(st['v']), st['flat'].numel(),
+                      s['lr'], s['b1'], s['b2'], s['eps'], s['mc_t'], s['mc_t1'], s['ms_new'], s['ms_next'], s['b2_pow_t'],
+                      _stream_ptr(self.device))
+        self.set_weights_device(st['flat'])
+
+    def _to_device(self, arrays, shapes):
+        out = []
+        for a, shp in zip(arrays, shapes):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shp:
+                raise ValueError('array of shape %r where %r is expected' % (a.shape, shp))
+            out.append(torch.from_numpy(a).to(self.device))
+        return out
+
+    def train_on_batch(self, x, y):
+        """keras Model.train_on_batch: one Nadam step on the batch; returns [loss, mean_squared_error] of the batch
+        before the step."""
+        st = self._train_state()
+        if len(x) != len(self.bands):
+            raise ValueError('expected %d inputs, got %d' % (len(self.bands), len(x)))
+        n, _, h, w = np.shape(x[0])
+        xs = self._to_device(x, [(n, c, h, w) for c in self.bands])
+        yd = self._to_device([y], [(n, self.cout, h, w)])[0]
+        self.gradients_device(xs, yd, st['grad'], st['loss2'])
+        self.nadam_update(st['grad'])
+        loss = st['loss2'].cpu().numpy().astype(np.float64)
+        return [float(loss[0]), float(loss[1])]
+
+    def evaluate(self, x, y, batch_size=None, verbose=0):
+        """keras Model.evaluate: [loss, mean_squared_error] over all samples (predict(), then float64 means)."""
+        y = np.asarray(y, dtype=np.float32)
+        pred = self.predict(x, batch_size=batch_size, verbose=verbose)
+        if pred.shape != y.shape:
+            raise ValueError('target of shape %r where %r is expected' % (y.shape, pred.shape))
+        e = pred.astype(np.float64) - y.astype(np.float64)
+        return [float(np.mean(np.abs(e))), float(np.mean(e * e))]
+
+    def fit(self, x=None, y=None, batch_size=32, epochs=1, verbose=1, callbacks=None, validation_data=None, shuffle=True,
+            initial_epoch=0, seed=None):
+        """keras Model.fit: a fresh permutation each epoch when `shuffle`, the last partial batch kept, the epoch loss the
+        sample-weighted mean of the batch losses.  Returns a training.History (loss, mean_squared_error, val_loss,
+        val_mean_squared_error, lr)."""
+        from . import training
+        x = [np.ascontiguousarray(a, dtype=np.float32) for a in x]
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        count = y.shape[0]
+        if any(a.shape[0] != count for a in x):
+            raise ValueError('inputs and target hold different numbers of samples')
+        self._train_state()
+        callbacks = list(callbacks or [])
+        history = training.History()
+        for cb in callbacks:
+            cb.set_model(self)
+            cb.on_train_begin()
+        rng = np.random.default_rng(seed)
+        self.stop_training = False
+        for epoch in range(initial_epoch, epochs):
+            order = rng.permutation(count) if shuffle else np.arange(count)
+            sums = np.zeros(2)
+            for i0 in range(0, count, batch_size):
+                idx = order[i0:i0 + batch_size]
+                r = self.train_on_batch([a[idx] for a in x], y[idx])
+                sums += np.asarray(r) * len(idx)
+                if verbose:
+                    sys.stdout.write('\rEpoch %d/%d %d/%d loss %.4e' % (epoch + 1, epochs, min(i0 + batch_size, count), count,
+                                                                     sums[0] / min(i0 + batch_size, count)))
+                    sys.stdout.flush()
+            logs = {'loss': sums[0] / count, 'mean_squared_error': sums[1] / count}
+            if validation_data is not None:
+                vl = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size)
+                logs['val_loss'], logs['val_mean_squared_error'] = vl
+            logs['lr'] = self.optimizer.lr
+            if verbose:
+                sys.stdout.write('\rEpoch %d/%d ' % (epoch + 1, epochs) +
+                                 ' '.join('%s %.4e' % kv for kv in logs.items()) + '\n')
+            for cb in callbacks:
+                cb.on_epoch_end(epoch, logs)
+            history.append(epoch, logs)
+            if self.stop_training:
+                break
+        return history
+
+    def get_weights_flat(self):
+        """The current weights in keras-flat order (host float32)."""
+        if self._train is not None:
+            flat = self._train['flat']
+        else:
+            flat = torch.empty(self.count_params(), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.call('dsen2_model_get_weights', self._handle, _ptr(flat), _stream_ptr(self.device))
+        return flat.cpu().numpy()
+
+    def save_weights(self, path):
+        """A flat .npy in keras-flat order (weights.load_flat reads it; DSen2_20 picks it up in place of a missing .hdf5)."""
+        np.save(path, self.get_weights_flat())
 
     def __del__(self):
         try:

@@ -1,7 +1,6 @@
 // capi.hip — the extern "C" boundary of libdsen2_hip.so (declared in include/dsen2_hip.h).
 // Host-side orchestration only: argument checks, weight packing/upload, workspace carving and the
 // launch sequence of one forward pass.  No torch types, no allocation inside the forward path.
-#include "../../include/dsen2_hip.h"
 
 #include <chrono>
 #include <cstdarg>
@@ -11,7 +10,7 @@
 #include <new>
 #include <vector>
 
-#include "dsen2_internal.h"
+#include "capi_internal.h"
 
 using namespace dsen2;
 
@@ -27,38 +26,11 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// Nothing may leave an extern "C" entry point as a C++ exception (std::bad_alloc from a staging vector, std::system_error
-// from a mutex): through a C / ctypes caller that is std::terminate -> abort() of the host process.  Every entry point
-// that can allocate or lock runs its body through this and reports DSEN2_ERR_* with dsen2_last_error() instead.
-template <class F>
-int guarded(F&& body) noexcept {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(DSEN2_ERR_NOMEM, "out of host memory");            // not the caller's arguments: its own code
-  } catch (const std::exception& e) {
-    return fail(DSEN2_ERR_INTERNAL, "unexpected C++ exception: %s", e.what());
-  } catch (...) {
-    return fail(DSEN2_ERR_INTERNAL, "unexpected C++ exception");
-  }
-}
-
 #define HIP_TRY(expr)                                                                          \
   do {                                                                                         \
     hipError_t e_ = (expr);                                                                    \
     if (e_ != hipSuccess) return fail(DSEN2_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
-
-struct Layer {
-  int cin, cout;        // real channel counts (keras)
-  int epilogue;
-  bool bf16;            // weights packed as bf16 for the bf16-operand body kernel (conv3x3_body16w.hip)
-  bool x3;              // ... as the (wh, wl, wh) planes of the bf16x3 form (precision 2): 3 x the bf16 weights
-  PackGeom geom;
-  size_t w_off, b_off;  // float offsets inside dev_params
-  size_t w16_off;       // first layer of a precision-1 / -2 model: its bf16 (wh | wl) form for conv3x3_first16.hip; 0 = none
-  size_t flat_off;      // float offset of the kernel inside the keras-flat array
-};
 
 constexpr int kBf16ChunkChannels = 32;   // input channels per weight chunk of conv3x3_body16w.hip
 
@@ -77,22 +49,18 @@ Tuning default_tuning() {
 }
 
 constexpr int kWarmLaunches = 24;      // dsen2_model_time_body_conv: untimed launches before the timed ones
-constexpr size_t kAlignFloats = 64;   // 256-byte alignment of every device sub-buffer
-size_t align_up(size_t v) { return (v + kAlignFloats - 1) / kAlignFloats * kAlignFloats; }
 
 }  // namespace
 
-struct dsen2_model {
-  int c10, c20, c60, cin, cout, num_layers, feat, precision;
-  int device;
-  Tuning tune;          // kernel structures, fixed at creation
-  std::vector<Layer> layers;
-  size_t n_params;
-  size_t chain_stride;  // precision 1 / 2: bytes between the packed weights (= between the biases) of consecutive body layers; 0 = not uniform
-  size_t dev_param_floats;
-  float* dev_params;
-  bool loaded;
-};
+namespace dsen2 {
+int capi_fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+}  // namespace dsen2
 
 // A handle belongs to the device that was current when it was created (its packed weights live there): a call made with
 // another current device would hand device A's pointers to kernels launched on device B.
@@ -193,7 +161,7 @@ static int model_create_unguarded(dsen2_model** out, int c10, int c20, int c60, 
   if (!m) return fail(DSEN2_ERR_INVALID, "out of host memory");
   m->c10 = c10; m->c20 = c20; m->c60 = c60; m->cin = cin; m->cout = cout;
   m->num_layers = num_layers; m->feat = feature_size; m->precision = precision;
-  m->dev_params = nullptr; m->loaded = false;
+  m->dev_params = nullptr; m->loaded = false; m->train = nullptr;
   m->tune = default_tuning();
   if (hipGetDevice(&m->device) != hipSuccess) {
     delete m;
@@ -251,6 +219,7 @@ static int model_create_unguarded(dsen2_model** out, int c10, int c20, int c60, 
 
 void dsen2_model_destroy(dsen2_model* m) {
   if (!m) return;
+  train_state_destroy(m->train);
   if (m->dev_params) (void)hipFree(m->dev_params);
   delete m;
 }
@@ -278,6 +247,7 @@ static int model_load_weights_unguarded(dsen2_model* m, const float* host_flat, 
   if (!m->dev_params) HIP_TRY(hipMalloc((void**)&m->dev_params, m->dev_param_floats * sizeof(float)));
   HIP_TRY(hipMemcpy(m->dev_params, staged.data(), m->dev_param_floats * sizeof(float), hipMemcpyHostToDevice));
   m->loaded = true;
+  if (m->train) return train_state_after_load(m);     // a model being trained: its master weights follow
   return DSEN2_OK;
 }
 

@@ -446,6 +446,10 @@ hipError_t launch_conv3x3(const ConvParams& p, const PackGeom& geom, int epilogu
   DSEN2_CASE(256, 32, 256, 128, kEpiRelu)
   DSEN2_CASE(256, 32, 256, 128, kEpiResidual)
   DSEN2_CASE(256, 32, 32, 32, kEpiSkipNCHW)
+  // 16 -> F with the residual epilogue: the input gradient of the output convolution (capi_train.hip), from dL/dout padded to
+  // 16 channels, with flipped and transposed weights
+  DSEN2_CASE(16, 16, 128, 128, kEpiResidual)
+  DSEN2_CASE(16, 16, 256, 128, kEpiResidual)
 #undef DSEN2_CASE
   return hipErrorInvalidValue;
 }

@@ -186,4 +186,25 @@ hipError_t launch_tile_gather(const float* img, int H, int W, int C, int border,
 hipError_t launch_recompose(const float* patches, int count, int C, int P, int border, float* img, int H, int W,
                             float scale, int row0, int row1, hipStream_t stream);
 
+// ---- training (conv3x3_wgrad.hip, train_ops.hip) --------------------------------------------------
+// Weight / bias gradient of a 3x3 'same' convolution: dw (HWIO (3,3,ci_real,co_real)) = scale * sum_p a[p + tap][ci] g[p][co],
+// db[co_real] = scale * sum_p g[p][co]; a NHWC with ca channels, g NHWC with cg.  Shapes: cg % 128 == 0 (body, first layer), or
+// cg <= 32 with ca % 128 == 0 (output layer); ca, cg multiples of 4.  ws: wgrad_workspace_floats() floats of split-K partials
+// (0 = shape not supported).  Fixed-order reduction: the same bits on every run.
+size_t wgrad_workspace_floats(int n, int h, int w, int ca, int cg);
+hipError_t launch_conv3x3_wgrad(const float* a, int ca, const float* g, int cg, int n, int h, int w, int ci_real, int co_real,
+                                float scale, float* dw, float* db, float* ws, size_t ws_floats, hipStream_t stream);
+// keras mean_absolute_error over NCHW out / y ([n][c][h][w], c <= 16): loss2 = (mean |e|, mean e^2), gpad = dL/dout =
+// sign(e) / (n*c*h*w) as NHWC16 (channels >= c zero).  partial: mae_loss_partial_doubles(n*h*w) doubles of scratch.
+size_t mae_loss_partial_doubles(size_t pixels);
+hipError_t launch_mae_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h,
+                                int w, hipStream_t stream);
+// v = m > 0 ? v : 0 (count % 4 == 0, 16-byte aligned)
+hipError_t launch_relu_mask(float* v, const float* m, size_t count, hipStream_t stream);
+hipError_t launch_nadam(float* p, const float* g, float* m, float* v, size_t count, float lr, float b1, float b2, float eps,
+                        float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, hipStream_t stream);
+// dst[i] = map[i] ? src[map[i] - 1] : 0   /   flat[map[i] - 1] = packed[i] where map[i] != 0
+hipError_t launch_gather(float* dst, const float* src, const int* map, size_t n, hipStream_t stream);
+hipError_t launch_scatter(float* flat, const float* packed, const int* map, size_t n, hipStream_t stream);
+
 }  // namespace dsen2

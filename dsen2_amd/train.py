@@ -1,0 +1,100 @@
+"""python -m dsen2_amd.train — fine-tune DSen2 / VDSen2 on the GPU: the counterpart of training/supres_train.py.
+
+Keeps that script's flags (--path, --resume, --run_60, --deep) and its recipe: MAE loss with MSE as a metric, keras-2 Nadam
+(beta_1 0.9, beta_2 0.999, epsilon 1e-8, schedule_decay 0.004), ReduceLROnPlateau (factor 0.5, patience 5, min_delta 1e-6,
+cooldown 20, min_lr 1e-5), best-only checkpointing on val_loss, shuffled epochs.  Each run writes
+
+  <out>/<model_nr>lr_<lr>.npy       the best-val_loss weights, flat (weights.load_flat reads it; DSen2_20 / DSen2_60 pick it up
+                                    in place of a missing .hdf5 of the same name)
+  <out>/<model_nr>_lr_<lr>.txt      one line per epoch: loss, val_loss, lr
+
+fp32 models on one GPU only.  Data: <path>/train/*SAFE/{data10,data20,data20_gt}.npy (train60/ and data60, data60_gt with
+--run_60) and val_index.npy, as training/create_patches.py writes them.
+"""
+import argparse
+import os
+import sys
+
+MODEL_NR = 's2_038_'    # training/supres_train.py: prefix of a new training
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog='python -m dsen2_amd.train', description='Fine-tune DSen2 / VDSen2 on the GPU (SupResS2).')
+    p.add_argument('--resume', action='store', dest='resume_file', help='Resume training from these weights (.hdf5 / .npy).')
+    p.add_argument('--run_60', action='store_true', help='Train a 60->10m network. Default 20->10m.')
+    p.add_argument('--deep', action='store_true', help='VDSen2: 32 blocks of 256 features, batch 8 (default DSen2: 6 x 128, batch 128).')
+    p.add_argument('--path', default='../data/', help='Path of the data (train/ or train60/ below it).')
+    p.add_argument('--epochs', type=int, default=8 * 1024, help='Epochs (default 8192, as the reference).')
+    p.add_argument('--lr', type=float, default=1e-4, help='Initial learning rate (default 1e-4).')
+    p.add_argument('--batch_size', type=int, default=None, help='Batch size (default 128, 8 with --deep).')
+    p.add_argument('--out', default=None, help='Output directory (default <path>/network_data/).')
+    p.add_argument('--seed', type=int, default=None, help='Seed of the epoch shuffles.')
+    return p.parse_args(argv)
+
+
+def model_number(resume_file):
+    """The reference's args.resume_file[-20:-13] for 's2_032_lr_1e-04.hdf5', for any extension."""
+    stem = os.path.splitext(os.path.basename(resume_file))[0]
+    return stem[-15:-8]
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.stderr.write('dsen2_amd.train runs on one GPU: data-parallel training (WORLD_SIZE > 1) is not supported\n')
+        return 2
+    from . import training
+    from .DSen2Net import s2model
+
+    path = args.path if args.path.endswith('/') else args.path + '/'
+    out = args.out if args.out is not None else path + 'network_data/'
+    os.makedirs(out, exist_ok=True)
+    bands = ((4, None, None), (6, None, None), (2, None, None)) if args.run_60 else ((4, None, None), (6, None, None))
+    if args.deep:
+        model = s2model(bands, num_layers=32, feature_size=256)
+        batch_size = 8
+    else:
+        model = s2model(bands, num_layers=6, feature_size=128)
+        batch_size = 128
+    if args.batch_size:
+        batch_size = args.batch_size
+    model_nr = MODEL_NR
+    if args.resume_file:
+        print('Will resume from the weights {}'.format(args.resume_file))
+        model.load_weights(args.resume_file)
+        model_nr = model_number(args.resume_file)
+        print('Changing the model number to: {}'.format(model_nr))
+    else:
+        from . import weights
+        model.set_weights_flat(weights.random_he_uniform(model.cin, model.cout, model.num_layers, model.feature_size,
+                                                         seed=args.seed if args.seed is not None else 1))
+        print('Model number is {}'.format(model_nr))
+    model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
+                  loss='mean_absolute_error')
+
+    print('Loading the training data...')
+    train, label, val_tr, val_lb = training.load_training_data(path, args.run_60, training.SCALE)
+    print('Loaded {} patches for training, {} for validation.'.format(label.shape[0], val_lb.shape[0]))
+
+    ckpt = os.path.join(out, model_nr + 'lr_{:.0e}.npy'.format(args.lr))
+    log_path = os.path.join(out, model_nr + '_lr_{:.1e}.txt'.format(args.lr))
+    open(log_path, 'w').close()
+
+    class EpochLog(training.Callback):
+        def on_epoch_end(self, epoch, logs=None):
+            with open(log_path, 'a') as f:
+                f.write('Finished epoch {:5d}: loss {:.3e}, valid: {:.3e}, lr: {:.1e}\n'
+                        .format(epoch, logs.get('loss'), logs.get('val_loss'), self.model.optimizer.lr))
+
+    callbacks = [training.ModelCheckpoint(ckpt, monitor='val_loss', verbose=1, save_best_only=True), EpochLog(),
+                 training.ReduceLROnPlateau(monitor='val_loss', factor=0.5, patience=5, verbose=1, min_delta=1e-6,
+                                            cooldown=20, min_lr=1e-5)]
+    print('Training starts...')
+    model.fit(x=train, y=label, batch_size=batch_size, epochs=args.epochs, verbose=1, callbacks=callbacks,
+              validation_data=(val_tr, val_lb), shuffle=True, seed=args.seed)
+    print('best weights: {}\nlog: {}'.format(ckpt, log_path))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -198,6 +198,42 @@ int dsen2_model_time_body_conv(dsen2_model *m, int layer, const float *dev_in, c
                                float *dev_out, int n, int h, int w, int iters, void *stream,
                                float *ms_per_launch);
 
+/* ---- training (fp32 models only) ------------------------------------------------------------
+ * The counterpart of training/supres_train.py's model.fit: MAE loss (keras mean_absolute_error, MSE as a metric), the
+ * gradients of every parameter, keras-2 Nadam.  Every training entry returns DSEN2_ERR_INVALID ("training needs an fp32
+ * model") for a precision-1 or -2 handle.  No float atomics: the same inputs give the same bits, run to run.
+ *
+ * dsen2_model_train_workspace_bytes: scratch dsen2_model_gradients needs for n patches of h x w (the saved activations
+ *   x0 .. x_d and t_1 .. t_d, two gradient tensors, the weight-gradient partials; ~1 GB for DSen2 at 128 x 32 x 32).
+ * dsen2_model_gradients: one forward with every activation kept and its backward.  x10 / x20 / x60 as dsen2_model_forward,
+ *   target [n,cout,h,w] NCHW; dev_out_or_NULL receives the forward output (bit-identical to dsen2_model_forward's), or NULL;
+ *   dev_grad_flat [num_params] receives dLoss/dParameter in keras-flat order (the order dsen2_model_load_weights takes);
+ *   dev_loss2 (or NULL) receives [mean |out - target|, mean (out - target)^2].  dL/dout = sign(out - target) / (n*cout*h*w),
+ *   sign(0) = 0; the ReLU gradient passes where the saved ReLU output is > 0.
+ * dsen2_model_get_weights: the model's weights, keras-flat, into dev_flat [num_params].
+ * dsen2_model_set_weights_device: new keras-flat weights from device memory, repacked on the device (no host round trip);
+ *   dsen2_model_forward uses them afterwards.  Bit-identical to dsen2_model_load_weights of the same values.
+ * dsen2_nadam_step: keras 2.2 Nadam on `count` parameters p with gradients g and state m, v (updated in place).  The
+ *   per-step scalars come from the host, t = the 1-based step, sd = schedule_decay, m_schedule starting at 1:
+ *     mc_t = b1 (1 - 0.5 * 0.96^(t sd)),  mc_t1 = b1 (1 - 0.5 * 0.96^((t+1) sd)),  ms_new = m_schedule * mc_t,
+ *     ms_next = ms_new * mc_t1,  b2_pow_t = b2^t;
+ *   g' = g / (1 - ms_new), m = b1 m + (1 - b1) g, m' = m / (1 - ms_next), v = b2 v + (1 - b2) g^2, v' = v / (1 - b2_pow_t),
+ *   p -= lr ((1 - mc_t) g' + mc_t1 m') / (sqrt(v') + eps).
+ * dsen2_conv3x3_wgrad: the weight-gradient kernel alone (kernel-level tests): dev_dw (3,3,ci,co) = scale * sum over all pixels
+ *   of a[p + tap][c] g[p][o], dev_db [co] = scale * sum g[p][o]; dev_a NHWC [n,h,w,ca], dev_g NHWC [n,h,w,cg]; ci <= ca, co <= cg.
+ *   Shapes: cg a multiple of 128 (ca a multiple of 4), or cg <= 32 with ca a multiple of 128.  Allocates its scratch and
+ *   synchronises (test path). */
+int dsen2_model_train_workspace_bytes(const dsen2_model *m, int n, int h, int w, size_t *bytes);
+int dsen2_model_gradients(dsen2_model *m, const float *x10, const float *x20, const float *x60, const float *target,
+                          float *dev_out_or_NULL, float *dev_grad_flat, float *dev_loss2, int n, int h, int w, void *ws,
+                          size_t ws_bytes, void *stream);
+int dsen2_model_get_weights(const dsen2_model *m, float *dev_flat, void *stream);
+int dsen2_model_set_weights_device(dsen2_model *m, const float *dev_flat, void *stream);
+int dsen2_nadam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float b1, float b2, float eps,
+                     float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, void *stream);
+int dsen2_conv3x3_wgrad(const float *dev_a, const float *dev_g, float *dev_dw, float *dev_db, int n, int h, int w, int ca,
+                        int cg, int ci, int co, float scale, void *stream);
+
 /* ---- tiling / up-sampling / recomposition (utils/patches.py) --------------------------------
  * dsen2_upsample_mirror_bilinear  <->  interp_patches            utils/patches.py:11-16
  *   planes x [h,w] -> planes x [oh,ow]; half-pixel-centre bilinear with mirror boundary (skimage

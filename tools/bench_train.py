@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""Fine-tuning speed: one JSON line per configuration.
+
+    python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N]
+
+  step_ms            one training step on device-resident data: dsen2_model_gradients + dsen2_nadam_step + the device repack
+  train_on_batch_ms  S2Model.train_on_batch from host arrays (adds the H2D copies and the loss read-back)
+  forward_ms         dsen2_model_forward at the same batch
+  patches_per_s      batch / step_ms
+  wgrad_tflops       the weight-gradient kernel of one body layer (conv3x3_wgrad.hip) alone, timed with HIP events over
+                     `iters` launches through dsen2_conv3x3_wgrad's kernels on device buffers (2 * 9 * F^2 * n*h*w FLOP each)
+DSen2 runs at batch 128, VDSen2 at batch 8, both on 32 x 32 patches (training/supres_train.py's batch sizes).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dsen2_amd import _lib, training, weights  # noqa: E402
+from dsen2_amd.DSen2Net import _ptr, _stream_ptr, s2model  # noqa: E402
+
+PEAK_TF = 157.3   # fp32 MFMA peak of the MI355X (MI355X_MICROARCH.md)
+CONFIGS = {'dsen2': dict(d=6, F=128, batch=128), 'vdsen2': dict(d=32, F=256, batch=8)}
+
+
+def timed(fn, iters, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def run(name, iters):
+    c = CONFIGS[name]
+    d, F, n, h, w = c['d'], c['F'], c['batch'], 32, 32
+    dev = torch.device('cuda', 0)
+    m = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev)
+    m.set_weights_flat(weights.random_he_uniform(10, 6, d, F, seed=1, bias_scale=0.05))
+    m.compile(training.Nadam(lr=1e-4))
+    rng = np.random.default_rng(0)
+    xs = [rng.uniform(0, 0.5, (n, k, h, w)).astype(np.float32) for k in (4, 6)]
+    y = rng.uniform(0, 0.5, (n, 6, h, w)).astype(np.float32)
+    xs_d = [torch.from_numpy(a).to(dev) for a in xs]
+    y_d = torch.from_numpy(y).to(dev)
+    st = m._train_state()
+
+    def step():
+        m.gradients_device(xs_d, y_d, st['grad'], st['loss2'])
+        m.nadam_update(st['grad'])
+    step_ms = timed(step, iters)
+    tob_ms = timed(lambda: m.train_on_batch(xs, y), max(2, iters // 2), warm=1)
+    fwd_ms = timed(lambda: m.forward_device(xs_d), iters)
+
+    # the weight-gradient kernel of one body layer, through the library's launcher on preallocated buffers
+    a = torch.from_numpy(rng.uniform(-1, 1, (n, h, w, F)).astype(np.float32)).to(dev)
+    g = torch.from_numpy(rng.uniform(-1, 1, (n, h, w, F)).astype(np.float32)).to(dev)
+    dw = torch.empty(9 * F * F, device=dev)
+    db = torch.empty(F, device=dev)
+
+    def wgrad():
+        _lib.call('dsen2_conv3x3_wgrad', _ptr(a), _ptr(g), _ptr(dw), _ptr(db), n, h, w, F, F, F, F, 1.0, _stream_ptr(dev))
+    # dsen2_conv3x3_wgrad allocates its scratch and synchronises on every call: its kernels' share is what a HIP-event pair
+    # around the call measures minus that overhead, so the kernels are timed from a rocprofv3 kernel trace instead when one
+    # is given (profiles/); here: the call's wall time, an upper bound of the kernel time
+    wg_ms = timed(wgrad, iters, warm=2)
+    flop = 2.0 * 9 * F * F * n * h * w
+    res = dict(config=name, batch=n, h=h, w=w, num_layers=d, feature_size=F, step_ms=round(step_ms, 4),
+               train_on_batch_ms=round(tob_ms, 4), forward_ms=round(fwd_ms, 4), step_over_forward=round(step_ms / fwd_ms, 3),
+               patches_per_s=round(n / step_ms * 1e3, 1), wgrad_call_ms=round(wg_ms, 4),
+               wgrad_tflops_lower_bound=round(flop / wg_ms / 1e9, 2), wgrad_fraction_of_peak_lower_bound=round(flop / wg_ms / 1e9 / PEAK_TF, 3))
+    print(json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--config', default='both', choices=['dsen2', 'vdsen2', 'both'])
+    ap.add_argument('--iters', type=int, default=10)
+    args = ap.parse_args()
+    for name in (['dsen2', 'vdsen2'] if args.config == 'both' else [args.config]):
+        run(name, args.iters)
+
+
+if __name__ == '__main__':
+    main()
