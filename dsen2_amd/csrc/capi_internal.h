@@ -1,5 +1,7 @@
-// Host-side declarations shared by the two C-ABI translation units (capi.hip: network object and forward; capi_train.hip:
-// the training entries).
+// The one host-side vocabulary of the two C-ABI translation units (capi.hip: network object, the forward, single-layer and
+// patch entries; capi_train.hip: the training entries): the error setter and HIP_TRY, guarded(), the model object, the shape
+// and device checks, make_params, the RAII holders of events and of a temporary device buffer, and the declarations of the
+// forward's launch sequence (capi.hip), which inference and training both run.
 #pragma once
 #include <exception>
 #include <new>
@@ -11,7 +13,13 @@
 namespace dsen2 {
 
 // sets the thread-local text of dsen2_last_error() and returns `code` (capi.hip)
-int capi_fail(int code, const char* fmt, ...);
+int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                                              \
+  do {                                                                                                             \
+    hipError_t e_ = (expr);                                                                                        \
+    if (e_ != hipSuccess) return dsen2::fail(DSEN2_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
+  } while (0)
 
 // Nothing may leave an extern "C" entry point as a C++ exception (std::bad_alloc from a staging vector, std::system_error
 // from a mutex): through a C / ctypes caller that is std::terminate -> abort() of the host process.  Every entry point
@@ -21,11 +29,11 @@ int guarded(F&& body) noexcept {
   try {
     return body();
   } catch (const std::bad_alloc&) {
-    return capi_fail(DSEN2_ERR_NOMEM, "out of host memory");            // not the caller's arguments: its own code
+    return fail(DSEN2_ERR_NOMEM, "out of host memory");            // not the caller's arguments: its own code
   } catch (const std::exception& e) {
-    return capi_fail(DSEN2_ERR_INTERNAL, "unexpected C++ exception: %s", e.what());
+    return fail(DSEN2_ERR_INTERNAL, "unexpected C++ exception: %s", e.what());
   } catch (...) {
-    return capi_fail(DSEN2_ERR_INTERNAL, "unexpected C++ exception");
+    return fail(DSEN2_ERR_INTERNAL, "unexpected C++ exception");
   }
 }
 
@@ -64,3 +72,95 @@ struct dsen2_model {
   bool loaded;
   dsen2::TrainState* train;   // NULL until the first training call
 };
+
+namespace dsen2 {
+
+inline int check_shape(const dsen2_model* m, int n, int h, int w) {
+  if (n <= 0 || h <= 0 || w <= 0) return fail(DSEN2_ERR_INVALID, "bad shape n=%d h=%d w=%d", n, h, w);
+  if ((size_t)h * w * (size_t)(m ? m->feat : 256) >= ((size_t)1 << 29))
+    return fail(DSEN2_ERR_INVALID, "one image of %dx%d exceeds 2^31 activation bytes", h, w);
+  return DSEN2_OK;
+}
+
+// A handle belongs to the device that was current when it was created (its packed weights live there): a call made with
+// another current device would hand device A's pointers to kernels launched on device B.
+inline int check_device(const dsen2_model* m) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return fail(DSEN2_ERR_NO_DEVICE, "no HIP device");
+  if (dev != m->device)
+    return fail(DSEN2_ERR_INVALID, "model handle belongs to device %d but the calling thread's current device is %d "
+                     "(one handle per device: hipSetDevice(%d) before the call)", m->device, dev, m->device);
+  return DSEN2_OK;
+}
+
+inline ConvParams make_params(const float* in, const float* wpk, const float* bias, const float* aux, float* out, int n, int h,
+                              int w, int cout_real, float scale) {
+  ConvParams p;
+  p.in = in; p.wpk = wpk; p.bias = bias; p.aux = aux; p.out = out; p.out2 = nullptr;
+  p.n = n; p.h = h; p.w = w;
+  p.tiles_x = (w + kTile - 1) / kTile; p.tiles_y = (h + kTile - 1) / kTile;
+  p.cout_real = cout_real; p.res_scale = scale; p.diag = nullptr;
+  return p;
+}
+
+// events that are destroyed on every path
+struct Events {
+  std::vector<hipEvent_t> ev;
+  int create(size_t count) {
+    ev.assign(count, nullptr);
+    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
+    return DSEN2_OK;
+  }
+  ~Events() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// a temporary device buffer that is freed on every path
+struct DeviceBuffer {
+  char* p = nullptr;
+  ~DeviceBuffer() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// The single-layer entries (tests and tools; they own the stream until they return): one temporary device buffer holding
+// parts a | b, each copied from the host (host == NULL: scratch the kernel fills itself), one launch(buffer), synchronise.
+struct HostPart { const void* host; size_t bytes; };
+template <class Launch>
+int launch_once_with_temp(const char* what, HostPart a, HostPart b, hipStream_t stream, Launch&& launch) {
+  DeviceBuffer dev;
+  HIP_TRY(hipMalloc((void**)&dev.p, a.bytes + b.bytes));
+  if (a.host) HIP_TRY(hipMemcpy(dev.p, a.host, a.bytes, hipMemcpyHostToDevice));
+  if (b.host) HIP_TRY(hipMemcpy(dev.p + a.bytes, b.host, b.bytes, hipMemcpyHostToDevice));
+  hipError_t e = launch(dev.p);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return fail(DSEN2_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+  return DSEN2_OK;
+}
+
+// ---- the forward's launch sequence (capi.hip) ----
+// The activations of one forward pass.  Inference carves them from the caller's workspace (forward_ws), the residual blocks
+// running in place on `a` and `t`; training (capi_train.hip) points x0 / a / t into its own workspace and keeps every block's
+// activations (forward_launches, keep_step).
+struct ForwardWs {
+  float* x0 = nullptr;                                // NHWC16 packed input
+  float* a = nullptr;                                 // residual stream x, fp32 (16-bit precisions: the first convolution's
+                                                      // output where it is the generic kernel's, and the last block's)
+  float* t = nullptr;                                 // precision 0: relu(convA(x))
+  void *hi = nullptr, *lo = nullptr, *tbf = nullptr;  // precision 1: the stream as two 16-bit planes; relu(convA(x)) as bf16
+  void *hx = nullptr, *lo16 = nullptr, *t2 = nullptr; // precision 2: the stream as hx (hi | xl planes) and lo16; t as (hi | lo) planes
+  size_t bytes = 0;
+};
+// the inference workspace for n images of h x w: its size and, with base != NULL, its sub-buffers
+ForwardWs forward_ws(const dsen2_model* m, int n, int h, int w, char* base);
+// Every launch of one forward pass, in stream order; no argument checks.  keep_step = 0: the blocks run in place.  keep_step
+// > 0 (precision 0 only): block l reads x_{l-1} at B.a + (l - 1) * keep_step and writes t_l at B.t + (l - 1) * keep_step and
+// x_l at B.a + l * keep_step (floats).  x0_packed: the caller has already run launch_pack_inputs into B.x0.
+// ev (optional, 4 events): recorded on the stream before the first convolution, before the first and after the last
+// residual-block convolution, and after the output convolution.
+int forward_launches(const dsen2_model* m, const float* x10, const float* x20, const float* x60, float* out, int n, int h, int w,
+                     const ForwardWs& B, size_t keep_step, bool x0_packed, hipStream_t stream, const hipEvent_t* ev);
+
+}  // namespace dsen2

@@ -45,31 +45,10 @@ void train_state_destroy(TrainState* t) {
 
 namespace {
 
-#define TRY_HIP(expr)                                                                                          \
-  do {                                                                                                         \
-    hipError_t e_ = (expr);                                                                                    \
-    if (e_ != hipSuccess) return capi_fail(DSEN2_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-  } while (0)
-
 int check_train_model(const dsen2_model* m) {
-  if (!m) return capi_fail(DSEN2_ERR_INVALID, "NULL model");
-  if (m->precision != 0) return capi_fail(DSEN2_ERR_INVALID, "training needs an fp32 model");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return capi_fail(DSEN2_ERR_NO_DEVICE, "no HIP device");
-  if (dev != m->device)
-    return capi_fail(DSEN2_ERR_INVALID, "model handle belongs to device %d but the calling thread's current device is %d",
-                     m->device, dev);
-  return DSEN2_OK;
-}
-
-ConvParams conv_params(const float* in, const float* wpk, const float* bias, const float* aux, float* out, int n, int h, int w,
-                       int cout_real, float scale) {
-  ConvParams p;
-  p.in = in; p.wpk = wpk; p.bias = bias; p.aux = aux; p.out = out; p.out2 = nullptr;
-  p.n = n; p.h = h; p.w = w;
-  p.tiles_x = (w + kTile - 1) / kTile; p.tiles_y = (h + kTile - 1) / kTile;
-  p.cout_real = cout_real; p.res_scale = scale; p.diag = nullptr;
-  return p;
+  if (!m) return fail(DSEN2_ERR_INVALID, "NULL model");
+  if (m->precision != 0) return fail(DSEN2_ERR_INVALID, "training needs an fp32 model");
+  return check_device(m);
 }
 
 // map value for a packed float that holds iota value v of the layer starting at flat_off: 1 + flat index, 0 = padding
@@ -77,7 +56,7 @@ inline int map_value(float v, size_t flat_off) { return v > 0.f ? (int)(flat_off
 
 int ensure_train_state(dsen2_model* m) {
   if (m->train) return DSEN2_OK;
-  if (m->n_params >= (size_t)0x7fffffff) return capi_fail(DSEN2_ERR_INVALID, "too many parameters for the gather maps");
+  if (m->n_params >= (size_t)0x7fffffff) return fail(DSEN2_ERR_INVALID, "too many parameters for the gather maps");
   TrainState* t = new TrainState();
   struct Guard {                    // freed unless handed to the model
     TrainState* t;
@@ -86,7 +65,7 @@ int ensure_train_state(dsen2_model* m) {
   const int F = m->feat;
   const size_t L = m->layers.size();
   if (!conv_pack_geometry(F, F, kEpiResidual, m->tune, &t->body_geom) || !conv_pack_geometry(16, F, kEpiResidual, m->tune, &t->out_geom))
-    return capi_fail(DSEN2_ERR_INVALID, "no dgrad kernel for feature size %d", F);
+    return fail(DSEN2_ERR_INVALID, "no dgrad kernel for feature size %d", F);
   // forward map: the packers of dsen2_model_load_weights on iota kernels
   std::vector<int> fmap(m->dev_param_floats, 0);
   std::vector<float> staged(m->dev_param_floats, 0.f);
@@ -126,12 +105,12 @@ int ensure_train_state(dsen2_model* m) {
     pack_conv_weights_host(k.data(), cin2, cout2, g, buf.data());
     for (size_t i = 0; i < buf.size(); ++i) dmap[t->dg_off[li] + i] = map_value(buf[i], Ly.flat_off);
   }
-  TRY_HIP(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
-  TRY_HIP(hipMalloc((void**)&t->fwd_map, fmap.size() * sizeof(int)));
-  TRY_HIP(hipMalloc((void**)&t->dg, t->dg_floats * sizeof(float)));
-  TRY_HIP(hipMalloc((void**)&t->dg_map, dmap.size() * sizeof(int)));
-  TRY_HIP(hipMemcpy(t->fwd_map, fmap.data(), fmap.size() * sizeof(int), hipMemcpyHostToDevice));
-  TRY_HIP(hipMemcpy(t->dg_map, dmap.data(), dmap.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
+  HIP_TRY(hipMalloc((void**)&t->fwd_map, fmap.size() * sizeof(int)));
+  HIP_TRY(hipMalloc((void**)&t->dg, t->dg_floats * sizeof(float)));
+  HIP_TRY(hipMalloc((void**)&t->dg_map, dmap.size() * sizeof(int)));
+  HIP_TRY(hipMemcpy(t->fwd_map, fmap.data(), fmap.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(t->dg_map, dmap.data(), dmap.size() * sizeof(int), hipMemcpyHostToDevice));
   m->train = t;
   guard.t = nullptr;
   if (m->loaded) return train_state_after_load(m);
@@ -141,8 +120,8 @@ int ensure_train_state(dsen2_model* m) {
 // master <- the packed forward weights (inverse gather), dgrad weights <- master
 int refresh_from_packed(dsen2_model* m, hipStream_t s) {
   TrainState* t = m->train;
-  TRY_HIP(launch_scatter(t->master, m->dev_params, t->fwd_map, m->dev_param_floats, s));
-  TRY_HIP(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
+  HIP_TRY(launch_scatter(t->master, m->dev_params, t->fwd_map, m->dev_param_floats, s));
+  HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
   return DSEN2_OK;
 }
 
@@ -150,6 +129,7 @@ struct TrainWs {
   float *in16, *out, *gpad, *G, *DU, *wg, *loss2;
   double* partial;
   std::vector<float*> X, T;
+  size_t keep_step;   // X[l] = X[0] + l * keep_step, T[l] = T[1] + (l - 1) * keep_step: what forward_launches writes
   size_t wg_floats;
   size_t bytes;
 };
@@ -170,6 +150,7 @@ TrainWs carve(const dsen2_model* m, int n, int h, int w, char* base) {
     return p;
   };
   r.in16 = take(pix * 16);
+  r.keep_step = full;
   for (int l = 0; l <= m->num_layers; ++l) r.X.push_back(take(full));
   r.T.push_back(nullptr);
   for (int l = 1; l <= m->num_layers; ++l) r.T.push_back(take(full));
@@ -185,152 +166,13 @@ TrainWs carve(const dsen2_model* m, int n, int h, int w, char* base) {
   return r;
 }
 
-int check_shape_train(const dsen2_model* m, int n, int h, int w) {
-  if (n <= 0 || h <= 0 || w <= 0) return capi_fail(DSEN2_ERR_INVALID, "bad shape n=%d h=%d w=%d", n, h, w);
-  if ((size_t)h * w * (size_t)m->feat >= ((size_t)1 << 29))
-    return capi_fail(DSEN2_ERR_INVALID, "one image of %dx%d exceeds 2^31 activation bytes", h, w);
-  return DSEN2_OK;
-}
-
-int train_workspace_bytes_unguarded(const dsen2_model* m, int n, int h, int w, size_t* bytes) {
-  if (!bytes) return capi_fail(DSEN2_ERR_INVALID, "NULL argument");
-  if (int rc = check_train_model(m)) return rc;
-  if (int rc = check_shape_train(m, n, h, w)) return rc;
-  *bytes = carve(m, n, h, w, nullptr).bytes;
-  return DSEN2_OK;
-}
-
-int gradients_unguarded(dsen2_model* m, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out,
-                        float* grad, float* loss2, int n, int h, int w, void* ws, size_t ws_bytes, void* stream_) {
-  if (int rc = check_train_model(m)) return rc;
-  if (!x10 || !x20 || !target || !grad || !ws) return capi_fail(DSEN2_ERR_INVALID, "NULL argument");
-  if ((m->c60 > 0) != (x60 != nullptr)) return capi_fail(DSEN2_ERR_INVALID, "x60 must be given iff the model has a 60 m input");
-  if (!m->loaded) return capi_fail(DSEN2_ERR_NO_WEIGHTS, "no weights: dsen2_model_load_weights or dsen2_model_set_weights_device first");
-  if (int rc = check_shape_train(m, n, h, w)) return rc;
-  const size_t need = carve(m, n, h, w, nullptr).bytes;
-  if (ws_bytes < need) return capi_fail(DSEN2_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
-  if (int rc = ensure_train_state(m)) return rc;
-  TrainWs W = carve(m, n, h, w, reinterpret_cast<char*>(ws));
-  if (!dev_out) dev_out = W.out;
-  if (!loss2) loss2 = W.loss2;
-  hipStream_t s = (hipStream_t)stream_;
-  const TrainState* t = m->train;
-  const float* P = m->dev_params;
-  const float* zero = t->dg + t->zero_off;
-  const int F = m->feat, d = m->num_layers;
-  const size_t pix = (size_t)n * h * w;
-
-  // ---- forward, every activation kept (the launches of dsen2_model_forward's fp32 path: the same bits) ----
-  TRY_HIP(launch_pack_inputs(x10, x20, x60, m->c10, m->c20, m->c60, W.in16, n, h, w, s));
-  {
-    const Layer& L0 = m->layers[0];
-    ConvParams pf = conv_params(W.in16, P + L0.w_off, P + L0.b_off, nullptr, W.X[0], n, h, w, 0, 0.f);
-    hipError_t direct = hipErrorNotSupported;
-    if (L0.geom.variant == 10 || L0.geom.variant == 12) {
-      ConvParams pd = pf;
-      pd.in = x10;
-      pd.aux = x20;
-      direct = launch_conv3x3_first(pd, FirstInputs{x60, m->c10, m->c20, m->c60}, F, L0.epilogue, s, m->tune.first_ablate);
-      if (direct != hipSuccess && direct != hipErrorNotSupported)
-        return capi_fail(DSEN2_ERR_HIP, "first convolution launch: %s", hipGetErrorString(direct));
-    }
-    if (direct != hipSuccess) TRY_HIP(launch_conv3x3(pf, L0.geom, L0.epilogue, 0, s));
-  }
-  for (int l = 1; l <= d; ++l) {
-    const Layer& LA = m->layers[2 * l - 1];
-    const Layer& LB = m->layers[2 * l];
-    TRY_HIP(launch_conv3x3(conv_params(W.X[l - 1], P + LA.w_off, P + LA.b_off, nullptr, W.T[l], n, h, w, 0, 0.f), LA.geom, LA.epilogue, 0, s));
-    TRY_HIP(launch_conv3x3(conv_params(W.T[l], P + LB.w_off, P + LB.b_off, W.X[l - 1], W.X[l], n, h, w, 0, 0.1f), LB.geom, LB.epilogue, 0, s));
-  }
-  const Layer& LO = m->layers.back();
-  const float* skip = m->c60 > 0 ? x60 : x20;
-  TRY_HIP(launch_conv3x3(conv_params(W.X[d], P + LO.w_off, P + LO.b_off, skip, dev_out, n, h, w, m->cout, 0.f), LO.geom, LO.epilogue,
-                         m->tune.out_ablate, s));
-
-  // ---- loss, output layer ----
-  TRY_HIP(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, s));
-  auto wgrad = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly, float scale) -> hipError_t {
-    float* dw = grad + Ly.flat_off;
-    return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.cin, Ly.cout, scale, dw, dw + (size_t)9 * Ly.cin * Ly.cout, W.wg,
-                                W.wg_floats, s);
-  };
-  TRY_HIP(wgrad(W.X[d], F, W.gpad, 16, LO, 1.f));
-  const size_t fbytes = pix * F * sizeof(float);
-  TRY_HIP(hipMemsetAsync(W.G, 0, fbytes, s));
-  TRY_HIP(launch_conv3x3(conv_params(W.gpad, t->dg + t->dg_off[m->layers.size() - 1], zero, W.G, W.G, n, h, w, 0, 1.f), t->out_geom,
-                         kEpiResidual, 0, s));
-  // ---- residual blocks, last to first ----
-  for (int l = d; l >= 1; --l) {
-    const Layer& LA = m->layers[2 * l - 1];
-    const Layer& LB = m->layers[2 * l];
-    TRY_HIP(wgrad(W.T[l], F, W.G, F, LB, 0.1f));
-    TRY_HIP(hipMemsetAsync(W.DU, 0, fbytes, s));
-    TRY_HIP(launch_conv3x3(conv_params(W.G, t->dg + t->dg_off[2 * l], zero, W.DU, W.DU, n, h, w, 0, 0.1f), t->body_geom, kEpiResidual, 0, s));
-    TRY_HIP(launch_relu_mask(W.DU, W.T[l], pix * F, s));
-    TRY_HIP(wgrad(W.X[l - 1], F, W.DU, F, LA, 1.f));
-    TRY_HIP(launch_conv3x3(conv_params(W.DU, t->dg + t->dg_off[2 * l - 1], zero, W.G, W.G, n, h, w, 0, 1.f), t->body_geom, kEpiResidual, 0, s));
-  }
-  // ---- first convolution ----
-  TRY_HIP(launch_relu_mask(W.G, W.X[0], pix * F, s));
-  TRY_HIP(wgrad(W.in16, 16, W.G, F, m->layers[0], 1.f));
-  return DSEN2_OK;
-}
-
-int get_weights_unguarded(const dsen2_model* mc, float* dev_flat, void* stream) {
-  if (int rc = check_train_model(mc)) return rc;
-  if (!dev_flat) return capi_fail(DSEN2_ERR_INVALID, "NULL argument");
-  if (!mc->loaded) return capi_fail(DSEN2_ERR_NO_WEIGHTS, "no weights loaded");
-  dsen2_model* m = const_cast<dsen2_model*>(mc);     // the training state is a cache of the weights the model holds
-  if (int rc = ensure_train_state(m)) return rc;
-  TRY_HIP(hipMemcpyAsync(dev_flat, m->train->master, m->n_params * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return DSEN2_OK;
-}
-
-int set_weights_device_unguarded(dsen2_model* m, const float* dev_flat, void* stream) {
-  if (int rc = check_train_model(m)) return rc;
-  if (!dev_flat) return capi_fail(DSEN2_ERR_INVALID, "NULL argument");
-  if (!m->dev_params) TRY_HIP(hipMalloc((void**)&m->dev_params, m->dev_param_floats * sizeof(float)));
-  if (int rc = ensure_train_state(m)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  TrainState* t = m->train;
-  if (dev_flat != t->master)
-    TRY_HIP(hipMemcpyAsync(t->master, dev_flat, m->n_params * sizeof(float), hipMemcpyDeviceToDevice, s));
-  TRY_HIP(launch_gather(m->dev_params, t->master, t->fwd_map, m->dev_param_floats, s));
-  TRY_HIP(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
-  m->loaded = true;
-  return DSEN2_OK;
-}
-
-int nadam_unguarded(float* p, const float* g, float* mm, float* v, size_t count, float lr, float b1, float b2, float eps, float mc_t,
-                    float mc_t1, float ms_new, float ms_next, float b2_pow_t, void* stream) {
-  if (count > 0 && (!p || !g || !mm || !v)) return capi_fail(DSEN2_ERR_INVALID, "NULL argument");
-  TRY_HIP(launch_nadam(p, g, mm, v, count, lr, b1, b2, eps, mc_t, mc_t1, ms_new, ms_next, b2_pow_t, (hipStream_t)stream));
-  return DSEN2_OK;
-}
-
-int wgrad_unguarded(const float* a, const float* g, float* dw, float* db, int n, int h, int w, int ca, int cg, int ci, int co,
-                    float scale, void* stream_) {
-  if (!a || !g || !dw || !db) return capi_fail(DSEN2_ERR_INVALID, "NULL argument");
-  if (n <= 0 || h <= 0 || w <= 0 || ci <= 0 || co <= 0 || ci > ca || co > cg) return capi_fail(DSEN2_ERR_INVALID, "bad shape");
-  const size_t wf = wgrad_workspace_floats(n, h, w, ca, cg);
-  if (wf == 0) return capi_fail(DSEN2_ERR_INVALID, "no wgrad kernel for %d -> %d channels", ca, cg);
-  hipStream_t s = (hipStream_t)stream_;
-  float* ws = nullptr;
-  TRY_HIP(hipMalloc((void**)&ws, wf * sizeof(float)));
-  hipError_t e = launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, ci, co, scale, dw, db, ws, wf, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(ws);
-  if (e != hipSuccess) return capi_fail(DSEN2_ERR_HIP, "wgrad launch: %s", hipGetErrorString(e));
-  return DSEN2_OK;
-}
-
 }  // namespace
 
 namespace dsen2 {
 
 int train_state_after_load(dsen2_model* m) {
   if (int rc = refresh_from_packed(m, nullptr)) return rc;
-  TRY_HIP(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
   return DSEN2_OK;
 }
 
@@ -339,27 +181,125 @@ int train_state_after_load(dsen2_model* m) {
 extern "C" {
 
 int dsen2_model_train_workspace_bytes(const dsen2_model* m, int n, int h, int w, size_t* bytes) {
-  return guarded([&] { return train_workspace_bytes_unguarded(m, n, h, w, bytes); });
-}
-int dsen2_model_gradients(dsen2_model* m, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out,
-                          float* dev_grad_flat, float* dev_loss2, int n, int h, int w, void* ws, size_t ws_bytes, void* stream) {
-  return guarded([&] {
-    return gradients_unguarded(m, x10, x20, x60, target, dev_out, dev_grad_flat, dev_loss2, n, h, w, ws, ws_bytes, stream);
+  return guarded([&]() -> int {
+    if (!bytes) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if (int rc = check_train_model(m)) return rc;
+    if (int rc = check_shape(m, n, h, w)) return rc;
+    *bytes = carve(m, n, h, w, nullptr).bytes;
+    return DSEN2_OK;
   });
 }
-int dsen2_model_get_weights(const dsen2_model* m, float* dev_flat, void* stream) {
-  return guarded([&] { return get_weights_unguarded(m, dev_flat, stream); });
+
+int dsen2_model_gradients(dsen2_model* m, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out,
+                          float* grad, float* loss2, int n, int h, int w, void* ws, size_t ws_bytes, void* stream_) {
+  return guarded([&]() -> int {
+    if (int rc = check_train_model(m)) return rc;
+    if (!x10 || !x20 || !target || !grad || !ws) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if ((m->c60 > 0) != (x60 != nullptr)) return fail(DSEN2_ERR_INVALID, "x60 must be given iff the model has a 60 m input");
+    if (!m->loaded) return fail(DSEN2_ERR_NO_WEIGHTS, "no weights: dsen2_model_load_weights or dsen2_model_set_weights_device first");
+    if (int rc = check_shape(m, n, h, w)) return rc;
+    const size_t need = carve(m, n, h, w, nullptr).bytes;
+    if (ws_bytes < need) return fail(DSEN2_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
+    if (int rc = ensure_train_state(m)) return rc;
+    TrainWs W = carve(m, n, h, w, reinterpret_cast<char*>(ws));
+    if (!dev_out) dev_out = W.out;
+    if (!loss2) loss2 = W.loss2;
+    hipStream_t s = (hipStream_t)stream_;
+    const TrainState* t = m->train;
+    const float* zero = t->dg + t->zero_off;
+    const int F = m->feat, d = m->num_layers;
+    const size_t pix = (size_t)n * h * w;
+    const Layer& LO = m->layers.back();
+
+    // ---- forward, every activation kept: dsen2_model_forward's own launches (forward_launches), so the same bits.  The
+    // NHWC16 input is packed here whatever the first convolution reads: the first layer's weight gradient needs it ----
+    HIP_TRY(launch_pack_inputs(x10, x20, x60, m->c10, m->c20, m->c60, W.in16, n, h, w, s));
+    ForwardWs B;
+    B.x0 = W.in16;
+    B.a = W.X[0];
+    B.t = d > 0 ? W.T[1] : nullptr;
+    if (int rc = forward_launches(m, x10, x20, x60, dev_out, n, h, w, B, W.keep_step, true, s, nullptr)) return rc;
+
+    // ---- loss, output layer ----
+    HIP_TRY(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, s));
+    auto wgrad = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly, float scale) -> hipError_t {
+      float* dw = grad + Ly.flat_off;
+      return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.cin, Ly.cout, scale, dw, dw + (size_t)9 * Ly.cin * Ly.cout, W.wg,
+                                  W.wg_floats, s);
+    };
+    HIP_TRY(wgrad(W.X[d], F, W.gpad, 16, LO, 1.f));
+    const size_t fbytes = pix * F * sizeof(float);
+    HIP_TRY(hipMemsetAsync(W.G, 0, fbytes, s));
+    HIP_TRY(launch_conv3x3(make_params(W.gpad, t->dg + t->dg_off[m->layers.size() - 1], zero, W.G, W.G, n, h, w, 0, 1.f), t->out_geom,
+                           kEpiResidual, 0, s));
+    // ---- residual blocks, last to first ----
+    for (int l = d; l >= 1; --l) {
+      const Layer& LA = m->layers[2 * l - 1];
+      const Layer& LB = m->layers[2 * l];
+      HIP_TRY(wgrad(W.T[l], F, W.G, F, LB, 0.1f));
+      HIP_TRY(hipMemsetAsync(W.DU, 0, fbytes, s));
+      HIP_TRY(launch_conv3x3(make_params(W.G, t->dg + t->dg_off[2 * l], zero, W.DU, W.DU, n, h, w, 0, 0.1f), t->body_geom, kEpiResidual, 0, s));
+      HIP_TRY(launch_relu_mask(W.DU, W.T[l], pix * F, s));
+      HIP_TRY(wgrad(W.X[l - 1], F, W.DU, F, LA, 1.f));
+      HIP_TRY(launch_conv3x3(make_params(W.DU, t->dg + t->dg_off[2 * l - 1], zero, W.G, W.G, n, h, w, 0, 1.f), t->body_geom, kEpiResidual, 0, s));
+    }
+    // ---- first convolution ----
+    HIP_TRY(launch_relu_mask(W.G, W.X[0], pix * F, s));
+    HIP_TRY(wgrad(W.in16, 16, W.G, F, m->layers[0], 1.f));
+    return DSEN2_OK;
+  });
 }
+
+int dsen2_model_get_weights(const dsen2_model* mc, float* dev_flat, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = check_train_model(mc)) return rc;
+    if (!dev_flat) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if (!mc->loaded) return fail(DSEN2_ERR_NO_WEIGHTS, "no weights loaded");
+    dsen2_model* m = const_cast<dsen2_model*>(mc);     // the training state is a cache of the weights the model holds
+    if (int rc = ensure_train_state(m)) return rc;
+    HIP_TRY(hipMemcpyAsync(dev_flat, m->train->master, m->n_params * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DSEN2_OK;
+  });
+}
+
 int dsen2_model_set_weights_device(dsen2_model* m, const float* dev_flat, void* stream) {
-  return guarded([&] { return set_weights_device_unguarded(m, dev_flat, stream); });
+  return guarded([&]() -> int {
+    if (int rc = check_train_model(m)) return rc;
+    if (!dev_flat) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if (!m->dev_params) HIP_TRY(hipMalloc((void**)&m->dev_params, m->dev_param_floats * sizeof(float)));
+    if (int rc = ensure_train_state(m)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    TrainState* t = m->train;
+    if (dev_flat != t->master)
+      HIP_TRY(hipMemcpyAsync(t->master, dev_flat, m->n_params * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(launch_gather(m->dev_params, t->master, t->fwd_map, m->dev_param_floats, s));
+    HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
+    m->loaded = true;
+    return DSEN2_OK;
+  });
 }
+
 int dsen2_nadam_step(float* p, const float* g, float* m, float* v, size_t count, float lr, float b1, float b2, float eps, float mc_t,
                      float mc_t1, float ms_new, float ms_next, float b2_pow_t, void* stream) {
-  return guarded([&] { return nadam_unguarded(p, g, m, v, count, lr, b1, b2, eps, mc_t, mc_t1, ms_new, ms_next, b2_pow_t, stream); });
+  return guarded([&]() -> int {
+    if (count > 0 && (!p || !g || !m || !v)) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    HIP_TRY(launch_nadam(p, g, m, v, count, lr, b1, b2, eps, mc_t, mc_t1, ms_new, ms_next, b2_pow_t, (hipStream_t)stream));
+    return DSEN2_OK;
+  });
 }
+
 int dsen2_conv3x3_wgrad(const float* dev_a, const float* dev_g, float* dev_dw, float* dev_db, int n, int h, int w, int ca, int cg,
                         int ci, int co, float scale, void* stream) {
-  return guarded([&] { return wgrad_unguarded(dev_a, dev_g, dev_dw, dev_db, n, h, w, ca, cg, ci, co, scale, stream); });
+  return guarded([&]() -> int {
+    if (!dev_a || !dev_g || !dev_dw || !dev_db) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if (n <= 0 || h <= 0 || w <= 0 || ci <= 0 || co <= 0 || ci > ca || co > cg) return fail(DSEN2_ERR_INVALID, "bad shape");
+    const size_t wf = wgrad_workspace_floats(n, h, w, ca, cg);
+    if (wf == 0) return fail(DSEN2_ERR_INVALID, "no wgrad kernel for %d -> %d channels", ca, cg);
+    hipStream_t s = (hipStream_t)stream;
+    return launch_once_with_temp("wgrad", {nullptr, wf * sizeof(float)}, {nullptr, 0}, s, [&](char* dev) {
+      return launch_conv3x3_wgrad(dev_a, ca, dev_g, cg, n, h, w, ci, co, scale, dev_dw, dev_db, reinterpret_cast<float*>(dev), wf, s);
+    });
+  });
 }
 
 }  // extern "C"
