@@ -20,8 +20,6 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-constexpr int kBf16ChunkChannels = 32;   // input channels per weight chunk of conv3x3_body16w.hip
-
 #ifdef DSEN2_DIAG
 // Diagnostic build only (tools/): defaults copied into models and single-layer calls made AFTER dsen2_diag_set.
 // The product library has no mutable globals — a model's kernel structures are fixed constants.
@@ -50,16 +48,10 @@ int fail(int code, const char* fmt, ...) {
 }
 }  // namespace dsen2
 
-static hipError_t launch_bf16_body(const ConvParams& p, int feat, int epilogue, const Tuning& t, hipStream_t stream) {
-  // (masks from 1024 up belong to the chain kernel)
-  return launch_conv3x3_body16w(p, feat, epilogue, t.ablate & 1023, stream, t.grid_cap);
-}
-
 // One persistent launch over all 2d body convolutions of a precision-1 / -2 model may be tried (the launcher still answers
 // hipErrorNotSupported for a batch that keeps more CUs busy layer by layer); the precision-2 chain has no ablation build.
 static bool may_chain(const dsen2_model* m) {
-  return (m->precision == 1 || m->precision == 2) && m->num_layers > 0 && m->chain_stride != 0 && m->tune.chain &&
-         m->tune.grid_cap == 0 && (m->precision == 1 || m->tune.ablate == 0);
+  return m->chain_stride != 0 && m->tune.chain && m->tune.grid_cap == 0 && (m->precision == 1 || m->tune.ablate == 0);
 }
 
 // DSen2Net.py:24-29: Concatenate + Conv2D + ReLU.  Leaves the residual stream where the body reads it: fp32 B.a (precision 0,
@@ -67,40 +59,36 @@ static bool may_chain(const dsen2_model* m) {
 static int first_layer(const dsen2_model* m, const float* x10, const float* x20, const float* x60, int n, int h, int w,
                        const ForwardWs& B, bool x0_packed, hipStream_t stream) {
   const Layer& L = m->layers[0];
+  const ConvPlan& pl = L.plan;
   const float* P = m->dev_params;
-  const bool planes = m->precision == 1 && m->num_layers > 0;
   const bool x3 = m->precision == 2 && m->num_layers > 0;
-  ConvParams pf = make_params(B.x0, P + L.w_off, P + L.b_off, nullptr, B.a, n, h, w, 0, 0.f);
-  if (planes) {
+  ConvParams pf = make_params(B.x0, L.weights(P), L.bias(P), nullptr, B.a, n, h, w, 0, 0.f);
+  if (pl.epilogue == kEpiReluSplit) {
     // a precision-1 model's first convolution writes the residual stream directly as its two blocked 16-bit planes
     pf.out = reinterpret_cast<float*>(B.hi);
     pf.out2 = B.lo;
   }
-  // the default structure reads the NCHW inputs itself (conv3x3_first.hip); other channel counts, and the reference
-  // structure (variant 0), pack them to NHWC16 first
-  hipError_t direct = hipErrorNotSupported;
+  // the direct kernels read the NCHW inputs themselves; other channel counts, and the reference structure, pack them to
+  // NHWC16 first
   const FirstInputs fi{x60, m->c10, m->c20, m->c60};
   ConvParams pd = pf;
   pd.in = x10;
   pd.aux = x20;
-  if (L.w16_off && (planes || x3)) {
+  bool done = false;
+  if (pl.first16_planes) {
     // precision 1 / 2: on the bf16 matrix cores, writing the residual stream's planes itself (conv3x3_first16.hip) —
     // precision 1: (hi, lo); precision 2: hx (hi | xl planes) and lo16
-    pd.wpk = P + L.w16_off;
+    pd.wpk = L.first16(P);
     pd.out = reinterpret_cast<float*>(x3 ? B.hx : B.hi);
     pd.out2 = x3 ? B.lo16 : B.lo;
-    direct = launch_conv3x3_first16(pd, fi, m->feat, x3, stream);
-    if (direct != hipSuccess && direct != hipErrorNotSupported)
-      return fail(DSEN2_ERR_HIP, "first convolution (bf16 matrix cores) launch: %s", hipGetErrorString(direct));
-  } else if (!planes && !x3 && (L.geom.variant == 10 || L.geom.variant == 12)) {
-    direct = launch_conv3x3_first(pd, fi, m->feat, L.epilogue, stream, m->tune.first_ablate);
-    if (direct != hipSuccess && direct != hipErrorNotSupported)
-      return fail(DSEN2_ERR_HIP, "first convolution launch: %s", hipGetErrorString(direct));
+    HIP_TRY(try_launch(launch_conv3x3_first16(pd, fi, m->feat, x3, stream), &done));
+  } else if (pl.first_direct) {
+    HIP_TRY(try_launch(launch_conv3x3_first(pd, fi, m->feat, pl.epilogue, stream, m->tune.first_ablate), &done));
   }
-  if (direct != hipSuccess) {
+  if (!done) {
     if (!x0_packed) HIP_TRY(launch_pack_inputs(x10, x20, x60, m->c10, m->c20, m->c60, B.x0, n, h, w, stream));
-    HIP_TRY(launch_conv3x3(pf, L.geom, planes ? (int)kEpiReluSplit : L.epilogue, 0, stream));
-    if (x3) HIP_TRY(launch_split3_f32(B.a, B.hx, B.lo16, n, h, w, m->feat, stream));   // (fallback first layer: fp32 `a`)
+    HIP_TRY(launch(pl, pf, pl.epilogue, m->tune, stream));
+    if (x3) HIP_TRY(launch_split3_f32(B.a, B.hx, B.lo16, n, h, w, m->feat, stream));   // (generic first layer: fp32 `a`)
   }
   return DSEN2_OK;
 }
@@ -113,35 +101,32 @@ static int first_layer(const dsen2_model* m, const float* x10, const float* x20,
 // Either way the last block's conv-B writes plain fp32 out_f32 for the (fp32) output convolution.
 static int body16(const dsen2_model* m, void* s0, void* s1, void* t16, float* out_f32, int n, int h, int w, hipStream_t stream) {
   const float* P = m->dev_params;
-  const bool x3 = m->precision == 2;
   // One persistent launch over all 2d body convolutions when every CU gets whole patches (batch >= one patch per CU,
   // e.g. BASELINE configs[4]); hipErrorNotSupported = this batch keeps more CUs busy layer by layer.
   if (may_chain(m)) {
     const Layer& L1 = m->layers[1];
-    ConvParams pc = make_params(nullptr, P + L1.w_off, P + L1.b_off, nullptr, nullptr, n, h, w, 0, 0.1f);
+    const bool x3 = L1.plan.kernel == ConvKernel::Body16x3;
+    ConvParams pc = make_params(nullptr, L1.weights(P), L1.bias(P), nullptr, nullptr, n, h, w, 0, 0.1f);
 #ifdef DSEN2_DIAG
     if (!x3) pc.diag = g_diag_stamps;
 #endif
     ChainArgs ca;
     ca.hi = s0; ca.lo = s1; ca.t = t16; ca.out_f32 = out_f32;
     ca.layer_stride = (unsigned)m->chain_stride; ca.n_layers = 2 * m->num_layers; ca.patches_per_wg = 0; ca.seamless = 0;
-    const hipError_t chained = launch_conv3x3_body16w_chain(pc, ca, m->feat, stream, m->tune.ablate, x3);   // (x3: ablate is 0)
-    if (chained == hipSuccess) return DSEN2_OK;
-    if (chained != hipErrorNotSupported) return fail(DSEN2_ERR_HIP, "%schain kernel launch: %s", x3 ? "bf16x3 " : "", hipGetErrorString(chained));
+    bool done = false;
+    HIP_TRY(try_launch(launch_conv3x3_body16w_chain(pc, ca, m->feat, stream, m->tune.ablate, x3), &done));   // (x3: ablate is 0)
+    if (done) return DSEN2_OK;
   }
-  auto launch = [&](const ConvParams& p, int epilogue) -> hipError_t {
-    return x3 ? launch_conv3x3_body16w_x3(p, m->feat, epilogue, stream) : launch_bf16_body(p, m->feat, epilogue, m->tune, stream);
-  };
   for (int l = 1; l <= m->num_layers; ++l) {
     const Layer& LA = m->layers[2 * l - 1];
     const Layer& LB = m->layers[2 * l];
-    HIP_TRY(launch(make_params(reinterpret_cast<const float*>(s0), P + LA.w_off, P + LA.b_off, nullptr,
-                               reinterpret_cast<float*>(t16), n, h, w, 0, 0.f), kEpiRelu));
+    HIP_TRY(launch(LA.plan, make_params(reinterpret_cast<const float*>(s0), LA.weights(P), LA.bias(P), nullptr,
+                                        reinterpret_cast<float*>(t16), n, h, w, 0, 0.f), kEpiRelu, m->tune, stream));
     const bool last = l == m->num_layers;
-    ConvParams pb = make_params(reinterpret_cast<const float*>(t16), P + LB.w_off, P + LB.b_off,
+    ConvParams pb = make_params(reinterpret_cast<const float*>(t16), LB.weights(P), LB.bias(P),
                                 reinterpret_cast<const float*>(s0), last ? out_f32 : reinterpret_cast<float*>(s0), n, h, w, 0, 0.1f);
     pb.out2 = s1;
-    HIP_TRY(launch(pb, last ? kEpiResidualF32 : kEpiResidual));
+    HIP_TRY(launch(LB.plan, pb, last ? kEpiResidualF32 : kEpiResidual, m->tune, stream));
   }
   return DSEN2_OK;
 }
@@ -186,29 +171,28 @@ int forward_launches(const dsen2_model* m, const float* x10, const float* x20, c
   } else if (m->precision == 1 && d > 0) {
     if (int rc = body16(m, B.hi, B.lo, B.tbf, B.a, n, h, w, stream)) return rc;
   } else {
-    // (the training forward used to pass ablation mask 0 here; the mask is 0 in the product library, and a diagnostic build
-    // that sets it now times the ablated kernels in both)
-    const int abl = m->tune.ablate;
+    // (the ablation mask is 0 in the product library; a diagnostic build that sets it times the ablated kernels in the
+    // inference and in the training forward)
     for (int l = 1; l <= d; ++l) {      // DSen2Net.py:31-32 -> :9-15
       const Layer& LA = m->layers[2 * l - 1];
       const Layer& LB = m->layers[2 * l];
       const float* x_in = B.a + (size_t)(l - 1) * keep_step;
       float* t = B.t + (size_t)(l - 1) * keep_step;
-      HIP_TRY(launch_conv3x3(make_params(x_in, P + LA.w_off, P + LA.b_off, nullptr, t, n, h, w, 0, 0.f), LA.geom, LA.epilogue, abl, stream));
+      HIP_TRY(launch(LA.plan, make_params(x_in, LA.weights(P), LA.bias(P), nullptr, t, n, h, w, 0, 0.f), LA.plan.epilogue, m->tune, stream));
       // keep_step = 0: in place on the residual stream: every workgroup reads aux and writes out at its own pixels only
-      HIP_TRY(launch_conv3x3(make_params(t, P + LB.w_off, P + LB.b_off, x_in, B.a + (size_t)l * keep_step, n, h, w, 0, 0.1f), LB.geom,
-                             LB.epilogue, abl, stream));
+      HIP_TRY(launch(LB.plan, make_params(t, LB.weights(P), LB.bias(P), x_in, B.a + (size_t)l * keep_step, n, h, w, 0, 0.1f),
+                     LB.plan.epilogue, m->tune, stream));
     }
   }
   if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
   {
     const Layer& L = m->layers.back();           // DSen2Net.py:35,38,41
     const float* skip = m->c60 > 0 ? x60 : x20;  // utils/DSen2Net.py:38,41
-    ConvParams po = make_params(B.a + (size_t)d * keep_step, P + L.w_off, P + L.b_off, skip, out, n, h, w, m->cout, 0.f);
+    ConvParams po = make_params(B.a + (size_t)d * keep_step, L.weights(P), L.bias(P), skip, out, n, h, w, m->cout, 0.f);
 #ifdef DSEN2_DIAG
     po.diag = g_diag_stamps;
 #endif
-    HIP_TRY(launch_conv3x3(po, L.geom, L.epilogue, m->tune.out_ablate, stream));
+    HIP_TRY(launch(L.plan, po, L.plan.epilogue, m->tune, stream));
   }
   if (ev) HIP_TRY(hipEventRecord(ev[3], stream));
   return DSEN2_OK;
@@ -290,23 +274,26 @@ static int conv3x3_nhwc(const float* dev_in, const float* host_kernel, const flo
   if (epilogue != kEpiRelu && epilogue != kEpiResidual && epilogue != kEpiSkipNCHW) return fail(DSEN2_ERR_INVALID, "epilogue %d", epilogue);
   if (epilogue != kEpiRelu && !dev_aux) return fail(DSEN2_ERR_INVALID, "epilogue %d needs dev_aux", epilogue);
   if (int rc = check_shape(nullptr, n, h, w)) return rc;
-  PackGeom g;
-  if (!conv_pack_geometry(cin, cout, epilogue, tune, &g) || g.cin_pad != cin)
+  // the layer of DSen2Net.py's graph (or of its backward pass) that has this shape and epilogue
+  const ConvRole role = epilogue == kEpiSkipNCHW ? ConvRole::Output
+                        : cin <= 16 ? (epilogue == kEpiRelu ? ConvRole::First : ConvRole::DgradOutput)
+                        : epilogue == kEpiRelu ? ConvRole::BodyA : ConvRole::BodyB;
+  ConvPlan pl;
+  if (!plan_conv(role, cin, cout, 0, tune, nullptr, &pl) || pl.cin_pad != cin)
     return fail(DSEN2_ERR_INVALID, "unsupported conv %d->%d epilogue %d", cin, cout, epilogue);
   hipStream_t stream = (hipStream_t)stream_;
-  const size_t wf = packed_weight_floats(g);
-  std::vector<float> staged(wf + g.cout_pad, 0.f);
-  pack_conv_weights_host(host_kernel, cin, cout, g, staged.data());
-  memcpy(staged.data() + wf, host_bias, sizeof(float) * cout);
-  return launch_once_with_temp("conv3x3", {staged.data(), staged.size() * sizeof(float)}, {nullptr, 0}, stream, [&](char* dev) {
+  std::vector<float> staged(pl.floats);
+  pack(pl, host_kernel, host_bias, staged.data());
+  return launch_once_with_temp("conv3x3", staged.data(), staged.size() * sizeof(float), stream, [&](char* dev) {
     const float* wpk = reinterpret_cast<const float*>(dev);
-    return launch_conv3x3(make_params(dev_in, wpk, wpk + wf, dev_aux, dev_out, n, h, w, cout, res_scale), g, epilogue, tune.ablate, stream);
+    return launch(pl, make_params(dev_in, wpk, wpk + pl.bias_off, dev_aux, dev_out, n, h, w, cout, res_scale), epilogue, tune, stream);
   });
 }
 
-// dsen2_conv3x3_body_bf16 (x3 = false) and dsen2_conv3x3_body_bf16x3 (x3 = true): s0 / s1 = the residual stream's tensors
-static int conv3x3_body16(bool x3, const void* dev_in, const float* host_kernel, const float* host_bias, void* s0, void* s1,
+// dsen2_conv3x3_body_bf16 (precision 1) and dsen2_conv3x3_body_bf16x3 (precision 2): s0 / s1 = the residual stream's tensors
+static int conv3x3_body16(int precision, const void* dev_in, const float* host_kernel, const float* host_bias, void* s0, void* s1,
                           void* dev_out, int n, int h, int w, int feat, int epilogue, float res_scale, void* stream_) {
+  const bool x3 = precision == 2;
   if (!dev_in || !host_kernel || !host_bias) return fail(DSEN2_ERR_INVALID, "NULL argument");
   if (feat != 128 && feat != 256) return fail(DSEN2_ERR_INVALID, "feat %d unsupported", feat);
   if (epilogue != kEpiRelu && epilogue != kEpiResidual && epilogue != kEpiResidualF32) return fail(DSEN2_ERR_INVALID, "epilogue %d", epilogue);
@@ -315,18 +302,18 @@ static int conv3x3_body16(bool x3, const void* dev_in, const float* host_kernel,
   if (epilogue != kEpiResidual && !dev_out) return fail(DSEN2_ERR_INVALID, "dev_out is NULL");
   if (int rc = check_shape(nullptr, n, h, w)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  const size_t wn = (size_t)(x3 ? 27 : 9) * feat * feat;
-  std::vector<uint16_t> wb(wn);
-  if (x3)
-    pack_conv_weights_bf16x3_host(host_kernel, feat, feat, wb.data());
-  else
-    pack_conv_weights_bf16_host(host_kernel, feat, feat, kBf16ChunkChannels, true, wb.data());
-  return launch_once_with_temp(x3 ? "bf16x3 conv" : "bf16 conv", {wb.data(), wn * 2}, {host_bias, feat * sizeof(float)}, stream, [&](char* dev) {
-    ConvParams p = make_params(reinterpret_cast<const float*>(dev_in), reinterpret_cast<const float*>(dev),
-                               reinterpret_cast<const float*>(dev + wn * 2), reinterpret_cast<const float*>(s0),
+  const Tuning tune = default_tuning();
+  ConvPlan pl;
+  if (!plan_conv(epilogue == kEpiRelu ? ConvRole::BodyA : ConvRole::BodyB, feat, feat, precision, tune, nullptr, &pl))
+    return fail(DSEN2_ERR_INVALID, "feat %d unsupported", feat);
+  std::vector<float> staged(pl.floats);
+  pack(pl, host_kernel, host_bias, staged.data());
+  return launch_once_with_temp(x3 ? "bf16x3 conv" : "bf16 conv", staged.data(), staged.size() * sizeof(float), stream, [&](char* dev) {
+    const float* wpk = reinterpret_cast<const float*>(dev);
+    ConvParams p = make_params(reinterpret_cast<const float*>(dev_in), wpk, wpk + pl.bias_off, reinterpret_cast<const float*>(s0),
                                reinterpret_cast<float*>(epilogue == kEpiResidual ? s0 : dev_out), n, h, w, 0, res_scale);
     p.out2 = s1;
-    return x3 ? launch_conv3x3_body16w_x3(p, feat, epilogue, stream) : launch_bf16_body(p, feat, epilogue, default_tuning(), stream);
+    return launch(pl, p, epilogue, tune, stream);
   });
 }
 
@@ -371,40 +358,29 @@ const char* dsen2_version(void) {
 const char* dsen2_last_error(void) { return g_err; }
 
 #ifdef DSEN2_DIAG
-// Diagnostic build only — not declared in include/dsen2_hip.h.  key 0: structure of the fp32 body convolution
-// (14 default, 11-13 sub-variants of conv3x3_body32.hip, 0 one tile per workgroup); key 1: timing-only ablation
-// mask of the persistent body kernels (outputs are WRONG while non-zero); key 2: output-layer kernel (2 = vector units,
-// 0 = padded MFMA block).
+// Diagnostic build only — not declared in include/dsen2_hip.h.  The integer keys and values are the wire format of tools/ and
+// of DSEN2_DIAG_SET, translated to Tuning's typed fields here and nowhere else.  key 0: fp32 body convolution (14 default, 11-13
+// the other forms of conv3x3_body32.hip, 0 one tile per workgroup — and the first convolution over all 16 padded channels);
+// key 1: timing-only ablation mask of the persistent body kernels (outputs are WRONG while non-zero); key 2: output-layer
+// kernel (2 = matrix cores where the shape fits, 3 = vector units, 0 = padded MFMA block).
 int dsen2_diag_set(int key, int value) {
-  if (key == 0) {
-    if (value != 0 && (value < 11 || value > 14)) return fail(DSEN2_ERR_INVALID, "body variant %d unknown", value);
-    g_diag_tuning.body_variant = value;
-    return DSEN2_OK;
-  }
-  if (key == 1) {
-    g_diag_tuning.ablate = value;
-    return DSEN2_OK;
-  }
-  if (key == 2) {
-    if (value != 0 && value != 2 && value != 3) return fail(DSEN2_ERR_INVALID, "output variant %d unknown", value);
-    g_diag_tuning.out_variant = value;
-    return DSEN2_OK;
-  }
-  if (key == 3) {   // at most `value` workgroups for the bf16 body kernel (0 = one per CU): per-CU vs chip-wide limits
-    g_diag_tuning.grid_cap = value;
-    return DSEN2_OK;
-  }
-  if (key == 5) {   // timing-only ablation mask of the first convolution (1 no stores, 2 no MFMAs, 4 no gather)
-    g_diag_tuning.first_ablate = value;
-    return DSEN2_OK;
-  }
-  if (key == 6) {   // timing-only ablation mask of the matrix-core output convolution (conv3x3_out_mfma.hip)
-    g_diag_tuning.out_ablate = value;
-    return DSEN2_OK;
-  }
-  if (key == 4) {   // 0 = always launch the bf16 body convolutions layer by layer (A/B against the chain kernel)
-    g_diag_tuning.chain = value;
-    return DSEN2_OK;
+  Tuning& t = g_diag_tuning;
+  switch (key) {
+    case 0:
+      if (value != 0 && (value < 11 || value > 14)) return fail(DSEN2_ERR_INVALID, "body variant %d unknown", value);
+      t.first = value == 0 ? FirstKernel::Tile16 : FirstKernel::Direct;
+      t.body = value == 0 ? BodyKernel::Tile : BodyKernel::Body32;
+      t.body32 = value == 0 ? Body32Form::DeferStagger : static_cast<Body32Form>(value - 11);
+      return DSEN2_OK;
+    case 2:
+      if (value != 0 && value != 2 && value != 3) return fail(DSEN2_ERR_INVALID, "output variant %d unknown", value);
+      t.out = value == 2 ? OutKernel::MfmaThenValu : value == 3 ? OutKernel::Valu : OutKernel::Tile;
+      return DSEN2_OK;
+    case 1: t.ablate = value; return DSEN2_OK;
+    case 3: t.grid_cap = value; return DSEN2_OK;       // at most `value` workgroups for the bf16 body kernel (0 = one per CU): per-CU vs chip-wide limits
+    case 4: t.chain = value; return DSEN2_OK;          // 0 = always launch the bf16 body convolutions layer by layer (A/B against the chain kernel)
+    case 5: t.first_ablate = value; return DSEN2_OK;   // timing-only ablation mask of the first convolution (1 no stores, 2 no MFMAs, 4 no gather)
+    case 6: t.out_ablate = value; return DSEN2_OK;     // timing-only ablation mask of the matrix-core output convolution (conv3x3_out_mfma.hip)
   }
   return fail(DSEN2_ERR_INVALID, "unknown diagnostic key %d", key);
 }
@@ -453,51 +429,9 @@ int dsen2_model_create(dsen2_model** out, int c10, int c20, int c60, int num_lay
       delete m;
       return fail(DSEN2_ERR_NO_DEVICE, "no HIP device");
     }
-    // graph order of utils/DSen2Net.py:29-35
-    std::vector<std::pair<int, int>> shapes;
-    std::vector<int> epis;
-    shapes.push_back({cin, feature_size}); epis.push_back(kEpiRelu);
-    for (int i = 0; i < num_layers; ++i) {
-      shapes.push_back({feature_size, feature_size}); epis.push_back(kEpiRelu);
-      shapes.push_back({feature_size, feature_size}); epis.push_back(kEpiResidual);
-    }
-    shapes.push_back({feature_size, cout}); epis.push_back(kEpiSkipNCHW);
-    size_t flat = 0, dev = 0;
-    for (size_t i = 0; i < shapes.size(); ++i) {
-      Layer L;
-      L.cin = shapes[i].first; L.cout = shapes[i].second; L.epilogue = epis[i];
-      if (!conv_pack_geometry(L.cin, L.cout, L.epilogue, m->tune, &L.geom)) {
-        delete m;
-        return fail(DSEN2_ERR_INVALID, "no kernel for conv %d->%d", L.cin, L.cout);
-      }
-      L.flat_off = flat;
-      flat += (size_t)9 * L.cin * L.cout + L.cout;
-      const bool body = L.cin == feature_size && L.cout == feature_size;             // residual-block convolutions only
-      L.bf16 = precision == 1 && body;
-      L.x3 = precision == 2 && body;
-      L.w_off = dev;
-      dev += align_up(L.bf16 ? (size_t)9 * L.cin * L.cout / 2 : L.x3 ? (size_t)27 * L.cin * L.cout / 2 : packed_weight_floats(L.geom));
-      L.b_off = dev; dev += align_up((size_t)L.geom.cout_pad);
-      // precision 1 / 2: the first convolution runs on the bf16 matrix cores (conv3x3_first16.hip) for the Sentinel-2 band
-      // groups 4 + 6 (+ 2); its fp32 form above stays for the generic fallback
-      L.w16_off = 0;
-      if (i == 0 && precision != 0 && num_layers > 0 && c10 == 4 && c20 == 6 && (c60 == 0 || c60 == 2)) {
-        L.w16_off = dev;
-        dev += align_up((first16_weight_u16(L.cout, precision == 2) + 1) / 2);
-      }
-      m->layers.push_back(L);
-    }
-    m->n_params = flat;
-    m->dev_param_floats = dev;
-    // the chain kernel (one launch over all body layers) addresses layer l's weights and bias at l * chain_stride
-    m->chain_stride = 0;
-    if ((precision == 1 || precision == 2) && num_layers > 0) {
-      const size_t stride = m->layers[2].w_off - m->layers[1].w_off;
-      bool uniform = true;
-      for (int l = 1; l <= 2 * num_layers; ++l)
-        uniform = uniform && (m->layers[l].bf16 || m->layers[l].x3) && m->layers[l].w_off == m->layers[1].w_off + (size_t)(l - 1) * stride &&
-                  m->layers[l].b_off == m->layers[1].b_off + (size_t)(l - 1) * stride;
-      if (uniform) m->chain_stride = stride * sizeof(float);
+    if (!plan_network(c10, c20, c60, num_layers, feature_size, precision, m->tune, m)) {
+      delete m;
+      return fail(DSEN2_ERR_INVALID, "no kernel for a layer of this network");
     }
     *out = m;
     return DSEN2_OK;
@@ -519,18 +453,10 @@ int dsen2_model_load_weights(dsen2_model* m, const float* host_flat, size_t coun
     if (count != m->n_params)
       return fail(DSEN2_ERR_INVALID, "expected %zu parameters, got %zu", m->n_params, count);
     if (int rc = check_device(m)) return rc;      // the packed weights are allocated on the current device
-    std::vector<float> staged(m->dev_param_floats, 0.f);
+    std::vector<float> staged(m->dev_param_floats);
     for (const Layer& L : m->layers) {
       const float* k = host_flat + L.flat_off;
-      const float* b = k + (size_t)9 * L.cin * L.cout;
-      if (L.bf16)
-        pack_conv_weights_bf16_host(k, L.cin, L.cout, kBf16ChunkChannels, true, reinterpret_cast<uint16_t*>(staged.data() + L.w_off));
-      else if (L.x3)
-        pack_conv_weights_bf16x3_host(k, L.cin, L.cout, reinterpret_cast<uint16_t*>(staged.data() + L.w_off));
-      else
-        pack_conv_weights_host(k, L.cin, L.cout, L.geom, staged.data() + L.w_off);
-      memcpy(staged.data() + L.b_off, b, sizeof(float) * L.cout);
-      if (L.w16_off) pack_first16_weights_host(k, L.cin, L.cout, m->precision == 2, reinterpret_cast<uint16_t*>(staged.data() + L.w16_off));
+      pack(L.plan, k, k + (size_t)9 * L.plan.cin * L.plan.cout, staged.data() + L.off);
     }
     if (!m->dev_params) HIP_TRY(hipMalloc((void**)&m->dev_params, m->dev_param_floats * sizeof(float)));
     HIP_TRY(hipMemcpy(m->dev_params, staged.data(), m->dev_param_floats * sizeof(float), hipMemcpyHostToDevice));
@@ -590,10 +516,8 @@ int dsen2_conv3x3_nhwc(const float* dev_in, const float* host_kernel, const floa
 int dsen2_conv3x3_nhwc_ref(const float* dev_in, const float* host_kernel, const float* host_bias, const float* dev_aux,
                            float* dev_out, int n, int h, int w, int cin, int cout, int epilogue, float res_scale, void* stream) {
   return guarded([&] {
-    Tuning ref;                 // the one-tile-per-workgroup kernels of conv3x3_mfma.hip for every layer shape
-    ref.body_variant = 0;
-    ref.out_variant = 0;
-    return conv3x3_nhwc(dev_in, host_kernel, host_bias, dev_aux, dev_out, n, h, w, cin, cout, epilogue, res_scale, stream, ref);
+    return conv3x3_nhwc(dev_in, host_kernel, host_bias, dev_aux, dev_out, n, h, w, cin, cout, epilogue, res_scale, stream,
+                        Tuning::reference());
   });
 }
 
@@ -628,7 +552,7 @@ int dsen2_conv3x3_body_bf16(const void* dev_in_bf16, const float* host_kernel, c
                             void* dev_res_lo, void* dev_out, int n, int h, int w, int feat, int epilogue, float res_scale,
                             void* stream) {
   return guarded([&] {
-    return conv3x3_body16(false, dev_in_bf16, host_kernel, host_bias, dev_res_hi, dev_res_lo, dev_out, n, h, w, feat, epilogue, res_scale, stream);
+    return conv3x3_body16(1, dev_in_bf16, host_kernel, host_bias, dev_res_hi, dev_res_lo, dev_out, n, h, w, feat, epilogue, res_scale, stream);
   });
 }
 
@@ -636,7 +560,7 @@ int dsen2_conv3x3_body_bf16x3(const void* dev_in_planes, const float* host_kerne
                               void* dev_res_lo, void* dev_out, int n, int h, int w, int feat, int epilogue, float res_scale,
                               void* stream) {
   return guarded([&] {
-    return conv3x3_body16(true, dev_in_planes, host_kernel, host_bias, dev_res_hx, dev_res_lo, dev_out, n, h, w, feat, epilogue, res_scale, stream);
+    return conv3x3_body16(2, dev_in_planes, host_kernel, host_bias, dev_res_hx, dev_res_lo, dev_out, n, h, w, feat, epilogue, res_scale, stream);
   });
 }
 
@@ -651,15 +575,17 @@ int dsen2_conv3x3_first_planes(const float* dev_x10, const float* dev_x20, const
     if (c10 != 4 || c20 != 6 || (c60 != 0 && c60 != 2)) return fail(DSEN2_ERR_INVALID, "band groups %d + %d + %d (4 + 6 (+ 2) only)", c10, c20, c60);
     if (int rc = check_shape(nullptr, n, h, w)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const bool x3 = precision == 2;
-    const size_t wn = first16_weight_u16(feat, x3);
-    std::vector<uint16_t> wb(wn);
-    pack_first16_weights_host(host_kernel, c10 + c20 + c60, feat, x3, wb.data());
-    return launch_once_with_temp("first convolution (bf16 matrix cores)", {wb.data(), wn * 2}, {host_bias, feat * sizeof(float)}, stream, [&](char* dev) {
-      ConvParams p = make_params(dev_x10, reinterpret_cast<const float*>(dev), reinterpret_cast<const float*>(dev + wn * 2), dev_x20,
-                                 reinterpret_cast<float*>(dev_out), n, h, w, 0, 0.f);
+    const BandGroups bands{c10, c20, c60};
+    ConvPlan pl;
+    if (!plan_conv(ConvRole::First, c10 + c20 + c60, feat, precision, default_tuning(), &bands, &pl) || !pl.first16_planes)
+      return fail(DSEN2_ERR_INVALID, "no bf16 first convolution for this shape");
+    std::vector<float> staged(pl.floats);
+    pack(pl, host_kernel, host_bias, staged.data());
+    return launch_once_with_temp("first convolution (bf16 matrix cores)", staged.data(), staged.size() * sizeof(float), stream, [&](char* dev) {
+      const float* buf = reinterpret_cast<const float*>(dev);
+      ConvParams p = make_params(dev_x10, buf + pl.first16_off, buf + pl.bias_off, dev_x20, reinterpret_cast<float*>(dev_out), n, h, w, 0, 0.f);
       p.out2 = dev_out2;
-      return launch_conv3x3_first16(p, FirstInputs{dev_x60, c10, c20, c60}, feat, x3, stream);
+      return launch_conv3x3_first16(p, FirstInputs{dev_x60, c10, c20, c60}, feat, precision == 2, stream);
     });
   });
 }
@@ -673,13 +599,13 @@ int dsen2_model_time_body_conv(dsen2_model* m, int layer, const float* dev_in, c
     if (int rc = check_shape(m, n, h, w)) return rc;
     if (int rc = check_device(m)) return rc;
     const Layer& L = m->layers[layer];
-    if (L.x3) return fail(DSEN2_ERR_INVALID, "dsen2_model_time_body_conv: not available for precision 2 (use dsen2_model_forward_profile)");
-    if (L.epilogue == kEpiResidual && !dev_aux) return fail(DSEN2_ERR_INVALID, "residual layer needs dev_aux");
+    if (L.plan.kernel == ConvKernel::Body16x3) return fail(DSEN2_ERR_INVALID, "dsen2_model_time_body_conv: not available for precision 2 (use dsen2_model_forward_profile)");
+    if (L.plan.epilogue == kEpiResidual && !dev_aux) return fail(DSEN2_ERR_INVALID, "residual layer needs dev_aux");
     hipStream_t stream = (hipStream_t)stream_;
     const float* P = m->dev_params;
-    ConvParams p = make_params(dev_in, P + L.w_off, P + L.b_off, dev_aux, dev_out, n, h, w, 0, 0.1f);
-    int epi = L.epilogue;
-    if (L.bf16 && L.epilogue == kEpiResidual) {
+    ConvParams p = make_params(dev_in, L.weights(P), L.bias(P), dev_aux, dev_out, n, h, w, 0, 0.1f);
+    int epi = L.plan.epilogue;
+    if (L.plan.kernel == ConvKernel::Body16 && epi == kEpiResidual) {
       // dev_aux = hi plane followed by lo plane (one fp32-sized buffer), updated in place; the last block's layer
       // writes fp32 to dev_out instead
       const bool last = layer == 2 * m->num_layers;
@@ -687,13 +613,10 @@ int dsen2_model_time_body_conv(dsen2_model* m, int layer, const float* dev_in, c
       p.out = last ? dev_out : const_cast<float*>(dev_aux);
       epi = last ? kEpiResidualF32 : kEpiResidual;
     }
-    const int abl = m->tune.ablate;
 #ifdef DSEN2_DIAG
     p.diag = g_diag_stamps;
 #endif
-    auto launch = [&]() -> hipError_t {
-      return L.bf16 ? launch_bf16_body(p, m->feat, epi, m->tune, stream) : launch_conv3x3(p, L.geom, L.epilogue, abl, stream);
-    };
+    auto launch = [&]() -> hipError_t { return dsen2::launch(L.plan, p, epi, m->tune, stream); };
     Events ev;
     if (int rc = ev.create(2)) return rc;
     // warm-up: ~25 ms of this kernel bring the chip back to its steady clock after an idle stretch (see forward_profile)

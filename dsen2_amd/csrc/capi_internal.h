@@ -1,5 +1,5 @@
 // The one host-side vocabulary of the two C-ABI translation units (capi.hip: network object, the forward, single-layer and
-// patch entries; capi_train.hip: the training entries): the error setter and HIP_TRY, guarded(), the model object, the shape
+// patch entries; capi_train.hip: the training entries): the error setter and HIP_TRY, guarded(), the model object (its layers are conv_plan.h's), the shape
 // and device checks, make_params, the RAII holders of events and of a temporary device buffer, and the declarations of the
 // forward's launch sequence (capi.hip), which inference and training both run.
 #pragma once
@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "../../include/dsen2_hip.h"
-#include "dsen2_internal.h"
+#include "conv_plan.h"
 
 namespace dsen2 {
 
@@ -37,20 +37,6 @@ int guarded(F&& body) noexcept {
   }
 }
 
-struct Layer {
-  int cin, cout;        // real channel counts (keras)
-  int epilogue;
-  bool bf16;            // weights packed as bf16 for the bf16-operand body kernel (conv3x3_body16w.hip)
-  bool x3;              // ... as the (wh, wl, wh) planes of the bf16x3 form (precision 2): 3 x the bf16 weights
-  PackGeom geom;
-  size_t w_off, b_off;  // float offsets inside dev_params
-  size_t w16_off;       // first layer of a precision-1 / -2 model: its bf16 (wh | wl) form for conv3x3_first16.hip; 0 = none
-  size_t flat_off;      // float offset of the kernel inside the keras-flat array
-};
-
-constexpr size_t kAlignFloats = 64;   // 256-byte alignment of every device sub-buffer
-inline size_t align_up(size_t v) { return (v + kAlignFloats - 1) / kAlignFloats * kAlignFloats; }
-
 // Training state of an fp32 model (capi_train.hip), created by the first training call: the master weights as a device
 // keras-flat vector and the gather maps that rebuild every packed buffer from it.
 struct TrainState;
@@ -60,14 +46,10 @@ int train_state_after_load(dsen2_model* m);
 
 }  // namespace dsen2
 
-struct dsen2_model {
+struct dsen2_model : dsen2::NetworkPlan {   // every layer's plan and place inside dev_params (conv_plan.h)
   int c10, c20, c60, cin, cout, num_layers, feat, precision;
   int device;
   dsen2::Tuning tune;   // kernel structures, fixed at creation
-  std::vector<dsen2::Layer> layers;
-  size_t n_params;
-  size_t chain_stride;  // precision 1 / 2: bytes between the packed weights (= between the biases) of consecutive body layers; 0 = not uniform
-  size_t dev_param_floats;
   float* dev_params;
   bool loaded;
   dsen2::TrainState* train;   // NULL until the first training call
@@ -125,15 +107,13 @@ struct DeviceBuffer {
   }
 };
 
-// The single-layer entries (tests and tools; they own the stream until they return): one temporary device buffer holding
-// parts a | b, each copied from the host (host == NULL: scratch the kernel fills itself), one launch(buffer), synchronise.
-struct HostPart { const void* host; size_t bytes; };
+// The single-layer entries (tests and tools; they own the stream until they return): one temporary device buffer, copied from
+// the host (host == NULL: scratch the kernel fills itself), one launch(buffer), synchronise.
 template <class Launch>
-int launch_once_with_temp(const char* what, HostPart a, HostPart b, hipStream_t stream, Launch&& launch) {
+int launch_once_with_temp(const char* what, const void* host, size_t bytes, hipStream_t stream, Launch&& launch) {
   DeviceBuffer dev;
-  HIP_TRY(hipMalloc((void**)&dev.p, a.bytes + b.bytes));
-  if (a.host) HIP_TRY(hipMemcpy(dev.p, a.host, a.bytes, hipMemcpyHostToDevice));
-  if (b.host) HIP_TRY(hipMemcpy(dev.p + a.bytes, b.host, b.bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc((void**)&dev.p, bytes));
+  if (host) HIP_TRY(hipMemcpy(dev.p, host, bytes, hipMemcpyHostToDevice));
   hipError_t e = launch(dev.p);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (e != hipSuccess) return fail(DSEN2_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));

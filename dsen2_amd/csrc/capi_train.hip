@@ -29,7 +29,7 @@ struct TrainState {
   size_t dg_floats = 0;
   std::vector<size_t> dg_off;  // per layer: float offset of its dgrad weights in dg (layer 0: none)
   size_t zero_off = 0;         // feat zeros (the dgrad convolutions' bias)
-  PackGeom body_geom{}, out_geom{};
+  ConvPlan body_plan{}, out_plan{};   // the dgrad convolutions of a body layer (F -> F) and of the output layer (16 -> F)
 };
 
 void train_state_destroy(TrainState* t) {
@@ -64,19 +64,19 @@ int ensure_train_state(dsen2_model* m) {
   } guard{t};
   const int F = m->feat;
   const size_t L = m->layers.size();
-  if (!conv_pack_geometry(F, F, kEpiResidual, m->tune, &t->body_geom) || !conv_pack_geometry(16, F, kEpiResidual, m->tune, &t->out_geom))
+  if (!plan_conv(ConvRole::DgradBody, F, F, 0, m->tune, nullptr, &t->body_plan) ||
+      !plan_conv(ConvRole::DgradOutput, 16, F, 0, m->tune, nullptr, &t->out_plan))
     return fail(DSEN2_ERR_INVALID, "no dgrad kernel for feature size %d", F);
-  // forward map: the packers of dsen2_model_load_weights on iota kernels
+  // forward map: dsen2_model_load_weights' pack() on iota kernels (kernel, then bias, as in the keras-flat array)
   std::vector<int> fmap(m->dev_param_floats, 0);
-  std::vector<float> staged(m->dev_param_floats, 0.f);
+  std::vector<float> buf, k;
   for (const Layer& Ly : m->layers) {
-    const size_t nk = (size_t)9 * Ly.cin * Ly.cout;
-    std::vector<float> k(nk);
-    for (size_t i = 0; i < nk; ++i) k[i] = (float)(i + 1);
-    pack_conv_weights_host(k.data(), Ly.cin, Ly.cout, Ly.geom, staged.data() + Ly.w_off);
-    const size_t wf = packed_weight_floats(Ly.geom);
-    for (size_t i = 0; i < wf; ++i) fmap[Ly.w_off + i] = map_value(staged[Ly.w_off + i], Ly.flat_off);
-    for (int j = 0; j < Ly.cout; ++j) fmap[Ly.b_off + j] = (int)(Ly.flat_off + nk + j + 1);
+    const size_t nk = (size_t)9 * Ly.plan.cin * Ly.plan.cout;
+    k.resize(nk + Ly.plan.cout);
+    for (size_t i = 0; i < k.size(); ++i) k[i] = (float)(i + 1);
+    buf.resize(Ly.plan.floats);
+    pack(Ly.plan, k.data(), k.data() + nk, buf.data());
+    for (size_t i = 0; i < buf.size(); ++i) fmap[Ly.off + i] = map_value(buf[i], Ly.flat_off);
   }
   // dgrad weights: W'[tap][c'][o'] = W[8 - tap][o'][c'] for the body layers (F -> F) and the output layer (16 -> F, the
   // outputs zero-padded to 16 input channels); layer 0 needs no input gradient
@@ -84,26 +84,23 @@ int ensure_train_state(dsen2_model* m) {
   size_t off = 0;
   for (size_t li = 1; li < L; ++li) {
     t->dg_off[li] = off;
-    off += align_up(packed_weight_floats(li + 1 == L ? t->out_geom : t->body_geom));
+    off += align_up((li + 1 == L ? t->out_plan : t->body_plan).weight_floats);
   }
   t->zero_off = off;
   off += align_up((size_t)F);
   t->dg_floats = off;
   std::vector<int> dmap(off, 0);
-  std::vector<float> buf;
   for (size_t li = 1; li < L; ++li) {
-    const Layer& Ly = m->layers[li];
-    const bool last = li + 1 == L;
-    const int cin2 = last ? 16 : Ly.cout, cout2 = Ly.cin;      // the dgrad convolution: forward outputs -> forward inputs
-    std::vector<float> k((size_t)9 * cin2 * cout2, 0.f);
+    const int ci = m->layers[li].plan.cin, co = m->layers[li].plan.cout;
+    const ConvPlan& g = li + 1 == L ? t->out_plan : t->body_plan;    // the dgrad convolution: forward outputs -> forward inputs
+    k.assign((size_t)9 * g.cin * g.cout, 0.f);
     for (int tap = 0; tap < 9; ++tap)
-      for (int c = 0; c < Ly.cout; ++c)
-        for (int o = 0; o < Ly.cin; ++o)
-          k[((size_t)tap * cin2 + c) * cout2 + o] = (float)(((size_t)(8 - tap) * Ly.cin + o) * Ly.cout + c + 1);
-    const PackGeom& g = last ? t->out_geom : t->body_geom;
-    buf.assign(packed_weight_floats(g), 0.f);
-    pack_conv_weights_host(k.data(), cin2, cout2, g, buf.data());
-    for (size_t i = 0; i < buf.size(); ++i) dmap[t->dg_off[li] + i] = map_value(buf[i], Ly.flat_off);
+      for (int c = 0; c < co; ++c)
+        for (int o = 0; o < ci; ++o)
+          k[((size_t)tap * g.cin + c) * g.cout + o] = (float)(((size_t)(8 - tap) * ci + o) * co + c + 1);
+    buf.resize(g.weight_floats);
+    pack(g, k.data(), nullptr, buf.data());
+    for (size_t i = 0; i < buf.size(); ++i) dmap[t->dg_off[li] + i] = map_value(buf[i], m->layers[li].flat_off);
   }
   HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
   HIP_TRY(hipMalloc((void**)&t->fwd_map, fmap.size() * sizeof(int)));
@@ -224,24 +221,24 @@ int dsen2_model_gradients(dsen2_model* m, const float* x10, const float* x20, co
     HIP_TRY(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, s));
     auto wgrad = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly, float scale) -> hipError_t {
       float* dw = grad + Ly.flat_off;
-      return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.cin, Ly.cout, scale, dw, dw + (size_t)9 * Ly.cin * Ly.cout, W.wg,
+      return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.plan.cin, Ly.plan.cout, scale, dw, dw + (size_t)9 * Ly.plan.cin * Ly.plan.cout, W.wg,
                                   W.wg_floats, s);
     };
     HIP_TRY(wgrad(W.X[d], F, W.gpad, 16, LO, 1.f));
     const size_t fbytes = pix * F * sizeof(float);
     HIP_TRY(hipMemsetAsync(W.G, 0, fbytes, s));
-    HIP_TRY(launch_conv3x3(make_params(W.gpad, t->dg + t->dg_off[m->layers.size() - 1], zero, W.G, W.G, n, h, w, 0, 1.f), t->out_geom,
-                           kEpiResidual, 0, s));
+    HIP_TRY(launch(t->out_plan, make_params(W.gpad, t->dg + t->dg_off[m->layers.size() - 1], zero, W.G, W.G, n, h, w, 0, 1.f), kEpiResidual,
+                   m->tune, s));
     // ---- residual blocks, last to first ----
     for (int l = d; l >= 1; --l) {
       const Layer& LA = m->layers[2 * l - 1];
       const Layer& LB = m->layers[2 * l];
       HIP_TRY(wgrad(W.T[l], F, W.G, F, LB, 0.1f));
       HIP_TRY(hipMemsetAsync(W.DU, 0, fbytes, s));
-      HIP_TRY(launch_conv3x3(make_params(W.G, t->dg + t->dg_off[2 * l], zero, W.DU, W.DU, n, h, w, 0, 0.1f), t->body_geom, kEpiResidual, 0, s));
+      HIP_TRY(launch(t->body_plan, make_params(W.G, t->dg + t->dg_off[2 * l], zero, W.DU, W.DU, n, h, w, 0, 0.1f), kEpiResidual, m->tune, s));
       HIP_TRY(launch_relu_mask(W.DU, W.T[l], pix * F, s));
       HIP_TRY(wgrad(W.X[l - 1], F, W.DU, F, LA, 1.f));
-      HIP_TRY(launch_conv3x3(make_params(W.DU, t->dg + t->dg_off[2 * l - 1], zero, W.G, W.G, n, h, w, 0, 1.f), t->body_geom, kEpiResidual, 0, s));
+      HIP_TRY(launch(t->body_plan, make_params(W.DU, t->dg + t->dg_off[2 * l - 1], zero, W.G, W.G, n, h, w, 0, 1.f), kEpiResidual, m->tune, s));
     }
     // ---- first convolution ----
     HIP_TRY(launch_relu_mask(W.G, W.X[0], pix * F, s));
@@ -296,7 +293,7 @@ int dsen2_conv3x3_wgrad(const float* dev_a, const float* dev_g, float* dev_dw, f
     const size_t wf = wgrad_workspace_floats(n, h, w, ca, cg);
     if (wf == 0) return fail(DSEN2_ERR_INVALID, "no wgrad kernel for %d -> %d channels", ca, cg);
     hipStream_t s = (hipStream_t)stream;
-    return launch_once_with_temp("wgrad", {nullptr, wf * sizeof(float)}, {nullptr, 0}, s, [&](char* dev) {
+    return launch_once_with_temp("wgrad", nullptr, wf * sizeof(float), s, [&](char* dev) {
       return launch_conv3x3_wgrad(dev_a, ca, dev_g, cg, n, h, w, ci, co, scale, dev_dw, dev_db, reinterpret_cast<float*>(dev), wf, s);
     });
   });

@@ -813,14 +813,17 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body16w_x3_chain_kernel(co
   body16w<CINW, COUT, kEpiRelu, 0, true, true>(p, 0, chain);
 }
 
-template <int CINW, int COUT, int EPI, int ABL = 0>
+template <int CINW, int COUT, int EPI, int ABL = 0, bool X3 = false>
 static hipError_t launch_body16w_one(ConvParams p, hipStream_t stream, int grid_cap) {
-  auto kern = conv3x3_body16w_kernel<CINW, COUT, EPI, ABL>;
+  auto kern = [] {
+    if constexpr (X3) return conv3x3_body16w_x3_kernel<CINW, COUT, EPI>;
+    else return conv3x3_body16w_kernel<CINW, COUT, EPI, ABL>;
+  }();
   static KernelOnce once;
   int cus = 0;
   hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), LDS_BYTES, &cus);
   if (e != hipSuccess) return e;
-  // per-image buffer descriptors: byte offsets below 2^31 (bit 31 marks a pixel outside the image)
+  // per-image buffer descriptors (X3: of the two-plane tensors): byte offsets below 2^31 (bit 31 marks a pixel outside the image)
   if ((size_t)p.h * p.w * COUT >= ((size_t)1 << 29)) return hipErrorInvalidValue;
   p.tiles_x = (p.w + TW - 1) / TW;
   p.tiles_y = (p.h + TH - 1) / TH;
@@ -830,41 +833,6 @@ static hipError_t launch_body16w_one(ConvParams p, hipStream_t stream, int grid_
   if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), LDS_BYTES, stream, p, (int)items);
   return hipGetLastError();
-}
-
-template <int CINW, int COUT, int EPI>
-static hipError_t launch_body16w_x3_one(ConvParams p, hipStream_t stream) {
-  auto kern = conv3x3_body16w_x3_kernel<CINW, COUT, EPI>;
-  static KernelOnce once;
-  int cus = 0;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), LDS_BYTES, &cus);
-  if (e != hipSuccess) return e;
-  // per-image descriptors of the two-plane tensors (4 bytes per value): byte offsets below 2^31
-  if ((size_t)p.h * p.w * COUT >= ((size_t)1 << 29)) return hipErrorInvalidValue;
-  p.tiles_x = (p.w + TW - 1) / TW;
-  p.tiles_y = (p.h + TH - 1) / TH;
-  const long long items = (long long)p.n * p.tiles_x * p.tiles_y * (COUT / 128);
-  if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-  const int grid = (int)(items < cus ? items : cus);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), LDS_BYTES, stream, p, (int)items);
-  return hipGetLastError();
-}
-
-template <int F>
-static hipError_t launch_body16w_x3_feat(const ConvParams& p, int epilogue, hipStream_t stream) {
-  if (epilogue == kEpiRelu) return launch_body16w_x3_one<F / 2, F, kEpiRelu>(p, stream);
-  if (epilogue == kEpiResidual) return launch_body16w_x3_one<F / 2, F, kEpiResidual>(p, stream);
-  if (epilogue == kEpiResidualF32) return launch_body16w_x3_one<F / 2, F, kEpiResidualF32>(p, stream);
-  return hipErrorInvalidValue;
-}
-
-hipError_t launch_conv3x3_body16w_x3(const ConvParams& p, int feat, int epilogue, hipStream_t stream) {
-  if (!p.in || !p.wpk || !p.bias) return hipErrorInvalidValue;
-  if (epilogue != kEpiRelu && (!p.aux || !p.out2)) return hipErrorInvalidValue;
-  if (epilogue != kEpiResidual && !p.out) return hipErrorInvalidValue;
-  if (feat == 128) return launch_body16w_x3_feat<128>(p, epilogue, stream);
-  if (feat == 256) return launch_body16w_x3_feat<256>(p, epilogue, stream);
-  return hipErrorInvalidValue;
 }
 
 template <int CINW, int COUT, int ABL = 0, bool X3 = false>
@@ -935,11 +903,11 @@ hipError_t launch_conv3x3_body16w_chain(const ConvParams& p, const ChainArgs& c,
   return hipErrorInvalidValue;
 }
 
-template <int F>
+template <int F, bool X3>
 static hipError_t launch_body16w_feat(const ConvParams& p, int epilogue, int ablate, hipStream_t stream, int grid_cap) {
 #ifdef DSEN2_DIAG
 #define DSEN2_ABL(M)                                                                                         \
-  if (ablate == M)                                                                                           \
+  if (!X3 && ablate == M)                                                                                    \
     return epilogue == kEpiRelu       ? launch_body16w_one<F / 2, F, kEpiRelu, M>(p, stream, grid_cap)                  \
            : epilogue == kEpiResidual ? launch_body16w_one<F / 2, F, kEpiResidual, M>(p, stream, grid_cap)              \
                                       : launch_body16w_one<F / 2, F, kEpiResidualF32, M>(p, stream, grid_cap);
@@ -947,16 +915,18 @@ static hipError_t launch_body16w_feat(const ConvParams& p, int epilogue, int abl
 #undef DSEN2_ABL
 #endif
   if (ablate != 0) return hipErrorInvalidValue;
-  if (epilogue == kEpiRelu) return launch_body16w_one<F / 2, F, kEpiRelu>(p, stream, grid_cap);
-  if (epilogue == kEpiResidual) return launch_body16w_one<F / 2, F, kEpiResidual>(p, stream, grid_cap);
-  if (epilogue == kEpiResidualF32) return launch_body16w_one<F / 2, F, kEpiResidualF32>(p, stream, grid_cap);
+  if (epilogue == kEpiRelu) return launch_body16w_one<F / 2, F, kEpiRelu, 0, X3>(p, stream, grid_cap);
+  if (epilogue == kEpiResidual) return launch_body16w_one<F / 2, F, kEpiResidual, 0, X3>(p, stream, grid_cap);
+  if (epilogue == kEpiResidualF32) return launch_body16w_one<F / 2, F, kEpiResidualF32, 0, X3>(p, stream, grid_cap);
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv3x3_body16w(const ConvParams& p, int feat, int epilogue, int ablate, hipStream_t stream, int grid_cap) {
+hipError_t launch_conv3x3_body16w(const ConvParams& p, int feat, int epilogue, bool x3, int ablate, hipStream_t stream, int grid_cap) {
+  if (!p.in || !p.wpk || !p.bias) return hipErrorInvalidValue;
   if (epilogue != kEpiRelu && (!p.aux || !p.out2)) return hipErrorInvalidValue;
-  if (feat == 128) return launch_body16w_feat<128>(p, epilogue, ablate, stream, grid_cap);
-  if (feat == 256) return launch_body16w_feat<256>(p, epilogue, ablate, stream, grid_cap);
+  if (epilogue != kEpiResidual && !p.out) return hipErrorInvalidValue;
+  if (feat == 128) return x3 ? launch_body16w_feat<128, true>(p, epilogue, ablate, stream, grid_cap) : launch_body16w_feat<128, false>(p, epilogue, ablate, stream, grid_cap);
+  if (feat == 256) return x3 ? launch_body16w_feat<256, true>(p, epilogue, ablate, stream, grid_cap) : launch_body16w_feat<256, false>(p, epilogue, ablate, stream, grid_cap);
   return hipErrorInvalidValue;
 }
 

@@ -350,25 +350,24 @@ static hipError_t launch_body32_one(const ConvParams& p, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// per-image buffer descriptors address bytes with 32 bits (and keep 0x80000000 out of range)
-bool body32_supports(const ConvParams& p, int cout) { return (size_t)p.h * p.w * cout * 4 < 0x80000000ull; }
-
 template <int F>
-static hipError_t launch_body32_feat(const ConvParams& p, int epilogue, int sub, hipStream_t stream) {
-  if (epilogue == kEpiRelu)
-    return sub == 1   ? launch_body32_one<F, F, kEpiRelu, 0, 0, false>(p, stream)
-           : sub == 0 ? launch_body32_one<F, F, kEpiRelu, 0, 0, true>(p, stream)
-                      : launch_body32_one<F, F, kEpiRelu, 0, 0, true, true>(p, stream);
-  if (sub == 2) return launch_body32_one<F, F, kEpiResidual, 0, 0, false, true>(p, stream);
-  if (sub == 3) return launch_body32_one<F, F, kEpiResidual, 0, 0, true, true>(p, stream);
-  return launch_body32_one<F, F, kEpiResidual, 0, 2, false>(p, stream);
+static hipError_t launch_body32_feat(const ConvParams& p, int epilogue, Body32Form form, hipStream_t stream) {
+  const bool relu = epilogue == kEpiRelu;
+#ifdef DSEN2_DIAG
+  if (form == Body32Form::Plain || form == Body32Form::StaggerA) {
+    if (!relu) return launch_body32_one<F, F, kEpiResidual, 0, 2, false>(p, stream);
+    return form == Body32Form::Plain ? launch_body32_one<F, F, kEpiRelu, 0, 0, false>(p, stream) : launch_body32_one<F, F, kEpiRelu, 0, 0, true>(p, stream);
+  }
+  if (form == Body32Form::DeferStaggerA && !relu) return launch_body32_one<F, F, kEpiResidual, 0, 0, false, true>(p, stream);
+#else
+  if (form != Body32Form::DeferStagger) return hipErrorInvalidValue;     // the other forms exist in the diagnostic build only
+#endif
+  return relu ? launch_body32_one<F, F, kEpiRelu, 0, 0, true, true>(p, stream) : launch_body32_one<F, F, kEpiResidual, 0, 0, true, true>(p, stream);
 }
 
-// sub: 3 = deferred epilogue + wave-group stagger for both convolutions (default);
-//      2 = the same with conv-B not staggered; 0 = no deferral: conv-A staggered, conv-B with the whole residual
-//      tile prefetched under the last step; 1 = 0 without the stagger
-hipError_t launch_conv3x3_body32(const ConvParams& p, int feat, int epilogue, int sub, int ablate, hipStream_t stream) {
-  if (!body32_supports(p, feat)) return hipErrorInvalidValue;
+hipError_t launch_conv3x3_body32(const ConvParams& p, int feat, int epilogue, Body32Form form, int ablate, hipStream_t stream) {
+  // per-image buffer descriptors address bytes with 32 bits (and keep 0x80000000 out of range)
+  if ((size_t)p.h * p.w * feat * 4 >= 0x80000000ull) return hipErrorNotSupported;
 #ifdef DSEN2_DIAG
   if (feat == 128 && ablate != 0) {
 #define DSEN2_ABL(M)                                                                             \
@@ -381,8 +380,8 @@ hipError_t launch_conv3x3_body32(const ConvParams& p, int feat, int epilogue, in
   }
 #endif
   if (ablate != 0) return hipErrorInvalidValue;     // timing-only ablations exist in the diagnostic build only
-  if (feat == 128) return launch_body32_feat<128>(p, epilogue, sub, stream);
-  if (feat == 256) return launch_body32_feat<256>(p, epilogue, sub, stream);
+  if (feat == 128) return launch_body32_feat<128>(p, epilogue, form, stream);
+  if (feat == 256) return launch_body32_feat<256>(p, epilogue, form, stream);
   return hipErrorInvalidValue;
 }
 

@@ -289,7 +289,7 @@ static hipError_t launch_first_one(const ConvParams& p, const FirstInputs& f, hi
   return hipGetLastError();
 }
 
-// p.in = x10, p.aux = x20 (NCHW), p.wpk / p.bias: weights packed with PackGeom{16, 128, 16, cout, .}; p.out NHWC fp32
+// p.in = x10, p.aux = x20 (NCHW), p.wpk / p.bias: weights packed for the tile kernel (KC 16, NT 128); p.out NHWC fp32
 // (kEpiRelu only).  hipErrorNotSupported: channel counts
 // other than 10 / 12 (the generic pack_inputs + conv3x3_mfma path handles those).
 hipError_t launch_conv3x3_first(const ConvParams& p, const FirstInputs& f, int cout, int epilogue, hipStream_t stream, int ablate) {
@@ -298,7 +298,7 @@ hipError_t launch_conv3x3_first(const ConvParams& p, const FirstInputs& f, int c
   if ((size_t)p.h * p.w * 6 * 4 >= ((size_t)1 << 31)) return hipErrorNotSupported;               // 32-bit offsets inside one image
   if (!p.in || !p.aux || (f.c60 > 0 && !f.x60) || !p.out) return hipErrorInvalidValue;
   if ((size_t)p.h * p.w * (size_t)cout * 4 >= ((size_t)1 << 40)) return hipErrorInvalidValue;
-#define DSEN2_FIRST(CR, CO) \
+#define DSEN2_CASE(CR, CO) \
   if (creal == CR && cout == CO) return launch_first_one<CR, CO, kEpiRelu>(p, f, stream);
   if (epilogue != kEpiRelu) return hipErrorInvalidValue;      // the (hi, lo) / (hi | xl, lo16) plane forms: conv3x3_first16.hip
 #ifdef DSEN2_DIAG
@@ -312,8 +312,8 @@ hipError_t launch_conv3x3_first(const ConvParams& p, const FirstInputs& f, int c
     if (ablate == 6) return launch_first_one<10, 128, kEpiRelu, 6>(p, f, stream);
   }
 #endif
-  DSEN2_FIRST(10, 128) DSEN2_FIRST(12, 128) DSEN2_FIRST(10, 256) DSEN2_FIRST(12, 256)
-#undef DSEN2_FIRST
+  DSEN2_CASE(10, 128) DSEN2_CASE(12, 128) DSEN2_CASE(10, 256) DSEN2_CASE(12, 256)
+#undef DSEN2_CASE
   return hipErrorNotSupported;
 }
 

@@ -352,14 +352,6 @@ static hipError_t launch_first16_one(const ConvParams& p, const FirstInputs& f, 
 
 size_t first16_weight_u16(int cout, bool x3) { return (size_t)(cout / first16::NT) * (x3 ? 2 : 1) * first16::W_PLANE_U16; }
 
-static inline uint16_t first16_bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 // kernel HWIO fp32 (3, 3, cin <= 16, cout) -> [slab][plane: wh (| wl)][tap][k half][o: 128][8] bf16, zero in the unused
 // channel slots; wh = RNE bf16 of w, wl = RNE bf16 of w - wh (x3 only) — pack_conv_weights_bf16x3_host's split
 void pack_first16_weights_host(const float* k, int cin, int cout, bool x3, uint16_t* dst) {
@@ -375,14 +367,14 @@ void pack_first16_weights_host(const float* k, int cin, int cout, bool x3, uint1
               uint16_t v = 0;
               if (c < cin) {
                 const float w = k[((size_t)tap * cin + c) * cout + oc];
-                const uint16_t hb = first16_bf16_rne(w);
+                const uint16_t hb = f32_to_bf16_rne(w);
                 if (q == 0) {
                   v = hb;
                 } else {
                   const uint32_t hu = (uint32_t)hb << 16;
                   float wh;
                   memcpy(&wh, &hu, 4);
-                  v = first16_bf16_rne(w - wh);
+                  v = f32_to_bf16_rne(w - wh);
                 }
               }
               dst[i] = v;
@@ -398,10 +390,10 @@ hipError_t launch_conv3x3_first16(const ConvParams& p, const FirstInputs& f, int
   if ((size_t)p.h * p.w * 6 * 4 >= ((size_t)1 << 31)) return hipErrorNotSupported;               // 32-bit offsets inside one image
   if (!p.in || !p.aux || (f.c60 > 0 && !f.x60) || !p.out || !p.out2 || !p.wpk || !p.bias) return hipErrorInvalidValue;
   if ((size_t)p.h * p.w * (size_t)cout * 4 >= ((size_t)1 << 40)) return hipErrorInvalidValue;
-#define DSEN2_FIRST16(CR, CO)                                                                               \
+#define DSEN2_CASE(CR, CO)                                                                               \
   if (creal == CR && cout == CO) return x3 ? launch_first16_one<CR, CO, true>(p, f, stream) : launch_first16_one<CR, CO, false>(p, f, stream);
-  DSEN2_FIRST16(10, 128) DSEN2_FIRST16(12, 128) DSEN2_FIRST16(10, 256) DSEN2_FIRST16(12, 256)
-#undef DSEN2_FIRST16
+  DSEN2_CASE(10, 128) DSEN2_CASE(12, 128) DSEN2_CASE(10, 256) DSEN2_CASE(12, 256)
+#undef DSEN2_CASE
   return hipErrorNotSupported;
 }
 

@@ -300,158 +300,24 @@ static hipError_t launch_one(const ConvParams& p, hipStream_t stream) {
   return hipGetLastError();
 }
 
-bool conv_pack_geometry(int cin, int cout, int epilogue, const Tuning& tune, PackGeom* g) {
-  if (cin <= 0 || cout <= 0) return false;
-  if (epilogue == kEpiSkipNCHW) {
-    if (cout > 32 || (cin != 128 && cin != 256)) return false;
-    // variant 8: conv3x3_out_mfma.hip where the shape fits, else conv3x3_out.hip (the buffer holds both packings);
-    // variant 9: conv3x3_out.hip always
-    if (cout <= 8 && (tune.out_variant == 2 || tune.out_variant == 3)) {
-      *g = PackGeom{16, 8, cin, 8, tune.out_variant == 2 ? 8 : 9};
-      return true;
-    }
-    *g = PackGeom{32, 32, cin, 32, 0};
-    return true;
-  }
-  if (cout != 128 && cout != 256) return false;
-  if (cin <= 16) {
-    // first layer: variant = number of real channels whose MFMAs are issued (10 / 12: the Sentinel-2 band groups;
-    // 0 = all 16 padded channels, the reference structure)
-    *g = PackGeom{16, 128, 16, cout, (tune.body_variant != 0 && (cin == 10 || cin == 12)) ? cin : 0};
-    return true;
-  }
-  if (cin == cout) {
-    // every structure of the F->F body convolution reads the same packing (KC = 32, NT = 128):
-    // 11-14 = conv3x3_body32.hip sub-variants 0-3 (14 = default); 0 = one tile per workgroup (this file)
-    *g = PackGeom{32, 128, cin, cout, tune.body_variant >= 11 && tune.body_variant <= 14 ? tune.body_variant : 0};
-    return true;
-  }
-  return false;
-}
-
-size_t packed_weight_floats(const PackGeom& g) {
-  return (size_t)9 * g.cin_pad * g.cout_pad + (g.variant == 8 ? out_mfma_weight_floats(g.cin_pad) : 0);
-}
-
-void pack_conv_weights_host(const float* k, int cin, int cout, const PackGeom& g, float* dst) {
-  if (g.variant == 8 || g.variant == 9) {          // the output kernels have their own operand orders
-    pack_out_valu_weights_host(k, cin, cout, dst);
-    if (g.variant == 8) pack_out_mfma_weights_host(k, cin, cout, dst + (size_t)9 * cin * 8);
-    return;
-  }
-  const int ncc = g.cin_pad / g.kc, nslab = g.cout_pad / g.nt, ng = g.kc / 4;
-  size_t i = 0;
-  for (int slab = 0; slab < nslab; ++slab)
-    for (int cc = 0; cc < ncc; ++cc)
-      for (int tap = 0; tap < 9; ++tap)
-        for (int gg = 0; gg < ng; ++gg)
-          for (int o = 0; o < g.nt; ++o)
-            for (int j = 0; j < 4; ++j, ++i) {
-              const int c = cc * g.kc + 4 * gg + j, oc = slab * g.nt + o;
-              dst[i] = (c < cin && oc < cout) ? k[((size_t)tap * cin + c) * cout + oc] : 0.f;
-            }
-}
-
-static inline uint16_t f32_to_bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-void pack_conv_weights_bf16_host(const float* k, int cin, int cout, int chunk_ch, bool perm16, uint16_t* dst) {
-  // [slab][cc (chunk_ch channels)][step][g (8 channels)][o (128)][j (8)]: one (slab, cc, step) chunk is the LDS image.
-  // perm16 (conv3x3_body16w.hip's format): step s carries tap (dy, dx) = (s % 3, s / 3) — the kernel walks the taps
-  // dx-major to keep its pixel-row fragments over the three dy of one dx; otherwise step = tap.
-  const int ncc = cin / chunk_ch, nslab = cout / 128, ng = chunk_ch / 8;
-  size_t i = 0;
-  for (int slab = 0; slab < nslab; ++slab)
-    for (int cc = 0; cc < ncc; ++cc)
-      for (int step = 0; step < 9; ++step) {
-        const int tap = perm16 ? (step % 3) * 3 + step / 3 : step;
-        for (int g = 0; g < ng; ++g)
-          for (int o = 0; o < 128; ++o)
-            for (int j = 0; j < 8; ++j, ++i) {
-              const int ch = perm16 ? 32 * (o >> 5) + 8 * ((o & 15) >> 2) + 4 * ((o >> 4) & 1) + (o & 3) : o;
-              const int c = cc * chunk_ch + 8 * g + j, oc = slab * 128 + ch;
-              dst[i] = f32_to_bf16_rne(k[((size_t)tap * cin + c) * cout + oc]);
-            }
-      }
-}
-
-void pack_conv_weights_bf16x3_host(const float* k, int cin, int cout, uint16_t* dst) {
-  // a virtual (3, 3, 3*cin, cout) kernel: input chunk 3*cc + j of 32 channels = plane (wh, wl, wh)[j] of real chunk cc — the
-  // order in which conv3x3_body16w.hip (X3) walks the activation planes (xh, xh, xl)
-  const int vcin = 3 * cin;
-  std::vector<float> v((size_t)9 * vcin * cout);
-  for (int tap = 0; tap < 9; ++tap)
-    for (int c = 0; c < cin; ++c)
-      for (int o = 0; o < cout; ++o) {
-        const float w = k[((size_t)tap * cin + c) * cout + o];
-        const uint16_t hb = f32_to_bf16_rne(w);
-        uint32_t hu = (uint32_t)hb << 16;
-        float wh;
-        memcpy(&wh, &hu, 4);
-        const float wl = w - wh;                       // exact; rounded to bf16 by the packer below
-        const int cc = c / 32, j = c % 32;
-        float* base = v.data() + ((size_t)tap * vcin + (size_t)cc * 96 + j) * cout + o;
-        base[0] = wh;
-        base[(size_t)32 * cout] = wl;
-        base[(size_t)64 * cout] = wh;
-      }
-  pack_conv_weights_bf16_host(v.data(), vcin, cout, 32, true, dst);
-}
-
-hipError_t launch_conv3x3(const ConvParams& p, const PackGeom& geom, int epilogue, int ablate, hipStream_t stream) {
-  const int cin_pad = geom.cin_pad, cout_pad = geom.cout_pad;
-  if ((geom.variant == 8 || geom.variant == 9) && epilogue == kEpiSkipNCHW) {
-    if (geom.variant == 8) {
-      ConvParams pm = p;
-      pm.wpk = p.wpk + (size_t)9 * cin_pad * 8;
-      bool taken = false;
-      const hipError_t e = launch_conv3x3_out_mfma(pm, cin_pad, stream, &taken, ablate);
-      if (e != hipSuccess || taken) return e;
-    }
-    return launch_conv3x3_out_valu(p, cin_pad, stream);
-  }
-  // 11-14: the DMA-fed kernel (conv3x3_body32.hip) and its sub-variants.  An image it cannot address (>= 2 GiB of
-  // activations) is an error, not a silent switch of kernels: dsen2's entry points reject such shapes up front.
-  if (geom.variant >= 11 && geom.variant <= 14 && cin_pad == cout_pad && epilogue != kEpiSkipNCHW)
-    return launch_conv3x3_body32(p, cin_pad, epilogue, geom.variant - 11, ablate, stream);
-  if (ablate != 0) return hipErrorInvalidValue;
-  if (cin_pad == 16 && epilogue == kEpiReluSplit) {          // first convolution of a precision-1 model
-    if (!p.out2) return hipErrorInvalidValue;
-#define DSEN2_FIRST(CO, CR) return launch_one<16, 16, CO, 128, kEpiReluSplit, 8, 2, CR>(p, stream);
-    if (cout_pad == 128) { if (geom.variant == 10) DSEN2_FIRST(128, 10) if (geom.variant == 12) DSEN2_FIRST(128, 12) DSEN2_FIRST(128, 0) }
-    if (cout_pad == 256) { if (geom.variant == 10) DSEN2_FIRST(256, 10) if (geom.variant == 12) DSEN2_FIRST(256, 12) DSEN2_FIRST(256, 0) }
-#undef DSEN2_FIRST
-    return hipErrorInvalidValue;
-  }
-  if (cin_pad == 16 && epilogue == kEpiRelu && (geom.variant == 10 || geom.variant == 12)) {
-    if (cout_pad == 128)
-      return geom.variant == 10 ? launch_one<16, 16, 128, 128, kEpiRelu, 8, 2, 10>(p, stream)
-                                : launch_one<16, 16, 128, 128, kEpiRelu, 8, 2, 12>(p, stream);
-    if (cout_pad == 256)
-      return geom.variant == 10 ? launch_one<16, 16, 256, 128, kEpiRelu, 8, 2, 10>(p, stream)
-                                : launch_one<16, 16, 256, 128, kEpiRelu, 8, 2, 12>(p, stream);
-  }
-#define DSEN2_CASE(CI, KC_, CO, NT_, EP) \
-  if (cin_pad == CI && cout_pad == CO && epilogue == EP) return launch_one<CI, KC_, CO, NT_, EP>(p, stream);
-  DSEN2_CASE(16, 16, 128, 128, kEpiRelu)
-  DSEN2_CASE(128, 32, 128, 128, kEpiRelu)
-  DSEN2_CASE(128, 32, 128, 128, kEpiResidual)
-  DSEN2_CASE(128, 32, 32, 32, kEpiSkipNCHW)
-  DSEN2_CASE(16, 16, 256, 128, kEpiRelu)
-  DSEN2_CASE(256, 32, 256, 128, kEpiRelu)
-  DSEN2_CASE(256, 32, 256, 128, kEpiResidual)
-  DSEN2_CASE(256, 32, 32, 32, kEpiSkipNCHW)
-  // 16 -> F with the residual epilogue: the input gradient of the output convolution (capi_train.hip), from dL/dout padded to
-  // 16 channels, with flipped and transposed weights
-  DSEN2_CASE(16, 16, 128, 128, kEpiResidual)
-  DSEN2_CASE(16, 16, 256, 128, kEpiResidual)
+template <int F>
+static hipError_t launch_tile_feat(const ConvParams& p, int cin_pad, int cout_pad, int epilogue, int real_channels, hipStream_t stream) {
+  if (epilogue == kEpiReluSplit && !p.out2) return hipErrorInvalidValue;
+#define DSEN2_CASE(CI, KC_, CO, NT_, EP, CR) \
+  if (cin_pad == CI && cout_pad == CO && epilogue == EP && real_channels == CR) return launch_one<CI, KC_, CO, NT_, EP, 8, 2, CR>(p, stream);
+  // 16 -> F: the first convolution (CR: the MFMAs of the 10 / 12 real input channels only; kEpiReluSplit: of a precision-1 model);
+  // kEpiResidual: the input gradient of the output convolution (capi_train.hip), from dL/dout padded to 16 channels
+  DSEN2_CASE(16, 16, F, 128, kEpiRelu, 0) DSEN2_CASE(16, 16, F, 128, kEpiRelu, 10) DSEN2_CASE(16, 16, F, 128, kEpiRelu, 12)
+  DSEN2_CASE(16, 16, F, 128, kEpiReluSplit, 0) DSEN2_CASE(16, 16, F, 128, kEpiReluSplit, 10) DSEN2_CASE(16, 16, F, 128, kEpiReluSplit, 12)
+  DSEN2_CASE(16, 16, F, 128, kEpiResidual, 0)
+  DSEN2_CASE(F, 32, F, 128, kEpiRelu, 0) DSEN2_CASE(F, 32, F, 128, kEpiResidual, 0) DSEN2_CASE(F, 32, 32, 32, kEpiSkipNCHW, 0)
 #undef DSEN2_CASE
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_conv3x3_tile(const ConvParams& p, int cin_pad, int cout_pad, int epilogue, int real_channels, hipStream_t stream) {
+  if (cin_pad == 256 || cout_pad == 256) return launch_tile_feat<256>(p, cin_pad, cout_pad, epilogue, real_channels, stream);
+  return launch_tile_feat<128>(p, cin_pad, cout_pad, epilogue, real_channels, stream);
 }
 
 }  // namespace dsen2

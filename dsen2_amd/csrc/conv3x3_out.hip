@@ -176,7 +176,7 @@ static hipError_t launch_out_valu_one(const ConvParams& p, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// weights packed by pack_out_valu_weights_host (PackGeom variant 8)
+// weights packed by pack_out_valu_weights_host
 hipError_t launch_conv3x3_out_valu(const ConvParams& p, int feat, hipStream_t stream) {
   if (p.cout_real < 1 || p.cout_real > 8) return hipErrorInvalidValue;
   const int nslot = (p.cout_real + 1) / 2;

@@ -386,7 +386,7 @@ static bool out_mfma_geometry(const ConvParams& p, int feat, int cus, OutMfmaGeo
 }
 
 template <int F, int CL>
-static hipError_t launch_out_mfma_one(const ConvParams& p, hipStream_t stream, bool* taken, int ablate) {
+static hipError_t launch_out_mfma_one(const ConvParams& p, hipStream_t stream, int ablate) {
   auto kern = conv3x3_out_mfma_kernel<F, CL>;
   static KernelOnce once;
   int cus = 0;
@@ -394,23 +394,21 @@ static hipError_t launch_out_mfma_one(const ConvParams& p, hipStream_t stream, b
   if (e != hipSuccess) return e;
   OutMfmaGeom g;
   size_t lds = 0;
-  if (!out_mfma_geometry(p, F, cus, &g, &lds)) { *taken = false; return hipSuccess; }
-  *taken = true;
+  if (!out_mfma_geometry(p, F, cus, &g, &lds)) return hipErrorNotSupported;
   g.ablate = ablate;
   const unsigned grid = (unsigned)(g.njobs < cus ? g.njobs : cus);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(outm::THREADS), lds, stream, p, g);
   return hipGetLastError();
 }
 
-// p.wpk = the weights packed by pack_out_mfma_weights_host.  *taken = false (and nothing launched) when the shape does not
+// p.wpk = the weights packed by pack_out_mfma_weights_host.  hipErrorNotSupported (and nothing launched) when the shape does not
 // fit this kernel (row of Q too wide for LDS, more than 6 outputs): the caller then uses conv3x3_out.hip.
-hipError_t launch_conv3x3_out_mfma(const ConvParams& p, int feat, hipStream_t stream, bool* taken, int ablate) {
-  *taken = false;
-  if (p.cout_real < 1 || p.cout_real > 6) return hipSuccess;
+hipError_t launch_conv3x3_out_mfma(const ConvParams& p, int feat, hipStream_t stream, int ablate) {
+  if (p.cout_real < 1 || p.cout_real > 6) return hipErrorNotSupported;
   const bool small = p.cout_real <= 2;
-  if (feat == 128) return small ? launch_out_mfma_one<128, 1>(p, stream, taken, ablate) : launch_out_mfma_one<128, 3>(p, stream, taken, ablate);
-  if (feat == 256) return small ? launch_out_mfma_one<256, 1>(p, stream, taken, ablate) : launch_out_mfma_one<256, 3>(p, stream, taken, ablate);
-  return hipSuccess;
+  if (feat == 128) return small ? launch_out_mfma_one<128, 1>(p, stream, ablate) : launch_out_mfma_one<128, 3>(p, stream, ablate);
+  if (feat == 256) return small ? launch_out_mfma_one<256, 1>(p, stream, ablate) : launch_out_mfma_one<256, 3>(p, stream, ablate);
+  return hipErrorNotSupported;
 }
 
 size_t out_mfma_weight_floats(int cin) { return (size_t)2 * (cin / 64) * 2048; }

@@ -1,4 +1,6 @@
-// Internal declarations shared by the HIP translation units of libdsen2_hip.so (gfx950 only).
+// Internal declarations shared by the HIP translation units of libdsen2_hip.so (gfx950 only): the tensor layouts, ConvParams,
+// Tuning, and one launcher per kernel file.  Which launcher runs a layer, which weight format it reads and how many floats that
+// is, is decided in conv_plan.h.  A launcher that does not take a shape returns hipErrorNotSupported and has launched nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -10,7 +12,8 @@ namespace dsen2 {
 
 // ---- data layout ------------------------------------------------------------------------------
 // Activations inside the network: NHWC float32, [n][y][x][c], c contiguous (512 B per pixel at F=128).
-// Packed conv weights (one buffer per Conv2D):
+// Packed conv weights of the tile kernel (conv3x3_mfma.hip) and of conv3x3_body32.hip (conv_plan.hip: pack_tile_weights; the
+// other kernels' formats are described at their packers, there or beside the kernel):
 //   wpk[slab][cc][tap][g][o][j]  float32
 //     slab : output-channel slab of NT channels handled by one workgroup      (COUT_PAD / NT)
 //     cc   : input-channel chunk of KC channels                               (CIN_PAD / KC)
@@ -50,17 +53,29 @@ struct ConvParams {
 
 // Kernel-structure choices of a model.  The product library always uses the defaults; the diagnostic build
 // (-DDSEN2_DIAG, tools/ only) can change them through dsen2_diag_set for A/B measurements.
+// First: Direct = conv3x3_first.hip / conv3x3_first16.hip where they take the band groups, else the tile kernel issuing the
+// MFMAs of the 10 / 12 real channels only; Tile16 = the tile kernel over all 16 padded channels.  Body (fp32 F->F):
+// conv3x3_body32.hip, or one tile per workgroup (conv3x3_mfma.hip, the independent first implementation).  Body32Form:
+// DeferStagger = deferred epilogue + wave-group stagger for both convolutions (the product's, the only one outside DSEN2_DIAG
+// builds); DeferStaggerA = conv-B not staggered; StaggerA = no deferral: conv-A staggered, conv-B with the whole residual tile
+// prefetched under the last step; Plain = StaggerA without the stagger.  Out (Cout <= 8): conv3x3_out_mfma.hip where the shape
+// fits it, else conv3x3_out.hip; always conv3x3_out.hip; Tile (and Cout > 8) = padded 32-wide block of conv3x3_mfma.hip.
+enum class FirstKernel { Direct, Tile16 };
+enum class BodyKernel { Body32, Tile };
+enum class Body32Form { StaggerA, Plain, DeferStaggerA, DeferStagger };
+enum class OutKernel { MfmaThenValu, Valu, Tile };
 struct Tuning {
-  int body_variant = 14;   // fp32 F->F body convolution: 11-14 = conv3x3_body32.hip sub-variants 0-3; 0 = one tile per
-                           // workgroup (conv3x3_mfma.hip, the independent first implementation)
-  int out_variant = 2;     // last layer, Cout <= 8: 2 = the tap-expanded matrix-core kernel (conv3x3_out_mfma.hip) where the
-                           // shape fits it, else the vector-unit kernel (conv3x3_out.hip); 3 = always the vector-unit kernel;
-                           // 0 (and Cout > 8) = padded 32-wide MFMA block (conv3x3_mfma.hip, the reference structure)
+  FirstKernel first = FirstKernel::Direct;
+  BodyKernel body = BodyKernel::Body32;
+  Body32Form body32 = Body32Form::DeferStagger;
+  OutKernel out = OutKernel::MfmaThenValu;
   int ablate = 0;          // timing-only ablation mask of the persistent body kernels (DSEN2_DIAG builds; wrong outputs)
   int grid_cap = 0;        // DSEN2_DIAG builds: launch at most this many workgroups of the bf16 body kernel (0 = one per CU)
   int first_ablate = 0;    // DSEN2_DIAG builds: timing-only ablation mask of the first convolution (conv3x3_first.hip)
   int out_ablate = 0;      // DSEN2_DIAG builds: timing-only ablation mask of conv3x3_out_mfma.hip
   int chain = 1;           // precision 1: one persistent launch over all body layers when the batch gives every CU whole patches
+  // the one-tile-per-workgroup kernels of conv3x3_mfma.hip for every layer shape (dsen2_conv3x3_nhwc_ref)
+  static Tuning reference() { Tuning t; t.first = FirstKernel::Tile16; t.body = BodyKernel::Tile; t.out = OutKernel::Tile; return t; }
 };
 
 // Per-kernel launch preparation: the dynamic-LDS attribute is a property of (kernel, device) and is set once per pair,
@@ -91,22 +106,20 @@ struct KernelOnce {
   }
 };
 
-// Supported (CIN_PAD, COUT_PAD, epilogue) combinations; returns hipErrorInvalidValue otherwise.
-struct PackGeom { int kc, nt, cin_pad, cout_pad, variant; };
-hipError_t launch_conv3x3(const ConvParams& p, const PackGeom& geom, int epilogue, int ablate, hipStream_t stream);
-// last layer, F -> Cout <= 8, on the vector units (conv3x3_out.hip; PackGeom variant 8, weights packed by
-// pack_out_valu_weights_host)
+// One 16 x 16 tile per workgroup (conv3x3_mfma.hip); layout above with (KC, NT) = (16, 128) for 16 -> F, (32, 128) for F -> F,
+// (32, 32) for F -> 32 (kEpiSkipNCHW).  real_channels (16 -> F): issue the MFMAs of the first 10 / 12 input channels only (0 = all).
+hipError_t launch_conv3x3_tile(const ConvParams& p, int cin_pad, int cout_pad, int epilogue, int real_channels, hipStream_t stream);
+// last layer, F -> Cout <= 8, on the vector units (conv3x3_out.hip; weights packed by pack_out_valu_weights_host)
 hipError_t launch_conv3x3_out_valu(const ConvParams& p, int feat, hipStream_t stream);
 void pack_out_valu_weights_host(const float* kernel_hwio, int cin, int cout, float* dst);
-// last layer, F -> Cout <= 6, the nine taps expanded into the M side of one GEMM (conv3x3_out_mfma.hip).  Its weights follow
-// the vector-unit kernel's in a variant-8 buffer (9 * cin * 8 floats further).  *taken = false: shape not supported,
-// nothing launched.
-hipError_t launch_conv3x3_out_mfma(const ConvParams& p, int feat, hipStream_t stream, bool* taken, int ablate = 0);
+// last layer, F -> Cout <= 6, the nine taps expanded into the M side of one GEMM (conv3x3_out_mfma.hip); weights packed by
+// pack_out_mfma_weights_host.  hipErrorNotSupported: the shape does not fit it (row of Q too wide for LDS, more than 6 outputs).
+hipError_t launch_conv3x3_out_mfma(const ConvParams& p, int feat, hipStream_t stream, int ablate = 0);
 size_t out_mfma_weight_floats(int cin);
 void pack_out_mfma_weights_host(const float* kernel_hwio, int cin, int cout, float* dst);
 // First convolution reading the NCHW inputs directly (conv3x3_first.hip, exact fp32): p.in = x10, p.aux = x20; weights packed
-// with PackGeom{16, 128, 16, cout, .}; epilogue kEpiRelu only (p.out fp32 NHWC).
-// hipErrorNotSupported for channel counts other than 10 / 12 (then: launch_pack_inputs + launch_conv3x3).
+// for the tile kernel (KC 16, NT 128); epilogue kEpiRelu only (p.out fp32 NHWC).
+// hipErrorNotSupported for channel counts other than 10 / 12 (then: launch_pack_inputs + launch_conv3x3_tile).
 struct FirstInputs { const float* x60; int c10, c20, c60; };
 hipError_t launch_conv3x3_first(const ConvParams& p, const FirstInputs& f, int cout, int epilogue, hipStream_t stream, int ablate = 0);
 // ... of a precision-1 / -2 model, on the bf16 matrix cores (conv3x3_first16.hip): same inputs; p.wpk = the buffer
@@ -116,31 +129,22 @@ hipError_t launch_conv3x3_first(const ConvParams& p, const FirstInputs& f, int c
 hipError_t launch_conv3x3_first16(const ConvParams& p, const FirstInputs& f, int cout, bool x3, hipStream_t stream);
 size_t first16_weight_u16(int cout, bool x3);
 void pack_first16_weights_host(const float* kernel_hwio, int cin, int cout, bool x3, uint16_t* dst);
-// DMA-fed fp32 kernel (conv3x3_body32.hip): F = 128 or 256, images < 2 GiB; weights packed with KC=32, NT=128
-bool body32_supports(const ConvParams& p, int cout);
-hipError_t launch_conv3x3_body32(const ConvParams& p, int feat, int epilogue, int sub, int ablate, hipStream_t stream);
-// kernel HWIO fp32 -> bf16 packed [slab][cc (chunk_ch channels)][step][g (groups of 8 ch)][o(128)][8]; dst holds
-// 9*cin*cout uint16.  step = tap, except with perm16 (conv3x3_body16w.hip walks the taps dx-major: step s carries tap
-// (dy, dx) = (s % 3, s / 3)).  perm16: row o of a slab holds output channel 32*(o>>5) + 8*((o&15)>>2) + 4*((o>>4)&1) + (o&3),
-// so that the two 16-row accumulators of a 32-channel pair give a lane 8 consecutive channels (conv3x3_body16w.hip)
-void pack_conv_weights_bf16_host(const float* kernel_hwio, int cin, int cout, int chunk_ch, bool perm16, uint16_t* dst);
+// DMA-fed fp32 kernel (conv3x3_body32.hip): F = 128 or 256; weights packed for the tile kernel (KC 32, NT 128).
+// hipErrorNotSupported: an image of 2 GiB or more (its per-image descriptors address bytes with 32 bits).
+hipError_t launch_conv3x3_body32(const ConvParams& p, int feat, int epilogue, Body32Form form, int ablate, hipStream_t stream);
 // bf16-operand body convolution, wide tile (conv3x3_body16w.hip), F = 128 or 256.  16-bit tensors are BLOCKED:
 // [n][C/8][h][w][8] (an 8-channel block = a plane of 16-byte pixels).  p.in bf16 blocked; weights packed by
-// pack_conv_weights_bf16_host(chunk_ch = 32, perm16).  kEpiRelu: p.out bf16 blocked.  kEpiResidual: the residual
+// pack_conv_weights_bf16_host (conv_plan.hip).  kEpiRelu: p.out bf16 blocked.  kEpiResidual: the residual
 // stream as two blocked 16-bit tensors p.aux (hi = bf16 rounding, the next operand) / p.out2 (lo), updated in place.
 // kEpiResidualF32: same inputs, result to p.out as fp32 NHWC (last block).  `ablate` != 0 only in DSEN2_DIAG builds.
-hipError_t launch_conv3x3_body16w(const ConvParams& p, int feat, int epilogue, int ablate, hipStream_t stream, int grid_cap = 0);
-// precision 2 ("bf16x3", conv3x3_body16w.hip X3): fp32-grade products on the bf16 matrix cores — every operand is two bf16
+// x3 = precision 2 ("bf16x3", conv3x3_body16w.hip X3): fp32-grade products on the bf16 matrix cores — every operand is two bf16
 // numbers (hi + lo), a product is hi*hi + hi*lo + lo*hi.  16-bit OPERAND tensors carry two planes per image,
 // [n][2][F/8][h][w][8] (hi | lo).  p.in = such a tensor; weights packed by pack_conv_weights_bf16x3_host.
 //   kEpiRelu: p.out = relu(conv + bias) as a two-plane tensor.
 //   kEpiResidual: the residual stream = p.aux (two planes: hi = bf16 rounding (ties away) of the bit pattern, xl = bf16(x - hi))
 //     + p.out2 (lo16: the low halves, one plane): (hi, lo16) hold the exact fp32 value as in precision 1; updated in place.
 //   kEpiResidualF32: same inputs, result to p.out as fp32 NHWC.
-hipError_t launch_conv3x3_body16w_x3(const ConvParams& p, int feat, int epilogue, hipStream_t stream);
-// kernel HWIO fp32 (3,3,cin,cout) -> the packed bf16 layout of a (3,3,3*cin,cout) convolution whose input chunk 3*cc + j holds
-// (wh, wl, wh)[j] of real chunk cc (wh = RNE bf16 of w, wl = RNE bf16 of w - wh); dst holds 27*cin*cout uint16
-void pack_conv_weights_bf16x3_host(const float* kernel_hwio, int cin, int cout, uint16_t* dst);
+hipError_t launch_conv3x3_body16w(const ConvParams& p, int feat, int epilogue, bool x3, int ablate, hipStream_t stream, int grid_cap = 0);
 // fp32 NHWC -> the precision-2 residual stream: hx [n][2][C/8][h][w][8] (hi | xl), lo [n][C/8][h][w][8] (c % 8 == 0)
 hipError_t launch_split3_f32(const float* in_nhwc, void* hx, void* lo, int n, int h, int w, int c, hipStream_t stream);
 // One launch over all 2d residual-block convolutions of a precision-1 network (conv3x3_body16w.hip, CHAIN): a workgroup
@@ -167,11 +171,13 @@ int body16w_chain_patches_per_wg(int n, int h, int w, int feat, int cus);
 // fp32 NHWC tensor <-> blocked (hi, lo) tensors: hi = (u + 0x8000) >> 16, lo = u & 0xffff per value (c % 8 == 0)
 hipError_t launch_split_f32(const float* in_nhwc, void* hi, void* lo, int n, int h, int w, int c, hipStream_t stream);
 hipError_t launch_join_f32(const void* hi, const void* lo, float* out_nhwc, int n, int h, int w, int c, hipStream_t stream);
-// Geometry helpers for packing
-bool conv_pack_geometry(int cin, int cout, int epilogue, const Tuning& tune, PackGeom* g);
-size_t packed_weight_floats(const PackGeom& g);
-// host_kernel HWIO (3,3,cin,cout) -> packed layout (host memory, zero padded)
-void pack_conv_weights_host(const float* kernel_hwio, int cin, int cout, const PackGeom& g, float* dst);
+// RNE bf16 of an fp32 value: the one rounding of every host packer of 16-bit weights
+inline uint16_t f32_to_bf16_rne(float f) {
+  uint32_t u = __builtin_bit_cast(uint32_t, f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
 
 // ---- elementwise / gather kernels (patch_ops.hip) ---------------------------------------------
 // concat(x10,x20,x60) NCHW -> NHWC with 16 channels (zero padded): folds keras Concatenate(axis=1).
