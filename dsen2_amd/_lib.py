@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get('DSEN2_HIP_LIB') or os.path.join(_HERE, 'libdsen2_hip.
 
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_NO_WEIGHTS, ERR_WORKSPACE, ERR_NO_DEVICE, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6, -7
+DTYPE_U16, DTYPE_F32 = 0, 1          # dsen2_down_pixel_aggr
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -69,6 +70,8 @@ SIGNATURES = {
                                 c_void_p]),
     'dsen2_recompose_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_float,
                                      c_int, c_int, c_void_p]),
+    'dsen2_down_pixel_aggr': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int,
+                                      c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

@@ -100,13 +100,14 @@ def _load(path, lazy=False):
     raise ValueError('unsupported input %r (use .npz or .mat)' % path)
 
 
-def snap_roi(x1, y1, x2, y2, width, height):
-    """s2_tiles_supres.py:111-120 — ROI clipped to the raster and grown to 60 m pixel boundaries (10 m pixels)."""
+def snap_roi(x1, y1, x2, y2, width, height, step=6):
+    """s2_tiles_supres.py:111-120 — ROI clipped to the raster and grown to 60 m pixel boundaries (10 m pixels); step=36:
+    training/create_patches.py:63-71, whose 60 m image must itself divide by 6."""
     xmin = max(min(x1, x2, width - 1), 0)
     xmax = min(max(x1, x2, 0), width - 1)
     ymin = max(min(y1, y2, height - 1), 0)
     ymax = min(max(y1, y2, 0), height - 1)
-    return int(xmin / 6) * 6, int(ymin / 6) * 6, int((xmax + 1) / 6) * 6 - 1, int((ymax + 1) / 6) * 6 - 1
+    return int(xmin / step) * step, int(ymin / step) * step, int((xmax + 1) / step) * step - 1, int((ymax + 1) / step) * step - 1
 
 
 def lon_lat_to_pixel(ds, osr, lon, lat):
@@ -200,7 +201,7 @@ class LazyRows(object):
 class GdalProduct(object):
     """The GDAL side of s2_tiles_supres.py for one product: which sub-datasets and bands, the ROI, the arrays."""
 
-    def __init__(self, gdal, path, want, roi_x_y=None, select_utm='', fmt='GTiff', roi_lon_lat=None, osr=None):
+    def __init__(self, gdal, path, want, roi_x_y=None, select_utm='', fmt='GTiff', roi_lon_lat=None, osr=None, snap=6):
         self.gdal, self.fmt = gdal, fmt
         if roi_lon_lat and not roi_x_y and osr is None:
             raise ImportError('--roi_lon_lat needs osgeo.osr')
@@ -221,11 +222,11 @@ class GdalProduct(object):
             ds = gdal.Open(name)
             w, h = ds.RasterXSize, ds.RasterYSize
             if roi_x_y:                            # pixels win over lon/lat when both are given (:125-137)
-                box = snap_roi(roi_x_y[0], roi_x_y[1], roi_x_y[2], roi_x_y[3], w, h)
+                box = snap_roi(roi_x_y[0], roi_x_y[1], roi_x_y[2], roi_x_y[3], w, h, snap)
             elif roi_lon_lat:
                 xa, ya = lon_lat_to_pixel(ds, osr, roi_lon_lat[0], roi_lon_lat[1])
                 xb, yb = lon_lat_to_pixel(ds, osr, roi_lon_lat[2], roi_lon_lat[3])
-                box = snap_roi(xa, ya, xb, yb, w, h)
+                box = snap_roi(xa, ya, xb, yb, w, h, snap)
             else:
                 box = (0, 0, w - 1, h - 1)
             utm = desc[desc.find('UTM'):] if 'UTM' in desc else ''

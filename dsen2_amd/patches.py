@@ -1,16 +1,21 @@
-"""Host-side mirror of the inference half of the reference's utils/patches.py, running on the GPU.
+"""Host-side mirror of the reference's utils/patches.py, running on the GPU.
 
 Same function names, arguments, defaults, return types and quirks as the reference:
   interp_patches(image_20, image_10_shape)                              utils/patches.py:11-16
   get_test_patches(dset_10, dset_20, patchSize=128, border=4, interp)   utils/patches.py:19-80
   get_test_patches60(dset_10, dset_20, dset_60, patchSize=128, border=8, interp)   :83-156
   recompose_images(a, border, size=None)                                utils/patches.py:374-405
+and of its training-set half (python -m dsen2_amd.create_patches):
+  downPixelAggr(img, SCALE=2)                                           utils/patches.py:353-371
+  save_test_patches / save_test_patches60(..., file, ...)               utils/patches.py:159-178
+  save_random_patches / save_random_patches60(..., file, NR_CROP)       utils/patches.py:181-271  (+ seed=, origins=)
 numpy in, numpy out; the ``*_device`` variants keep everything in HBM (torch CUDA tensors) so that
 supres.DSen2_20/60 never bounce patches through the host.  The gathers, the mirror-bilinear
 up-sampling and the recomposition are HIP kernels behind the C ABI (include/dsen2_hip.h); only the
 O(#patches) origin arithmetic runs on the host.
 """
 import ctypes
+import random
 from math import ceil
 
 import numpy as np
@@ -283,3 +288,175 @@ def recompose_images(a, border, size=None):
     x = _to_device_f32(a, dev)
     print((a.shape[1], size[0], size[1]))
     return recompose_device(x, border, size).cpu().numpy()
+
+
+# ---- training-set creation (utils/patches.py:159-271, :353-371) --------------------------------
+# numpy's exp is not one function: an AVX-512 kernel in some builds, libm in others, and exp(-2) differs in its last bit between
+# them — and with it w.sum() and the centre weight.  A drop-in must not depend on that, so the two scales of the DSen2 protocol are
+# pinned to what the reference's stack computes (scipy 1.7.1 on numpy 1.26.4, AVX-512; tests/golden/make_golden_trainset.py
+# asserts it there and records them); any other scale evaluates the same formula with the numpy at hand.
+_REFERENCE_WEIGHTS = {
+    2: ('0x1.14aebe6a24088p-12', '0x1.b405b9842b206p-4', '0x1.92b965ef5aaefp-1', '0x1.b405b9842b206p-4', '0x1.14aebe6a24088p-12'),
+    6: ('0x1.05a62840e3dcep-26', '0x1.fffffefa59d7cp-1', '0x1.05a62840e3dcep-26'),
+}
+
+
+def gaussian_weights(scale):
+    """(weights float64 [2 * radius + 1], radius): what scipy.ndimage.gaussian_filter1d(sigma=1/scale, truncate=4.0) builds
+    (scipy/ndimage/filters.py, _gaussian_kernel1d) — float64 on the host, so that the kernel never evaluates exp."""
+    sigma = 1.0 / scale
+    radius = int(4.0 * sigma + 0.5)
+    if scale in _REFERENCE_WEIGHTS:
+        return np.array([float.fromhex(v) for v in _REFERENCE_WEIGHTS[scale]]), radius
+    x = np.arange(-radius, radius + 1)
+    w = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return w / w.sum(), radius
+
+
+def _check_divisible(h, w, scale):
+    # the reference fails here too: block_reduce pads to a multiple of SCALE while new_dims floors (ValueError on assignment)
+    if scale < 1 or h % scale or w % scale:
+        raise ValueError('downPixelAggr: image of %d x %d pixels is not a multiple of SCALE = %d' % (h, w, scale))
+
+
+def _down(img_dev, np_dtype, scale, out_dtype):
+    h, w, c = img_dev.shape
+    _check_divisible(h, w, scale)
+    weights, radius = gaussian_weights(scale)
+    if radius > min(h, w):
+        raise ValueError('downPixelAggr: image of %d x %d pixels is smaller than the filter radius %d' % (h, w, radius))
+    out = torch.empty((h // scale, w // scale, c), dtype=out_dtype, device=img_dev.device)
+    if out.numel() == 0:
+        return out
+    host_w = (ctypes.c_double * len(weights))(*weights)
+    with torch.cuda.device(img_dev.device):
+        _lib.call('dsen2_down_pixel_aggr', _ptr(img_dev), _lib.DTYPE_U16 if np_dtype == np.uint16 else _lib.DTYPE_F32, h, w, c,
+                  int(scale), host_w, radius, _ptr(out), 1 if out_dtype == torch.float64 else 0, _stream(img_dev.device))
+    return out
+
+
+def upload_raster(img, device=None):
+    """A host raster -> (device tensor, numpy dtype) IN ITS OWN DTYPE: uint16 travels as its bits in an int16 tensor and is never
+    widened (downPixelAggr truncates to uint16 after each filter axis: the float32 path gives other numbers), float32 as it is.
+    Any other dtype is refused: the reference would filter it in that dtype, and only these two have a kernel."""
+    device = device or default_device()
+    a = np.asarray(img)
+    if a.dtype not in (np.uint16, np.float32):
+        raise TypeError('downPixelAggr on the GPU takes uint16 or float32 rasters, not %s (the reference filters in the input\'s '
+                        'dtype: cast explicitly to the one you mean)' % a.dtype)
+    a = np.ascontiguousarray(a)
+    if not a.flags.writeable:
+        a = np.array(a)
+    t = torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)
+    return t, a.dtype.type
+
+
+def down_pixel_aggr_device(img_dev, scale, np_dtype=None):
+    """[H,W,C] device tensor (float32, or int16 holding uint16 bits — `upload_raster`) -> float32 [H/scale,W/scale,C] device
+    tensor: float32(reference downPixelAggr), which is what every consumer of the reference's float64 result casts it to."""
+    if np_dtype is None:
+        np_dtype = np.uint16 if img_dev.dtype == torch.int16 else np.float32
+    if img_dev.dtype != (torch.int16 if np_dtype == np.uint16 else torch.float32):
+        raise TypeError('down_pixel_aggr_device: tensor of %s for a raster of %s' % (img_dev.dtype, np.dtype(np_dtype)))
+    if img_dev.dim() == 2:
+        img_dev = img_dev[:, :, None]
+    return _down(img_dev.contiguous(), np_dtype, scale, torch.float32)
+
+
+def downPixelAggr(img, SCALE=2):
+    """utils/patches.py:353-371 — Gaussian blur (sigma = 1/SCALE) + SCALE x SCALE pixel aggregation; float64 ndarray, squeezed,
+    the reference's result bit for bit (dsen2_down_pixel_aggr)."""
+    img = np.asarray(img)
+    if img.ndim == 2:
+        img = img[:, :, None]
+    _check_divisible(img.shape[0], img.shape[1], SCALE)          # before anything touches the GPU
+    t, dt = upload_raster(img)
+    return np.squeeze(_down(t, dt, SCALE, torch.float64).cpu().numpy())
+
+
+def save_test_patches(dset_10, dset_20, file, patchSize=128, border=4, interp=True):
+    """utils/patches.py:159-166."""
+    image_10, data20_interp = get_test_patches(dset_10, dset_20, patchSize=patchSize, border=border, interp=interp)
+    print("Saving to file {}".format(file))
+    np.save(file + 'data10', image_10)
+    np.save(file + 'data20', data20_interp)
+    print('Done!')
+
+
+def save_test_patches60(dset_10, dset_20, dset_60, file, patchSize=192, border=12, interp=True):
+    """utils/patches.py:169-178."""
+    image_10, data20_interp, data60_interp = get_test_patches60(dset_10, dset_20, dset_60, patchSize=patchSize, border=border,
+                                                                interp=interp)
+    print("Saving to file {}".format(file))
+    np.save(file + 'data10', image_10)
+    np.save(file + 'data20', data20_interp)
+    np.save(file + 'data60', data60_interp)
+    print('Done!')
+
+
+def random_origins(lr_shape, patch_lr, nr_crop, seed=None):
+    """int32 [nr_crop, 2] upper-left corners on the low-resolution grid, drawn as utils/patches.py:199-200 / :244-245 draws them:
+    two randrange calls per crop, axis 0 first, each over [0, extent - patch).  seed=None draws from the `random` module's
+    global generator like the reference (random.seed(s) before the call == seed=s)."""
+    rr = random.randrange if seed is None else random.Random(seed).randrange
+    h, w = int(lr_shape[0]) - patch_lr, int(lr_shape[1]) - patch_lr
+    if h <= 0 or w <= 0:
+        raise ValueError('low-resolution image %r leaves no room for a %d x %d patch' % (tuple(lr_shape[:2]), patch_lr, patch_lr))
+    org = np.empty((nr_crop, 2), np.int32)
+    for i in range(nr_crop):
+        org[i, 0] = rr(0, h)
+        org[i, 1] = rr(0, w)
+    return org
+
+
+def _random_crops(img, origins, scale, patch, device):
+    """The crops of one image at `origins * scale`, [N,C,patch,patch] float32 on the device (dsen2_tile_gather, border 0)."""
+    img = _to_device_f32(img, device)
+    if img.dim() == 2:
+        img = img[:, :, None]
+    if origins.shape[0] and ((origins.min() < 0) or (origins[:, 0].max() * scale + patch > img.shape[0])
+                             or (origins[:, 1].max() * scale + patch > img.shape[1])):
+        raise ValueError('crop origins reach outside the image of shape %r' % (tuple(img.shape),))
+    return gather_patches_device(img, origins, scale, 0, patch, origins.shape[0])
+
+
+def _origins_arg(origins, lr_shape, patch_lr, nr_crop, seed):
+    if origins is None:
+        return random_origins(lr_shape, patch_lr, nr_crop, seed)
+    origins = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1, 2)
+    if origins.shape[0] != nr_crop:
+        raise ValueError('%d origins for NR_CROP = %d' % (origins.shape[0], nr_crop))
+    return origins
+
+
+def save_random_patches(dset_20gt, dset_10, dset_20, file, NR_CROP=8000, seed=None, origins=None):
+    """utils/patches.py:181-219: NR_CROP random 32 x 32 (10 m) patches — data10, data20_gt and the up-sampled data20 as float32
+    [N,C,32,32] .npy files.  Images: host arrays of any real dtype or device tensors ([H,W,C]); they are cropped and up-sampled
+    on the GPU and only the finished arrays are downloaded."""
+    dev = default_device()
+    org = _origins_arg(origins, dset_20.shape, 16, NR_CROP, seed)
+    image_10 = _random_crops(dset_10, org, 2, 32, dev)
+    np.save(file + 'data10', image_10.cpu().numpy())
+    hr_hw = image_10.shape[2:4]
+    del image_10
+    np.save(file + 'data20_gt', _random_crops(dset_20gt, org, 2, 32, dev).cpu().numpy())
+    image_20 = _random_crops(dset_20, org, 1, 16, dev)
+    np.save(file + 'data20', interp_patches_device(image_20, hr_hw).cpu().numpy())
+    print('Done!')
+
+
+def save_random_patches60(dset_60gt, dset_10, dset_20, dset_60, file, NR_CROP=500, seed=None, origins=None):
+    """utils/patches.py:222-271: NR_CROP random 96 x 96 (10 m) patches — data10, data60_gt, and data20 / data60 up-sampled."""
+    dev = default_device()
+    bands = [int(d.shape[2]) for d in (dset_60gt, dset_10, dset_20, dset_60)]
+    for b, p in zip(bands, (96, 96, 48, 16)):                  # the reference prints its four array shapes (:236-239)
+        print((NR_CROP, b, p, p))
+    org = _origins_arg(origins, dset_60.shape, 16, NR_CROP, seed)
+    image_10 = _random_crops(dset_10, org, 6, 96, dev)
+    np.save(file + 'data10', image_10.cpu().numpy())
+    hr_hw = image_10.shape[2:4]
+    del image_10
+    np.save(file + 'data60_gt', _random_crops(dset_60gt, org, 6, 96, dev).cpu().numpy())
+    np.save(file + 'data20', interp_patches_device(_random_crops(dset_20, org, 3, 48, dev), hr_hw).cpu().numpy())
+    np.save(file + 'data60', interp_patches_device(_random_crops(dset_60, org, 1, 16, dev), hr_hw).cpu().numpy())
+    print('Done!')

@@ -9,7 +9,8 @@ cooldown 20, min_lr 1e-5), best-only checkpointing on val_loss, shuffled epochs.
   <out>/<model_nr>_lr_<lr>.txt      one line per epoch: loss, val_loss, lr
 
 fp32 models on one GPU only.  Data: <path>/train/*SAFE/{data10,data20,data20_gt}.npy (train60/ and data60, data60_gt with
---run_60) and val_index.npy, as training/create_patches.py writes them.
+--run_60) and val_index.npy, as `python -m dsen2_amd.create_patches` and `python -m dsen2_amd.create_random` write them (the
+counterparts of training/create_patches.py and create_random.py, whose files it reads just the same).
 """
 import argparse
 import os

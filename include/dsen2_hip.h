@@ -274,6 +274,20 @@ int dsen2_recompose(const float *dev_patches, int count, int C, int P, int borde
 int dsen2_recompose_rows(const float *dev_patches, int count, int C, int P, int border, float *dev_img, int H,
                          int W, float scale, int row0, int row1, void *stream);
 
+/* dsen2_down_pixel_aggr  <->  downPixelAggr                       utils/patches.py:353-371
+ *   dev_img: one HWC image [H,W,C] of uint16 or float32 samples; writes the HWC image [H/scale, W/scale, C] as float32
+ *   (out_f64 = 0) or float64 (1).  scipy.ndimage.gaussian_filter(band, 1/scale) + skimage block_reduce(np.mean), operation by
+ *   operation: per axis (0, then 1) the symmetric float64 correlation tmp = in[l]*w[r]; tmp += (in[l+ii] + in[l-ii])*w[ii+r]
+ *   for ii = -r..-1 with the 'reflect' boundary, un-fused; after EACH axis a cast to the input's dtype (uint16 truncates,
+ *   float32 rounds); then the float64 block sum / scale^2.  The reference's float64 result bit for bit (out_f64 = 1), or its
+ *   float32 cast.  host_weights: the 2*radius + 1 normalised Gaussian weights, computed by the caller as scipy does (they are
+ *   passed to the kernel by value).  DSEN2_ERR_INVALID, with nothing launched: H or W not a multiple of scale (the reference
+ *   raises ValueError), scale outside 1..32, radius > 8, radius > min(H, W), unknown dtype.  Any C. */
+#define DSEN2_DTYPE_U16 0
+#define DSEN2_DTYPE_F32 1
+int dsen2_down_pixel_aggr(const void *dev_img, int dtype, int H, int W, int C, int scale, const double *host_weights,
+                          int radius, void *dev_out, int out_f64, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
