@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('DSEN2_HIP_LIB') or os.path.join(_HERE, 'libdsen2_hip.
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_NO_WEIGHTS, ERR_WORKSPACE, ERR_NO_DEVICE, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6, -7
 DTYPE_U16, DTYPE_F32 = 0, 1          # dsen2_down_pixel_aggr
+DTYPE_F64 = 2                        # dsen2_imresize_axis, dsen2_band_errors
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -72,6 +73,11 @@ SIGNATURES = {
                                      c_int, c_int, c_void_p]),
     'dsen2_down_pixel_aggr': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int,
                                       c_void_p, c_int, c_void_p]),
+    'dsen2_imresize_axis': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'dsen2_band_errors_workspace_bytes': (c_int, [c_int, ctypes.POINTER(c_size_t)]),
+    'dsen2_band_errors': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_imresize_band_errors': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                           c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,110 @@
+"""python -m dsen2_amd.evaluate — score the predictions of `python -m dsen2_amd.train --predict` against the ground truth, beside
+the MATLAB-bicubic baseline: the numbers the reference publishes (testing/demoDSen2.py:45-48, 70-73), computed on the GPU.
+
+    python -m dsen2_amd.evaluate --path P [--run_60] [--model_nr s2_038_] [--json OUT]
+
+For every directory below <P>/test/ (test60/ with --run_60) that holds no_tiling/ — what `python -m dsen2_amd.create_patches
+--test_data` wrote — it loads the ground truth no_tiling/data20_gt.npy (data60_gt) and the downsampled bands no_tiling/data20.npy
+(data60) and prints the demo's block
+
+    <name>
+    DSen2:
+    RMSE: 12.3456          <model_nr>-predict.npy against the ground truth (left out when there is no such file)
+    Bicubic:
+    RMSE: 23.4567          imresize(downsampled bands, SCALE) against the ground truth
+
+then RMSE and SRE (dB) per band, and after the last tile the mean of each column over all tiles.  --json writes every value
+unrounded.  The bicubic baseline never stores the enlarged image: the second resampling pass adds up the errors itself
+(metrics.bicubic_error_sums).  The downsampled bands are read as create_patches stores them, float32.
+"""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+
+MODEL_NR = 's2_038_'
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog='python -m dsen2_amd.evaluate', description='RMSE / SRE of predicted test sets and of the bicubic baseline, on the GPU.')
+    p.add_argument('--path', default='../data/', help='Path of the data (test/ or test60/ below it).')
+    p.add_argument('--run_60', action='store_true', help='Score the 60->10m test sets (test60/). Default 20->10m (test/).')
+    p.add_argument('--model_nr', default=MODEL_NR, help='Prefix of the prediction files: <model_nr>-predict.npy.')
+    p.add_argument('--json', default=None, metavar='OUT', help='Write every value, unrounded, to this file.')
+    return p.parse_args(argv)
+
+
+def _entry(sums):
+    from . import metrics
+    rmse, sre, total = metrics.scores(sums)
+    return {'rmse': total, 'band_rmse': rmse.tolist(), 'band_sre': sre.tolist()}
+
+
+def _table(rows, bands):
+    print('%-8s' % 'band' + ''.join('%24s' % name for name, _ in rows))
+    print('%-8s' % '' + ''.join('%12s%12s' % ('RMSE', 'SRE [dB]') for _ in rows))
+    for c in range(bands):
+        print('%-8d' % c + ''.join('%12.4f%12.4f' % (e['band_rmse'][c], e['band_sre'][c]) for _, e in rows))
+
+
+def evaluate_tile(d, run_60, model_nr):
+    """{'bicubic': {...}, 'dsen2': {...} or absent} of one test directory."""
+    from . import metrics
+    key, scale = ('data60', 6) if run_60 else ('data20', 2)
+    gt = np.load(os.path.join(d, 'no_tiling', key + '_gt.npy'))
+    lr = np.load(os.path.join(d, 'no_tiling', key + '.npy'))
+    out = {}
+    pred = os.path.join(d, model_nr + '-predict.npy')
+    if os.path.exists(pred):
+        out['dsen2'] = _entry(metrics.error_sums(np.load(pred), gt))
+    out['bicubic'] = _entry(metrics.bicubic_error_sums(lr, gt, scale))
+    return out
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    path = args.path if args.path.endswith('/') else args.path + '/'
+    folder = 'test60/' if args.run_60 else 'test/'
+    tiles = [d for d in sorted(glob.glob(path + folder + '*')) if os.path.isdir(os.path.join(d, 'no_tiling'))]
+    if not tiles:
+        print('No test set below {} (python -m dsen2_amd.create_patches --test_data writes one)'.format(path + folder))
+        return 2
+    result = {'model_nr': args.model_nr, 'folder': folder, 'tiles': {}}
+    for d in tiles:
+        name = os.path.basename(d)
+        r = evaluate_tile(d, args.run_60, args.model_nr)
+        result['tiles'][name] = r
+        print(name)
+        if 'dsen2' in r:
+            print('DSen2:')
+            print('RMSE: {:.4f}'.format(r['dsen2']['rmse']))
+        print('Bicubic:')
+        print('RMSE: {:.4f}'.format(r['bicubic']['rmse']))
+        rows = [(k, r[k]) for k in ('dsen2', 'bicubic') if k in r]
+        _table([({'dsen2': 'DSen2', 'bicubic': 'Bicubic'}[k], e) for k, e in rows], len(r['bicubic']['band_rmse']))
+    mean = {}
+    for k in ('dsen2', 'bicubic'):
+        have = [r[k] for r in result['tiles'].values() if k in r]
+        if have:
+            mean[k] = {'tiles': len(have), 'rmse': float(np.mean([e['rmse'] for e in have])),
+                       'band_rmse': np.mean([e['band_rmse'] for e in have], axis=0).tolist(),
+                       'band_sre': np.mean([e['band_sre'] for e in have], axis=0).tolist()}
+    result['mean'] = mean
+    print('Mean over {} tile(s)'.format(len(tiles)))
+    for k, label in (('dsen2', 'DSen2'), ('bicubic', 'Bicubic')):
+        if k in mean:
+            print('{}: RMSE {:.4f} ({} tile(s))'.format(label, mean[k]['rmse'], mean[k]['tiles']))
+    _table([({'dsen2': 'DSen2', 'bicubic': 'Bicubic'}[k], mean[k]) for k in ('dsen2', 'bicubic') if k in mean],
+           len(mean['bicubic']['band_rmse']))
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+            f.write('\n')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -9,12 +9,15 @@ and of its training-set half (python -m dsen2_amd.create_patches):
   downPixelAggr(img, SCALE=2)                                           utils/patches.py:353-371
   save_test_patches / save_test_patches60(..., file, ...)               utils/patches.py:159-178
   save_random_patches / save_random_patches60(..., file, NR_CROP)       utils/patches.py:181-271  (+ seed=, origins=)
+and of what the evaluation step (python -m dsen2_amd.train --predict) reads back:
+  OpenDataFilesTest(path, run_60, SCALE, true_scale=False)              utils/patches.py:327-350
 numpy in, numpy out; the ``*_device`` variants keep everything in HBM (torch CUDA tensors) so that
 supres.DSen2_20/60 never bounce patches through the host.  The gathers, the mirror-bilinear
 up-sampling and the recomposition are HIP kernels behind the C ABI (include/dsen2_hip.h); only the
 O(#patches) origin arithmetic runs on the host.
 """
 import ctypes
+import json
 import random
 from math import ceil
 
@@ -460,3 +463,25 @@ def save_random_patches60(dset_60gt, dset_10, dset_20, dset_60, file, NR_CROP=50
     np.save(file + 'data20', interp_patches_device(_random_crops(dset_20, org, 3, 48, dev), hr_hw).cpu().numpy())
     np.save(file + 'data60', interp_patches_device(_random_crops(dset_60, org, 1, 16, dev), hr_hw).cpu().numpy())
     print('Done!')
+
+
+# ---- reading a test set back (utils/patches.py:327-350) ------------------------------------------
+def OpenDataFilesTest(path, run_60, SCALE, true_scale=False):
+    """utils/patches.py:327-350: the tiled test set `python -m dsen2_amd.create_patches --test_data` wrote under `path` — ([data10,
+    data20(, data60)] divided by SCALE, image_size).  image_size comes from roi.json = [xmin, ymin, xmax, ymax] and is, as in the
+    reference, [xmax - xmin, ymax - ymin] = [width, height]; the three printed lines are the reference's.  Host work only."""
+    if not SCALE:
+        SCALE = 1
+    names = ('data10', 'data20', 'data60') if run_60 else ('data10', 'data20')
+    train = []
+    for name in names:
+        a = np.load(path + '/' + name + '.npy')
+        a /= SCALE
+        train.append(a)
+    with open(path + '/roi.json') as f:
+        roi = json.load(f)
+    image_size = [roi[2] - roi[0], roi[3] - roi[1]]
+    print("The image size is: {}".format(image_size))
+    print("The SCALE is: {}".format(SCALE))
+    print("The true_scale is: {}".format(true_scale))
+    return train, image_size

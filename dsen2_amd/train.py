@@ -11,16 +11,31 @@ cooldown 20, min_lr 1e-5), best-only checkpointing on val_loss, shuffled epochs.
 fp32 models on one GPU only.  Data: <path>/train/*SAFE/{data10,data20,data20_gt}.npy (train60/ and data60, data60_gt with
 --run_60) and val_index.npy, as `python -m dsen2_amd.create_patches` and `python -m dsen2_amd.create_random` write them (the
 counterparts of training/create_patches.py and create_random.py, whose files it reads just the same).
+
+    python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] --path P
+is that script's predict branch: for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
+loads the tiled test set (patches.OpenDataFilesTest), runs predict(batch_size=8), recomposes the image (border 4; 12 for test60/
+and true/), multiplies by SCALE = 2000 and writes <P>/<folder>/<dset>/<model_nr>-predict.npy, model_nr being the seven
+characters in front of 'lr_1e-04' in FILE's name (model_number).  `python -m dsen2_amd.evaluate` scores those files.
+DECISION: the reference hands recompose_images `image_size` = [width, height] as read from roi.json, where that function takes
+(rows, columns).  For a square region the two agree, and that is what the recorded behaviour pins; for any other region the
+reference recomposes a transposed canvas.  Here recompose_images always gets (rows, columns) = (height, width), so a non-square
+region predicts to the shape of its ground truth.
 """
 import argparse
+import glob
 import os
 import sys
+import time
 
 MODEL_NR = 's2_038_'    # training/supres_train.py: prefix of a new training
+SCALE = 2000
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog='python -m dsen2_amd.train', description='Fine-tune DSen2 / VDSen2 on the GPU (SupResS2).')
+    p.add_argument('--predict', action='store', dest='predict_file', help='Predict: the test sets below --path with these weights (.hdf5 / .npy).')
+    p.add_argument('--true', action='store_true', help='Use true scale data. No simulation or different resolutions.')
     p.add_argument('--resume', action='store', dest='resume_file', help='Resume training from these weights (.hdf5 / .npy).')
     p.add_argument('--run_60', action='store_true', help='Train a 60->10m network. Default 20->10m.')
     p.add_argument('--deep', action='store_true', help='VDSen2: 32 blocks of 256 features, batch 8 (default DSen2: 6 x 128, batch 128).')
@@ -39,6 +54,33 @@ def model_number(resume_file):
     return stem[-15:-8]
 
 
+def predict(model, args, path):
+    """training/supres_train.py:149-179."""
+    import numpy as np
+    from . import patches
+    if args.true:
+        folder, border = 'true/', 12
+    elif args.run_60:
+        folder, border = 'test60/', 12
+    else:
+        folder, border = 'test/', 4
+    model_nr = model_number(args.predict_file)
+    print('Changing the model number to: {}'.format(model_nr))
+    model.load_weights(args.predict_file)
+    print('Predicting using file: {}'.format(args.predict_file))
+    for dset in [os.path.basename(x) for x in sorted(glob.glob(path + folder + '*SAFE'))]:
+        start = time.time()
+        print('Timer started.')
+        print('Predicting: {}.'.format(dset))
+        train, image_size = patches.OpenDataFilesTest(path + folder + dset, args.run_60, SCALE, args.true)
+        prediction = model.predict(train, batch_size=8, verbose=1)
+        images = patches.recompose_images(prediction, border=border, size=(image_size[1], image_size[0]))     # (rows, columns): see above
+        print('Writing to file...')
+        np.save(path + folder + dset + '/' + model_nr + '-predict', images * SCALE)
+        print('Elapsed time: {}.'.format(time.time() - start))
+    return 0
+
+
 def main(argv=None):
     args = parse_args(argv)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
@@ -48,6 +90,9 @@ def main(argv=None):
     from .DSen2Net import s2model
 
     path = args.path if args.path.endswith('/') else args.path + '/'
+    if args.predict_file:
+        bands = ((4, None, None), (6, None, None), (2, None, None)) if args.run_60 else ((4, None, None), (6, None, None))
+        return predict(s2model(bands, num_layers=32 if args.deep else 6, feature_size=256 if args.deep else 128), args, path)
     out = args.out if args.out is not None else path + 'network_data/'
     os.makedirs(out, exist_ok=True)
     bands = ((4, None, None), (6, None, None), (2, None, None)) if args.run_60 else ((4, None, None), (6, None, None))

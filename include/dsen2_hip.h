@@ -288,6 +288,32 @@ int dsen2_recompose_rows(const float *dev_patches, int count, int C, int P, int 
 int dsen2_down_pixel_aggr(const void *dev_img, int dtype, int H, int W, int C, int scale, const double *host_weights,
                           int radius, void *dev_out, int out_f64, void *stream);
 
+/* ---- evaluation: MATLAB-compatible bicubic resize and per-band errors (utils/imresize.py, testing/demoDSen2.py:31-35) ----
+ * dsen2_imresize_axis  <->  imresizemex(inimg, weights, indices, dim)          utils/imresize.py:50-74
+ *   One resampling pass along `axis` (0 = rows, 1 = columns) of the HWC image dev_in [H,W,C] of uint16, float32 or float64
+ *   samples; writes float64 [out_len,W,C] (axis 0) or [H,out_len,C] (axis 1).  Per output, sequentially in k and un-fused:
+ *   out = sum_k w[k][o] * (double)in[idx[k][o]].  dev_weights (float64) and dev_indices (int32) are DEVICE tables of `taps` rows
+ *   of out_len entries each (k-major: the transpose of what contributions() returns); the caller builds them
+ *   (dsen2_amd/imresize.py).  imresize = two such passes, the smaller scale first, the second reading the first's float64.
+ *   Refused with DSEN2_ERR_INVALID and nothing launched: any other dtype (uint8: the reference rounds it; not supported), taps
+ *   outside 1..256, an axis other than 0 / 1, a slice of 2^31 elements or more.  Indices are clamped to the axis on the device. */
+#define DSEN2_DTYPE_F64 2
+int dsen2_imresize_axis(const void *dev_in, int dtype, int H, int W, int C, int axis, int out_len, const double *dev_weights,
+                        const int *dev_indices, int taps, double *dev_out, void *stream);
+
+/* dsen2_band_errors: per band c of the HWC images dev_x and dev_gt [H,W,C] (float32 or float64 each), dev_out[3c .. 3c+2] =
+ *   { sum (x - gt)^2, sum gt, H * W } as float64: RMSE_c = sqrt(out[3c] / out[3c+2]), SRE_c = 10 log10((out[3c+1] / out[3c+2])^2 /
+ *   (out[3c] / out[3c+2])).  The order of every addition depends on the shape only (no float atomics): the same bits on every
+ *   run.  dev_work: dsen2_band_errors_workspace_bytes(C) bytes of device scratch.  1 <= C <= 64.
+ * dsen2_imresize_band_errors: dsen2_imresize_axis followed by dsen2_band_errors against dev_gt (which has the OUTPUT's shape) in
+ *   one pass that never stores the resampled image — the second pass of the bicubic baseline of a whole tile. */
+int dsen2_band_errors_workspace_bytes(int C, size_t *bytes);
+int dsen2_band_errors(const void *dev_x, int x_dtype, const void *dev_gt, int gt_dtype, int H, int W, int C, void *dev_work,
+                      size_t work_bytes, double *dev_out, void *stream);
+int dsen2_imresize_band_errors(const void *dev_in, int dtype, int H, int W, int C, int axis, int out_len, const double *dev_weights,
+                               const int *dev_indices, int taps, const void *dev_gt, int gt_dtype, void *dev_work,
+                               size_t work_bytes, double *dev_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
