@@ -191,21 +191,30 @@ def gather_patches_device(img_dev, origins_lr, scale, border, patch, n_alloc, di
     return out
 
 
-def device_origins(origins_lr, scale, device):
-    """int32 [n,2] crop origins at one resolution (low-res origins x scale) as a device tensor."""
-    return torch.from_numpy(np.ascontiguousarray(origins_lr * scale, dtype=np.int32)).to(device)
+def device_origins(origins_lr, scale, device, row0=0):
+    """int32 [n,2] crop origins at one resolution (low-res origins x scale) as a device tensor; `row0`: the image row the
+    uploaded slab starts at (the origins are shifted into it)."""
+    org = np.ascontiguousarray(origins_lr * scale, dtype=np.int32)
+    org[:, 0] -= row0
+    return torch.from_numpy(org).to(device)
 
 
-def _check_ratio(hi, lo, scale):
-    if hi.shape[0] < scale * lo.shape[0] or hi.shape[1] < scale * lo.shape[1]:
-        # the reference's crop loop fails with a broadcasting ValueError here (patches.py:67, :136-137)
-        raise ValueError('image of shape %r does not cover %d x the lower-resolution image %r'
-                         % (tuple(hi.shape), scale, tuple(lo.shape)))
+def check_sizes(dsets, scales, lowest='lowest'):
+    """The reference fails with a broadcasting ValueError when the images do not have the 10 m : 20 m (: 60 m) size ratio its
+    crop arithmetic assumes (patches.py:67, :136-137); say so before anything reaches the GPU.  dsets[-1] is the
+    lowest-resolution image, scales[i] the ratio of dsets[i] to it."""
+    lo = dsets[-1].shape
+    for d, s in zip(dsets, scales):
+        if len(d.shape) != 3:
+            raise ValueError('expected HWC images, got shape %r' % (tuple(d.shape),))
+        if d.shape[0] < s * lo[0] or d.shape[1] < s * lo[1]:
+            raise ValueError('image of shape %r does not cover %d x the %s-resolution image %r'
+                             % (tuple(d.shape), s, lowest, tuple(lo)))
 
 
 def get_test_patches(dset_10, dset_20, patchSize=128, border=4, interp=True):
     """utils/patches.py:19-80.  Returns (image_10 [N,B10,P,P], data20 [N,B20,P,P]) float32 ndarrays."""
-    _check_ratio(dset_10, dset_20, 2)
+    check_sizes([dset_10, dset_20], [2, 1], 'lower')
     dev = default_device()
     p_lr, b_lr = patchSize // 2, border // 2
     d10, d20 = _to_device_f32(dset_10, dev), _to_device_f32(dset_20, dev)
@@ -218,8 +227,7 @@ def get_test_patches(dset_10, dset_20, patchSize=128, border=4, interp=True):
 
 def get_test_patches60(dset_10, dset_20, dset_60, patchSize=128, border=8, interp=True):
     """utils/patches.py:83-156.  Returns (image_10, data20, data60) float32 ndarrays."""
-    _check_ratio(dset_10, dset_60, 6)
-    _check_ratio(dset_20, dset_60, 3)
+    check_sizes([dset_10, dset_20, dset_60], [6, 3, 1], 'lower')
     dev = default_device()
     p20, p60 = patchSize // 2, patchSize // 6
     b20, b60 = border // 2, border // 6
@@ -247,8 +255,7 @@ def final_row_runs(have, done_rows, size, inner):
     one [H - inner, H) (its start is clamped, patches.py:396-401, and it overwrites what the row before it put there).
     Returns merged [(row0, row1)] runs in ascending order."""
     H = int(size[0])
-    x_tiles = int(ceil(size[1] / float(inner)))
-    y_tiles = int(ceil(H / float(inner)))
+    x_tiles, y_tiles = recompose_grid(size, inner, 0)
     ready = np.asarray(have[:x_tiles * y_tiles], bool).reshape(y_tiles, x_tiles).all(axis=1) & ~done_rows
     runs = []
     for ty in np.nonzero(ready)[0]:

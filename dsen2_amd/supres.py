@@ -15,6 +15,7 @@ and re-read on every call as the reference does (supres.py:59,63) — observable
 """
 from __future__ import division
 
+import contextlib
 import os
 
 import numpy as np
@@ -81,18 +82,6 @@ def _predict(test, input_shape, deep=False, run_60=False):
     return model.predict(test, verbose=1)
 
 
-def _check_sizes(dsets, scales):
-    """The reference fails with a broadcasting ValueError when the images do not have the 10 m : 20 m (: 60 m) size
-    ratio its crop arithmetic assumes (patches.py:67,136-137); say so before anything reaches the GPU."""
-    lo = dsets[-1].shape
-    for d, s in zip(dsets, scales):
-        if len(d.shape) != 3:
-            raise ValueError('expected HWC images, got shape %r' % (tuple(d.shape),))
-        if d.shape[0] < s * lo[0] or d.shape[1] < s * lo[1]:
-            raise ValueError('image of shape %r does not cover %d x the lowest-resolution image %r'
-                             % (tuple(d.shape), s, tuple(lo)))
-
-
 def _row_slab(org_lr, scale, patch, border, height):
     """Rows [r0, r1) of one resolution's image that the patches with low-res origins `org_lr` read (the symmetric
     padding only ever reflects at the true image edges, which a slab touching them shares)."""
@@ -102,143 +91,117 @@ def _row_slab(org_lr, scale, patch, border, height):
     return r0, r1
 
 
-def _run(dsets, scales, patch, border, deep, run_60):
-    _check_sizes(dsets, scales)
-    dev = _patches.default_device()
-    rank, world = _dist.rank_world()
-    patch_sizes = [patch // (scales[0] // s) for s in scales]          # P, P//2(, P//6)
-    borders = [border // (scales[0] // s) for s in scales]             # b, b//2(, b//6)
-    org, n_alloc = _patches.tile_origins(dsets[-1].shape, patch_sizes[-1], borders[-1])
-    used = org.shape[0]
-    input_shape = tuple((int(d.shape[2]), None, None) for d in dsets)
-    model = _get_model(input_shape, deep, run_60)
-    cout = model.cout
-    size = dsets[0].shape
-    # this rank's contiguous share of the USED patches (the reference's trailing all-zero patches are
-    # never read by recompose_images, so they are not computed)
-    first, count = _dist.shard_range(used)
-    per = _dist.per_rank(used, world)
-    inner = patch - 2 * border
-    single = n_alloc == 1            # recompose_images' single-patch shortcut (patches.py:375-376): a[0] uncropped
-    # The buffer this rank's predictions go to.  One rank (or the single-patch case): whole patches.  Several ranks:
-    # the inner crops, in the [per, ...] buffer the gather sends as it is (2.95 GB for a 10980^2 tile over all ranks
-    # instead of 3.85 GB of whole patches to EVERY rank).
-    if world == 1 or single:
-        send = None
-        pred_local = torch.empty((count, cout, patch, patch), dtype=torch.float32, device=dev)
-    else:
-        send = torch.empty((per, cout, inner, inner), dtype=torch.float32, device=dev)
-        pred_local = None
-    # Several ranks, DSEN2_CHUNKED_GATHER=1: the crops travel in DSEN2_GATHER_CHUNKS (8) pieces while the shards are still computing
-    # (dist.ChunkedGather) and rank 0 recomposes + downloads what has arrived under the remaining work, instead of one
-    # gather at the very end followed by recomposition and 51 ms of D2H on rank 0 alone.  Off by default until
-    # an N > 1 box has measured RCCL's kernels next to two CU-filling persistent ones; the result is the same image.
-    cg, next_chunk, cg_img, cg_ready = None, 0, None, None
-    if send is not None and _chunked_gather_wanted():
-        cg = _dist.ChunkedGather(send, used, _gather_chunks())
-        if rank == 0:
-            # the image rank 0 recomposes into, allocated NOW and fenced by an event: its tail stream may then start on the
-            # first piece while the shard is still computing — waiting for the compute stream later (wait_stream) would wait
-            # for the whole shard and put recomposition + download back after it
-            cg_img = torch.empty((int(size[0]), int(size[1]), cout), dtype=torch.float32, device=dev)
-            cg_ready = torch.cuda.Event()
-            cg_ready.record(torch.cuda.current_stream(dev))
-    bands = None                     # one rank, large image: the bands of rows already recomposed (below)
-    if count > 0:
-        # upload only the rows this rank's patches read (1/world of the tile), origins shifted into the slab
-        my_org = org[first:first + count]
-        imgs, org_dev = [], []
-        for d, s, ps, b in zip(dsets, scales, patch_sizes, borders):
+class Shard(object):
+    """What one rank computes: the network's inputs for the patches with low-res origins `my_org` (at least one).  Uploads
+    only the rows those patches read (1/world of the tile; everything when there is one rank) and, once, the origins shifted
+    into that slab: batch() only enqueues."""
+
+    def __init__(self, dsets, scales, patch_sizes, borders, my_org, world):
+        dev = _patches.default_device()
+        self.org, self.geom, self.imgs, self.org_dev = my_org, list(zip(scales, patch_sizes, borders)), [], []
+        for d, (s, ps, b) in zip(dsets, self.geom):
             r0, r1 = _row_slab(my_org, s, ps, b, d.shape[0]) if world > 1 else (0, d.shape[0])
-            imgs.append(_patches._to_device_f32(d[r0:r1], dev))
-            shifted = (my_org * s).astype(np.int32)
-            shifted[:, 0] -= r0
-            org_dev.append(torch.from_numpy(np.ascontiguousarray(shifted)).to(dev))      # uploaded once: the loop only enqueues
-        bs = model.preferred_batch(patch, patch)
-        # One rank, a large image: rows that are final are recomposed right after the batch that completes them — rows below
-        # min(t * inner, H - inner) once the first t tile rows of patches are done (the last `inner` rows belong to the clamped
-        # last tile row, patches.py:396-401) — and an event marks each band, so that the download can later run band by band
-        # on a copy stream UNDER the batches still computing (a D2H takes 5-40 % of its own time away from the kernels,
-        # profiles/r04_ablation.md §3).  This loop still only enqueues.
-        if world == 1 and not single and _pinned_wanted((int(size[0]), int(size[1]), cout)) and \
-                os.environ.get('DSEN2_BANDED_OUTPUT', '1') != '0':
-            bands = dict(x_tiles=_patches.recompose_grid(size, patch, border)[0], rows=0, list=[],
-                         img=torch.empty((int(size[0]), int(size[1]), cout), dtype=torch.float32, device=dev))
-        for i0 in range(0, count, bs):
-            n = min(bs, count - i0)
-            xs = []
-            for k, (img, s, ps, b) in enumerate(zip(imgs, scales, patch_sizes, borders)):
-                if k == 0:
-                    # `p10 /= SCALE` (supres.py:23) folded into the gather (IEEE divide, bit-identical)
-                    xs.append(_patches.gather_patches_device(img, my_org, s, b, ps, n_alloc, divisor=SCALE,
-                                                             first=i0, count=n, origins_dev=org_dev[k]))
-                else:
-                    lr = _patches.gather_patches_device(img, my_org, s, b, ps, n_alloc, first=i0, count=n,
-                                                        origins_dev=org_dev[k])
-                    # up-sample raw values, then `/= SCALE` (supres.py:24,43-44)
-                    xs.append(_patches.interp_patches_device(lr, (patch, patch), post_divisor=SCALE))
-            if send is None:
-                model.forward_device(xs, out=pred_local[i0:i0 + n])
+            self.imgs.append(_patches._to_device_f32(d[r0:r1], dev))
+            self.org_dev.append(_patches.device_origins(my_org, s, dev, row0=r0))
+
+    def batch(self, i0, n):
+        """The inputs of patches [i0, i0 + n) of this shard, one [n, C, P, P] tensor per resolution."""
+        patch, n_alloc = self.geom[0][1], self.org.shape[0]         # (n_alloc only sizes a gather without `count`)
+        xs = []
+        for k, (img, org_dev, (s, ps, b)) in enumerate(zip(self.imgs, self.org_dev, self.geom)):
+            if k == 0:
+                # `p10 /= SCALE` (supres.py:23) folded into the gather (IEEE divide, bit-identical)
+                xs.append(_patches.gather_patches_device(img, self.org, s, b, ps, n_alloc, divisor=SCALE,
+                                                         first=i0, count=n, origins_dev=org_dev))
             else:
-                y = model.forward_device(xs)
-                send[i0:i0 + n].copy_(y[:, :, border:patch - border, border:patch - border])
-                # a piece whose slots this rank has all written (a short shard: all it will ever write) goes out now
-                while cg is not None and next_chunk < cg.n_chunks and i0 + n >= min(cg.bounds[next_chunk][1], count):
-                    cg.issue(next_chunk)
-                    next_chunk += 1
-            if bands is not None:
-                done = i0 + n
-                final = int(size[0]) if done == count else min((done // bands['x_tiles']) * inner, int(size[0]) - inner)
-                if final > bands['rows']:
-                    # `images *= SCALE` (supres.py:29) folded into the recomposition
-                    _patches.recompose_rows_device(pred_local, border, bands['img'], bands['rows'], final, scale=SCALE)
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dev))
-                    bands['list'].append((bands['rows'], final, ev))
-                    bands['rows'] = final
-    if bands is not None and count > 0:
-        # everything is enqueued; the page-locked buffer is allocated now, under that work (as in the one-shot path below),
-        # and the bands whose events have fired by then start downloading at once
-        print((cout, size[0], size[1]))                                # patches.py:392
-        host = _host_output((int(size[0]), int(size[1]), cout))
-        if host is None:               # page-locked memory exhausted: the image is complete on the device
-            return bands['img'].cpu().numpy()
-        copy_stream = torch.cuda.Stream(dev)
-        with torch.cuda.stream(copy_stream):
-            for r0, r1, ev in bands['list']:
-                copy_stream.wait_event(ev)
-                host[r0:r1].copy_(bands['img'][r0:r1], non_blocking=True)
-        copy_stream.synchronize()
-        return host.numpy()            # ndarray view of the page-locked tensor (kept alive by the array)
-    if single:
-        if rank != 0:
-            return None
-        images = pred_local[0].permute(1, 2, 0).contiguous() * SCALE
-        return images.cpu().numpy()
-    # Everything above is only ENQUEUED (seconds of GPU work for a full tile): rank 0 allocates the page-locked
-    # buffer the result is downloaded into now, under that work (0.18 s for a 10980^2 x 6 image; the download itself
-    # then runs at 57 GB/s instead of 11 GB/s from pageable memory: 0.05 s instead of 0.26 s).
-    if cg is not None:
-        return _finish_chunked(cg, next_chunk, rank, dev, size, cout, inner, cg_img, cg_ready)
-    host = _host_output((int(size[0]), int(size[1]), cout)) if rank == 0 else None
-    if world == 1:
-        print((cout, size[0], size[1]))                                # patches.py:392
-        # `images *= SCALE` (supres.py:29) folded into the recomposition
-        images = _patches.recompose_device(pred_local, border, size, scale=SCALE)
-    else:
-        # gather to root: rank 0 receives every rank's inner crops into views of one buffer and recomposes them
-        # (cropped patches of `inner` with border 0 tile exactly like whole patches with their border, patches.py:380-403);
-        # the other ranks return None — no page-locked buffer, no download, nothing received.
-        crops = _dist.gather_to_root(send, used)
-        if rank != 0:
-            return None
-        print((cout, size[0], size[1]))
-        images = _patches.recompose_device(crops, 0, size, scale=SCALE)
-    if host is None:
-        return images.cpu().numpy()
-    host.copy_(images, non_blocking=True)
-    torch.cuda.synchronize(dev)
-    return host.numpy()            # ndarray view of the page-locked tensor (kept alive by the array)
+                lr = _patches.gather_patches_device(img, self.org, s, b, ps, n_alloc, first=i0, count=n, origins_dev=org_dev)
+                # up-sample raw values, then `/= SCALE` (supres.py:24,43-44)
+                xs.append(_patches.interp_patches_device(lr, (patch, patch), post_divisor=SCALE))
+        return xs
+
+
+PINNED_OUTPUT_MIN_BYTES = 64 << 20     # DSEN2_PINNED_OUTPUT=0 disables; torch caches page-locked blocks for reuse
+
+
+def _pinned_wanted(shape):
+    return os.environ.get('DSEN2_PINNED_OUTPUT', '1') != '0' and 4 * shape[0] * shape[1] * shape[2] >= PINNED_OUTPUT_MIN_BYTES
+
+
+def _pinned_empty(shape):
+    return torch.empty(shape, dtype=torch.float32, pin_memory=True)
+
+
+class RowSink(object):
+    """How the image leaves the GPU, whoever computed its patches: rows() recomposes a band of rows that are final into the
+    device image, finish() returns the image — through a page-locked buffer (57 GB/s instead of 11 GB/s from pageable memory)
+    that is allocated only when the GPU work is enqueued, UNDER it (0.18 s for a 10980^2 x 6 image), or in one pageable
+    download: small image, DSEN2_PINNED_OUTPUT=0, page-locked memory exhausted.
+
+    Bands recomposed on the compute stream are marked with an event each, and finish() downloads them on a copy stream, every
+    band as soon as its event has fired: under the batches still computing when the bands came in during the loop (a D2H takes
+    5-40 % of its own time away from the kernels, profiles/r04_ablation.md §3).
+
+    own_stream (the chunked gather): a stream that waits for what the current stream holds NOW — the image exists — and for
+    nothing later, so that it may start on the first piece while the shard is still computing and the compute stream never
+    waits for the collective's.  `with sink.tail():` — entered when the shard is enqueued — allocates the buffer and makes that
+    stream current; every band is then downloaded right behind its recomposition and finish() only waits."""
+
+    def __init__(self, shape, dev, own_stream=False):
+        self.dev = dev
+        self.img = torch.empty(shape, dtype=torch.float32, device=dev)         # [H, W, cout]
+        self.pinned = _pinned_wanted(shape)
+        self.host, self.bands, self.stream = None, [], None
+        if own_stream:
+            self.stream = torch.cuda.Stream(dev)
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+
+    def _page_locked(self):
+        if self.pinned:
+            try:
+                return _pinned_empty(tuple(self.img.shape))
+            except RuntimeError:       # page-locked memory exhausted: the pageable path still works
+                pass
+        return None
+
+    @contextlib.contextmanager
+    def tail(self):
+        self.host = self._page_locked()
+        with torch.cuda.stream(self.stream):
+            yield
+
+    def rows(self, src_patches, border, r0, r1):
+        """Image rows [r0, r1) from the patch buffer (whole patches with their border, or inner crops with border 0: they tile
+        alike, patches.py:380-403), on the current stream; `images *= SCALE` (supres.py:29) folded into the recomposition."""
+        _patches.recompose_rows_device(src_patches, border, self.img, r0, r1, scale=SCALE)
+        if self.stream is not None:
+            if self.host is not None:
+                self.host[r0:r1].copy_(self.img[r0:r1], non_blocking=True)
+        elif self.pinned:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.dev))
+            self.bands.append((r0, r1, ev))
+
+    def finish(self):
+        """The image as an ndarray (a view of the page-locked tensor, which it keeps alive, where there is one)."""
+        if self.stream is not None:
+            self.stream.synchronize()
+        else:
+            self.host = self._page_locked()
+            if self.host is not None:
+                copy_stream = torch.cuda.Stream(self.dev)
+                with torch.cuda.stream(copy_stream):
+                    for r0, r1, ev in self.bands:
+                        copy_stream.wait_event(ev)
+                        self.host[r0:r1].copy_(self.img[r0:r1], non_blocking=True)
+                copy_stream.synchronize()
+        return self.host.numpy() if self.host is not None else self.img.cpu().numpy()
+
+
+def _final_bands(slots_done, per, done_rows, size, inner):
+    """[(r0, r1)] image rows that became final now that the first `slots_done` slots of every shard of `per` patches are
+    there (one rank: per = all patches, slots_done = patches computed so far); `done_rows` as in patches.final_row_runs."""
+    x_tiles = _patches.recompose_grid(size, inner, 0)[0]
+    return _patches.final_row_runs(np.arange(x_tiles * done_rows.size) % per < slots_done, done_rows, size, inner)
 
 
 def _chunked_gather_wanted():
@@ -249,55 +212,88 @@ def _gather_chunks():
     return max(1, int(os.environ.get('DSEN2_GATHER_CHUNKS', '8')))
 
 
-def _finish_chunked(cg, next_chunk, rank, dev, size, cout, inner, img, ready):
-    """The tail of a sharded run with the chunked gather.  Every rank: the pieces it has not issued yet (a rank whose shard
-    is short or empty still takes part in every gather).  Rank 0: on a stream of its own — so that its compute stream never
-    waits for RCCL — piece by piece: wait for the gather, recompose the image rows whose patches have all arrived (the crops
-    tile like whole patches with border 0, patches.py:380-403), download them into the page-locked buffer.  All of it is
-    enqueued at once; only the final synchronise blocks."""
-    while next_chunk < cg.n_chunks:
-        cg.issue(next_chunk)
-        next_chunk += 1
-    if rank != 0:
-        for c in range(cg.n_chunks):
-            cg.complete(c)             # the send buffer stays alive until every piece has left
-        return None
+def _run(dsets, scales, patch, border, deep, run_60):
+    _patches.check_sizes(dsets, scales)
+    dev = _patches.default_device()
+    rank, world = _dist.rank_world()
+    patch_sizes = [patch // (scales[0] // s) for s in scales]          # P, P//2(, P//6)
+    borders = [border // (scales[0] // s) for s in scales]             # b, b//2(, b//6)
+    org, n_alloc = _patches.tile_origins(dsets[-1].shape, patch_sizes[-1], borders[-1])
+    used = org.shape[0]
+    model = _get_model(tuple((int(d.shape[2]), None, None) for d in dsets), deep, run_60)
+    cout, size, inner = model.cout, dsets[0].shape, patch - 2 * border
+    shape = (int(size[0]), int(size[1]), cout)
+    # this rank's contiguous share of the USED patches (the reference's trailing all-zero patches are
+    # never read by recompose_images, so they are not computed)
+    first, count = _dist.shard_range(used)
+    single = n_alloc == 1            # recompose_images' single-patch shortcut (patches.py:375-376): a[0] uncropped
+    done_rows = np.zeros(_patches.recompose_grid(size, patch, border)[1], bool)
+    # Where this rank's predictions go and who feeds the sink.  One rank (or the single patch): whole patches; a large image
+    # leaves in bands, each right after the batch that completes its rows.  Several ranks: the inner crops, in the [per, ...]
+    # buffer the gather sends as it is (2.95 GB for a 10980^2 tile over all ranks instead of 3.85 GB of whole patches to EVERY
+    # rank): one gather at the end, or, with DSEN2_CHUNKED_GATHER=1, DSEN2_GATHER_CHUNKS (8) pieces that travel while the
+    # shards still compute (dist.ChunkedGather; off by default until an N > 1 box has measured RCCL's kernels
+    # next to two CU-filling persistent ones).  The image is the same.
+    pred = send = cg = sink = None
+    banded, issued = False, 0
+    if world == 1 or single:
+        pred = torch.empty((count, cout, patch, patch), dtype=torch.float32, device=dev)
+        banded = not single and _pinned_wanted(shape) and os.environ.get('DSEN2_BANDED_OUTPUT', '1') != '0'
+    else:
+        send = torch.empty((_dist.per_rank(used, world), cout, inner, inner), dtype=torch.float32, device=dev)
+        if _chunked_gather_wanted():
+            cg = _dist.ChunkedGather(send, used, _gather_chunks())
+            if rank == 0:
+                sink = RowSink(shape, dev, own_stream=True)            # BEFORE the loop: its stream waits for nothing later
+    if count > 0:
+        shard = Shard(dsets, scales, patch_sizes, borders, org[first:first + count], world)
+        if banded:
+            sink = RowSink(shape, dev)
+        bs = model.preferred_batch(patch, patch)
+        for i0 in range(0, count, bs):                                 # this loop only enqueues
+            n = min(bs, count - i0)
+            xs = shard.batch(i0, n)
+            if send is None:
+                model.forward_device(xs, out=pred[i0:i0 + n])
+                if banded:
+                    for r0, r1 in _final_bands(i0 + n, used, done_rows, size, inner):
+                        sink.rows(pred, border, r0, r1)
+            else:
+                y = model.forward_device(xs)
+                send[i0:i0 + n].copy_(y[:, :, border:patch - border, border:patch - border])
+                # a piece whose slots this rank has all written (a short shard: all it will ever write) goes out now
+                while cg is not None and issued < cg.n_chunks and i0 + n >= min(cg.bounds[issued][1], count):
+                    cg.issue(issued)
+                    issued += 1
+    if single:
+        return (pred[0].permute(1, 2, 0).contiguous() * SCALE).cpu().numpy() if rank == 0 else None
+    if cg is not None:
+        # every rank issues every gather (a short or empty shard too); the send buffer stays alive until every piece has left
+        for c in range(issued, cg.n_chunks):
+            cg.issue(c)
+        if rank != 0:
+            for c in range(cg.n_chunks):
+                cg.complete(c)
+            return None
+        print((cout, size[0], size[1]))                                # patches.py:392
+        with sink.tail():
+            for c in range(cg.n_chunks):
+                cg.complete(c)                                         # this stream waits for gather c
+                for r0, r1 in _final_bands(cg.slots_done(c), cg.per, done_rows, size, inner):
+                    sink.rows(cg.recv, 0, r0, r1)
+            assert done_rows.all()
+            return sink.finish()
+    if world > 1:
+        # gather to root: rank 0 receives every rank's inner crops into views of one buffer; the other ranks return None —
+        # no page-locked buffer, no download, nothing received
+        pred, border = _dist.gather_to_root(send, used), 0
+        if rank != 0:
+            return None
     print((cout, size[0], size[1]))                                    # patches.py:392
-    H, W = int(size[0]), int(size[1])
-    host = _host_output((H, W, cout))          # page-locked, allocated under the work already enqueued
-    x_tiles, y_tiles = int(np.ceil(W / float(inner))), int(np.ceil(H / float(inner)))
-    slot = np.arange(x_tiles * y_tiles) % cg.per                       # a patch's slot in its rank's shard
-    done_rows = np.zeros(y_tiles, bool)
-    tail = torch.cuda.Stream(dev)
-    tail.wait_event(ready)                     # `img` / `recv` exist as far as the compute stream is concerned (NOT: the shard is done)
-    with torch.cuda.stream(tail):
-        for c in range(cg.n_chunks):
-            cg.complete(c)
-            for r0, r1 in _patches.final_row_runs(slot < cg.slots_done(c), done_rows, size, inner):
-                # `images *= SCALE` (supres.py:29) folded into the recomposition
-                _patches.recompose_rows_device(cg.recv, 0, img, r0, r1, scale=SCALE)
-                if host is not None:
-                    host[r0:r1].copy_(img[r0:r1], non_blocking=True)
-    tail.synchronize()
-    assert done_rows.all()
-    return host.numpy() if host is not None else img.cpu().numpy()
-
-
-PINNED_OUTPUT_MIN_BYTES = 64 << 20     # DSEN2_PINNED_OUTPUT=0 disables; torch caches page-locked blocks for reuse
-
-
-def _pinned_wanted(shape):
-    nbytes = 4 * shape[0] * shape[1] * shape[2]
-    return os.environ.get('DSEN2_PINNED_OUTPUT', '1') != '0' and nbytes >= PINNED_OUTPUT_MIN_BYTES
-
-
-def _host_output(shape):
-    if not _pinned_wanted(shape):
-        return None
-    try:
-        return torch.empty(shape, dtype=torch.float32, pin_memory=True)
-    except RuntimeError:           # page-locked memory exhausted: the pageable path still works
-        return None
+    if sink is None:                 # not in bands: the whole image in one
+        sink = RowSink(shape, dev)
+        sink.rows(pred, border, 0, shape[0])
+    return sink.finish()
 
 
 def DSen2_20(d10, d20, deep=False):

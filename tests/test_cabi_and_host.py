@@ -144,6 +144,35 @@ def test_row_slabs_cover_what_a_shard_reads():
                     assert (rows.max() < H) or r1 == H
 
 
+def test_band_schedule_of_one_rank_is_the_closed_form_and_partitions_the_rows():
+    """One rank recomposes, after every batch, the rows supres._final_bands reports (patches.final_row_runs: the one statement
+    of which rows are final).  With the patches done in order that is the closed form the loop used to carry — rows below
+    min(t * inner, H - inner) once t tile rows are complete, everything after the last batch — and the bands cut [0, H) into
+    ascending pieces, no row twice."""
+    from dsen2_amd import supres
+    from dsen2_amd.patches import recompose_grid
+    cases = 0
+    for inner in (112, 168, 24):
+        for H in range(inner, 5 * inner + 3, 7):
+            for W in (inner, 2 * inner + 5, 3 * inner):
+                x_tiles, y_tiles = recompose_grid((H, W), inner, 0)
+                used = x_tiles * y_tiles
+                for bs in (1, 2, 3, 5, 7, used):
+                    done_rows, got, want, rows = np.zeros(y_tiles, bool), [], [], 0
+                    for done in list(range(bs, used, bs)) + [used]:
+                        got += supres._final_bands(done, used, done_rows, (H, W), inner)
+                        final = H if done == used else min((done // x_tiles) * inner, H - inner)
+                        if final > rows:
+                            want.append((rows, final))
+                            rows = final
+                    assert got == want, (inner, H, W, bs)
+                    assert got[0][0] == 0 and got[-1][1] == H and all(r0 < r1 for r0, r1 in got)
+                    assert all(a[1] == b[0] for a, b in zip(got, got[1:])), (inner, H, W, bs)
+                    assert done_rows.all()
+                    cases += 1
+    assert cases == 3186
+
+
 def test_weight_container_matches_oracle_layout(tmp_path):
     from dsen2_amd import weights as w
     for cin, cout, d, f in [(10, 6, 6, 128), (12, 2, 6, 128), (10, 6, 32, 256)]:

@@ -275,6 +275,70 @@ def test_recompose_rows_is_the_full_recomposition_cut_into_bands():
         gp.recompose_rows_device(a, 4, img, 30, 20)
 
 
+@pytest.mark.parametrize('limit', [1, 4])
+def test_every_ending_of_one_rank_gives_the_same_bits_and_prints(model_dir, monkeypatch, limit):
+    """One rank, 240 x 198 (3 x 2 tiles for DSen2_20, 2 x 2 for DSen2_60), page-locked threshold 0: (a) rows downloaded in bands
+    as the batches complete them, (b) DSEN2_BANDED_OUTPUT=0: one band at the end, (c) DSEN2_PINNED_OUTPUT=0: pageable download,
+    (d) the page-locked allocation fails: the pageable download after all — the same image and the same printed lines."""
+    from dsen2_amd import supres
+    from dsen2_amd.DSen2Net import S2Model
+    rng = np.random.default_rng(240 + 198 + limit)
+    d10 = rng.integers(35, 9000, size=(240, 198, 4), dtype=np.uint16)
+    d20 = rng.integers(35, 9000, size=(120, 99, 6), dtype=np.uint16)
+    d60 = rng.integers(35, 9000, size=(40, 33, 2), dtype=np.uint16)
+    monkeypatch.setattr(supres, 'PINNED_OUTPUT_MIN_BYTES', 0)
+    monkeypatch.setattr(S2Model, 'batch_limit', lambda self, hh, ww: limit)
+    tried = []
+
+    def exhausted(shape):
+        tried.append(shape)
+        raise RuntimeError('page-locked memory exhausted (simulated)')
+    for fn, args in ((supres.DSen2_20, (d10, d20)), (supres.DSen2_60, (d10, d20, d60))):
+        runs = []
+        for env, fail in (({}, False), ({'DSEN2_BANDED_OUTPUT': '0'}, False), ({'DSEN2_PINNED_OUTPUT': '0'}, False), ({}, True)):
+            with monkeypatch.context() as m:
+                m.delenv('DSEN2_BANDED_OUTPUT', raising=False)
+                m.delenv('DSEN2_PINNED_OUTPUT', raising=False)
+                for k, v in env.items():
+                    m.setenv(k, v)
+                if fail:
+                    m.setattr(supres, '_pinned_empty', exhausted)
+                runs.append(quiet(fn, *args, deep=False))
+        assert tried == [(240, 198, runs[0][0].shape[2])]           # (d) did ask for page-locked memory, once
+        del tried[:]
+        a, pa = runs[0]
+        assert a.shape == (240, 198, a.shape[2]) and a.dtype == np.float32
+        for b, pb in runs[1:]:
+            assert np.array_equal(a, b), (fn.__name__, limit)
+            assert pa == pb
+        assert pa.count('(%d, 240, 198)' % a.shape[2]) == 1
+
+
+@pytest.mark.parametrize('pinned', [True, False])
+def test_row_sink_fed_in_bands_is_the_full_recomposition(monkeypatch, pinned):
+    """supres.RowSink fed the bands patches.final_row_runs reports for batches of 1, 5 and 12 patches (4 x 3 tiles of inner 24 over
+    80 x 60: the clamped last tile row included) returns dsen2_recompose's image bit for bit, through page-locked memory and
+    without it."""
+    from dsen2_amd import patches as gp, supres
+    monkeypatch.setattr(supres, 'PINNED_OUTPUT_MIN_BYTES', 0)
+    monkeypatch.setenv('DSEN2_PINNED_OUTPUT', '1' if pinned else '0')
+    rng = np.random.default_rng(5)
+    a = torch.from_numpy(rng.standard_normal((12, 6, 32, 32)).astype(np.float32)).cuda()
+    size = (80, 60)
+    want = gp.recompose_device(a, 4, size, scale=float(supres.SCALE)).cpu().numpy()
+    for bs in (1, 5, 12):
+        sink = supres.RowSink(size + (6,), a.device)
+        assert sink.pinned == pinned
+        done_rows, fed = np.zeros(4, bool), []
+        for done in list(range(bs, 12, bs)) + [12]:
+            for r0, r1 in gp.final_row_runs(np.arange(12) < done, done_rows, size, 24):
+                sink.rows(a, 4, r0, r1)
+                fed.append((r0, r1))
+        assert fed[0][0] == 0 and fed[-1][1] == 80 and len(fed) == {1: 4, 5: 3, 12: 1}[bs]
+        got = sink.finish()
+        assert got.dtype == np.float32 and np.array_equal(got, want), bs
+
+
 def test_smallest_images_the_tiling_accepts(model_dir):
     """The smallest images whose symmetric padding still covers one patch: 112 x 112 for DSen2_20 (ONE used patch of the four
     the reference allocates, patches.py:35) and 168 x 168 for DSen2_60, plus one pixel row / 60 m cell more (a clamped second

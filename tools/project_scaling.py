@@ -57,7 +57,7 @@ def T():
 quiet(supres.DSen2_20, d10[:240, :240], d20[:120, :120])            # library load, model build, weight upload
 dev = P.default_device()
 model = quiet(supres._get_model, ((4, None, None), (6, None, None)), False, False)
-org, n_alloc = P.tile_origins(d20.shape, 64, 4)
+org, _ = P.tile_origins(d20.shape, 64, 4)
 used = org.shape[0]
 patch, border, inner = 128, 8, 112
 out = {'tile': [n, n], 'patches': int(used), 'xgmi_gbps_assumed_per_link': XGMI_GBPS}
@@ -72,35 +72,34 @@ del y
 
 # ---- rank 0's shard at each N: slab conversion + upload, GPU work on its patches, crop into the send buffer ----
 bs = model.preferred_batch(patch, patch)
+
+
+def run_shard(shard, send, after_batch=lambda done: None):
+    """supres._run's loop of a sharded rank over the patches of `shard`."""
+    for i0 in range(0, send.shape[0], bs):
+        nb = min(bs, send.shape[0] - i0)
+        yb = model.forward_device(shard.batch(i0, nb))
+        send[i0:i0 + nb].copy_(yb[:, :, border:patch - border, border:patch - border])
+        after_batch(i0 + nb)
+
+
 per_n = {}
 for world in (1, 2, 4, 8):
     per = D.per_rank(used, world)
-    my = org[:per]
     r = {}
     t0 = T()
-    imgs, orgs = [], []
-    for d, s, ps, b in ((d10, 2, 128, 8), (d20, 1, 64, 4)):
-        r0, r1 = supres._row_slab(my, s, ps, b, d.shape[0]) if world > 1 else (0, d.shape[0])
-        imgs.append(P._to_device_f32(d[r0:r1], dev))
-        sh = (my * s).astype(np.int32); sh[:, 0] -= r0
-        orgs.append(torch.from_numpy(np.ascontiguousarray(sh)).to(dev))
+    shard = supres.Shard([d10, d20], [2, 1], [128, 64], [8, 4], org[:per], world)
     t1 = T()
     r['slab_to_f32_and_h2d_s'] = round(t1 - t0, 4)
     send = torch.empty((per, 6, inner, inner), dtype=torch.float32, device=dev)
     t1 = T()
-    for i0 in range(0, per, bs):
-        nb = min(bs, per - i0)
-        p10 = P.gather_patches_device(imgs[0], my, 2, 8, 128, n_alloc, divisor=2000, first=i0, count=nb, origins_dev=orgs[0])
-        lr = P.gather_patches_device(imgs[1], my, 1, 4, 64, n_alloc, first=i0, count=nb, origins_dev=orgs[1])
-        p20 = P.interp_patches_device(lr, (patch, patch), post_divisor=2000)
-        yb = model.forward_device([p10, p20])
-        send[i0:i0 + nb].copy_(yb[:, :, border:patch - border, border:patch - border])
+    run_shard(shard, send)
     t2 = T()
     r['gpu_shard_s'] = round(t2 - t1, 4)
     r['patches_per_rank'] = int(per)
     r['gather_in_s_at_assumed_link_rate'] = round((per * 6 * inner * inner * 4) / (XGMI_GBPS * 1e9), 4) if world > 1 else 0.0
     per_n[world] = r
-    del imgs, orgs
+    del shard
     if world < 8:
         del send
 
@@ -116,6 +115,8 @@ host.copy_(img, non_blocking=True); t3 = T()
 out['d2h_pinned_s'] = round(t3 - t2, 4)
 tail = out['recompose_s'] + out['d2h_pinned_s']
 
+del host, img              # the chunked form below takes its image and its page-locked buffer (from torch's cache) itself
+
 # ---- the chunked form, emulated on this one GPU: rank 0 computes its shard while its tail stream recomposes and downloads
 # the rows whose crops "have arrived" (they are all in `crops` already; the transfers are priced, not run) ----
 K = int(os.environ.get('DSEN2_GATHER_CHUNKS', '8'))
@@ -123,43 +124,32 @@ out['gather_chunks'] = K
 chunked = {}
 for world in (2, 4, 8):
     per = D.per_rank(used, world)
-    my = org[:per]
-    imgs, orgs = [], []
-    for d, s, ps, b in ((d10, 2, 128, 8), (d20, 1, 64, 4)):
-        r0, r1 = supres._row_slab(my, s, ps, b, d.shape[0])
-        imgs.append(P._to_device_f32(d[r0:r1], dev))
-        sh = (my * s).astype(np.int32); sh[:, 0] -= r0
-        orgs.append(torch.from_numpy(np.ascontiguousarray(sh)).to(dev))
+    shard = supres.Shard([d10, d20], [2, 1], [128, 64], [8, 4], org[:per], world)
     send = torch.empty((per, 6, inner, inner), dtype=torch.float32, device=dev)
     bounds = D.chunk_bounds(per, K)
-    slot = np.arange(used) % per
-    done_rows = np.zeros(-(-n // inner), bool)
-    tail_stream = torch.cuda.Stream(dev)
+    done_rows = np.zeros(P.recompose_grid((n, n), inner, 0)[1], bool)
+    events = []
+
+    def piece_done(done):
+        while len(events) < len(bounds) and done >= bounds[len(events)][1]:
+            events.append(torch.cuda.Event())
+            events[-1].record()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    nxt = 0
-    events = []
-    for i0 in range(0, per, bs):
-        nb = min(bs, per - i0)
-        p10 = P.gather_patches_device(imgs[0], my, 2, 8, 128, n_alloc, divisor=2000, first=i0, count=nb, origins_dev=orgs[0])
-        lr = P.gather_patches_device(imgs[1], my, 1, 4, 64, n_alloc, first=i0, count=nb, origins_dev=orgs[1])
-        p20 = P.interp_patches_device(lr, (patch, patch), post_divisor=2000)
-        yb = model.forward_device([p10, p20])
-        send[i0:i0 + nb].copy_(yb[:, :, border:patch - border, border:patch - border])
-        while nxt < len(bounds) and i0 + nb >= bounds[nxt][1]:
-            ev = torch.cuda.Event(); ev.record(); events.append(ev); nxt += 1
-    with torch.cuda.stream(tail_stream):
+    sink = supres.RowSink((n, n, 6), dev, own_stream=True)
+    run_shard(shard, send, piece_done)
+    with sink.tail():
         for c, ev in enumerate(events):
-            tail_stream.wait_event(ev)                          # piece c of every rank is "there" when rank 0 has computed its own
-            for r0, r1 in P.final_row_runs(slot < bounds[c][1], done_rows, (n, n), inner):
-                P.recompose_rows_device(crops, 0, img, r0, r1, scale=2000)
-                host[r0:r1].copy_(img[r0:r1], non_blocking=True)
+            sink.stream.wait_event(ev)                          # piece c of every rank is "there" when rank 0 has computed its own
+            for r0, r1 in supres._final_bands(bounds[c][1], per, done_rows, (n, n), inner):
+                sink.rows(crops, 0, r0, r1)
+        y = sink.finish()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     assert done_rows.all()
     last_gather = (bounds[-1][1] - bounds[-1][0]) * 6 * inner * inner * 4 / (XGMI_GBPS * 1e9)
     chunked[world] = {'shard_with_overlapped_tail_s': round(t1 - t0, 4), 'last_piece_gather_s': round(last_gather, 4)}
-    del imgs, orgs, send
+    del shard, send, sink, y
 
 proj = {}
 for world, r in per_n.items():
