@@ -62,13 +62,33 @@ def _kernels(text):
     return out
 
 
-def check_listing(text, src):
-    code = _code_lines(text)
-    code = [ln.split(';')[0].strip() for ln in code]
+def normalised(body):
+    """An instruction list (a value of _kernels) with local labels and whitespace normalised: what isa_hashes hashes and
+    tools/isa_diff.py compares."""
+    return [re.sub(r'\.L\w+', 'L', re.sub(r'\s+', ' ', ln)) for ln in body]
 
+
+def compile_isa(hipcc, flags, path, out, verbose=False):
+    """The gfx950 ISA listing of one translation unit under the product's flags (position independence aside)."""
+    cmd = [hipcc] + [f for f in flags if f != '-fPIC'] + ['-S', '--cuda-device-only', path, '-o', out]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
+    with open(out) as f:
+        return f.read()
+
+
+def _needer(src):
     def need(cond, msg, ctx=()):
         if not cond:
             raise AsmContractError('%s: %s %s' % (src, msg, list(ctx)))
+    return need
+
+
+def check_listing(text, src):
+    code = _code_lines(text)
+    code = [ln.split(';')[0].strip() for ln in code]
+    need = _needer(src)
 
     m0 = [i for i, ln in enumerate(code) if re.search(r'\bm0\b', ln)]
     need(m0, 'no M0 use found (the DMA statements are gone?)')
@@ -135,63 +155,48 @@ def check_listing(text, src):
         # operations only: the DMAs are `... lds`), once in each of the two copies of the item loop (issuing waves
         # 0-3 / worker waves 4-7)
         expect = {0: (0, 32), 1: (64, 64), 3: (64, 64)}
-        found = 0
-        for name, body in _kernels(text).items():
-            m = re.search(r'conv3x3_body16[wx]_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E', name)
-            if not m or int(m.group(4)) != 0:
-                continue
-            found += 1
-            loads = sum(1 for ln in body if ln.startswith('buffer_load_dwordx4') and not ln.endswith('lds'))
-            stores = sum(1 for ln in body if ln.startswith('buffer_store_dwordx4'))
+        # the bf16x3 form (precision 2): conv-A stores two planes (32 per copy of the item loop), conv-B stores hi, xl and lo16 (48)
+        expect3 = {0: (0, 64), 1: (64, 96), 3: (64, 64)}
+
+        def count(pattern, want, msg, product=lambda m: True):
+            """The bodies of the kernels matching `pattern` (and `product`), each of which must have exactly want(m) = (non-LDS
+            128-bit loads, 128-bit stores)."""
+            found = []
+            for name, body in kernels.items():
+                m = re.search(pattern, name)
+                if not m or not product(m):
+                    continue
+                found.append(body)
+                loads = sum(1 for ln in body if ln.startswith('buffer_load_dwordx4') and not ln.endswith('lds'))
+                stores = sum(1 for ln in body if ln.startswith('buffer_store_dwordx4'))
+                need((loads, stores) == want(m), msg(m) % (loads, stores, want(m)))
+            return found
+
+        def total(e):
+            return lambda m: (sum(v[0] for v in e.values()), sum(v[1] for v in e.values()))
+
+        found = count(r'conv3x3_body16[wx]_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E', lambda m: expect[int(m.group(3))],
+                      lambda m: 'epilogue ' + m.group(3) + ' has %d loads / %d stores, the waits count %r', lambda m: int(m.group(4)) == 0)
+        need(len(found) >= 6, 'expected the 6 product instantiations of the bf16 body kernel, found %d' % len(found))
+        for body in found:
             other = [ln for ln in body if re.match(r'(buffer|global|flat)_(load|store|atomic)', ln)
                      and not ln.startswith(('buffer_load_dwordx4', 'buffer_store_dwordx4'))]
             # bias preload: global_load_dword in the prologue (before the first vmcnt(0)) is the only other access
             need(len(other) <= 1, 'unexpected vector-memory instructions in the bf16 body kernel', other[:4])
-            need((loads, stores) == expect[int(m.group(3))],
-                 'epilogue %s has %d loads / %d stores, the waits count %r' % (m.group(3), loads, stores, expect[int(m.group(3))]))
-        need(found >= 6, 'expected the 6 product instantiations of the bf16 body kernel, found %d' % found)
-        # the bf16x3 form (precision 2): conv-A stores two planes (32 per copy of the item loop), conv-B stores hi, xl and lo16 (48)
-        expect3 = {0: (0, 64), 1: (64, 96), 3: (64, 64)}
-        found3 = 0
-        for name, body in _kernels(text).items():
-            m = re.search(r'conv3x3_body16w_x3_kernelILi(\d+)ELi(\d+)ELi(\d+)E', name)
-            if not m:
-                continue
-            found3 += 1
-            loads = sum(1 for ln in body if ln.startswith('buffer_load_dwordx4') and not ln.endswith('lds'))
-            stores = sum(1 for ln in body if ln.startswith('buffer_store_dwordx4'))
-            need((loads, stores) == expect3[int(m.group(3))],
-                 'bf16x3 epilogue %s has %d loads / %d stores, the waits count %r' % (m.group(3), loads, stores, expect3[int(m.group(3))]))
-        need(found3 == 6, 'expected the 6 instantiations of the bf16x3 body kernel, found %d' % found3)
+        found3 = count(r'conv3x3_body16w_x3_kernelILi(\d+)ELi(\d+)ELi(\d+)E', lambda m: expect3[int(m.group(3))],
+                       lambda m: 'bf16x3 epilogue ' + m.group(3) + ' has %d loads / %d stores, the waits count %r')
+        need(len(found3) == 6, 'expected the 6 instantiations of the bf16x3 body kernel, found %d' % len(found3))
         # the chain kernel holds all three epilogues, each in both copies of the item loop
-        chains = 0
-        for name, body in _kernels(text).items():
-            m = re.search(r'conv3x3_body16w_chain_kernelILi(\d+)ELi(\d+)ELi(\d+)E', name)
-            if not m or int(m.group(3)) != 0:
-                continue
-            chains += 1
-            loads = sum(1 for ln in body if ln.startswith('buffer_load_dwordx4') and not ln.endswith('lds'))
-            stores = sum(1 for ln in body if ln.startswith('buffer_store_dwordx4'))
-            want = (sum(v[0] for v in expect.values()), sum(v[1] for v in expect.values()))
-            need((loads, stores) == want, 'chain kernel has %d loads / %d stores in its epilogues, the waits count %r' % (loads, stores, want))
-        need(chains == 2, 'expected the 2 product instantiations of the chain kernel, found %d' % chains)
-        chains3 = 0
-        for name, body in _kernels(text).items():
-            if not re.search(r'conv3x3_body16w_x3_chain_kernelILi(\d+)ELi(\d+)E', name):
-                continue
-            chains3 += 1
-            loads = sum(1 for ln in body if ln.startswith('buffer_load_dwordx4') and not ln.endswith('lds'))
-            stores = sum(1 for ln in body if ln.startswith('buffer_store_dwordx4'))
-            want = (sum(v[0] for v in expect3.values()), sum(v[1] for v in expect3.values()))
-            need((loads, stores) == want, 'bf16x3 chain kernel has %d loads / %d stores in its epilogues, the waits count %r' % (loads, stores, want))
-        need(chains3 == 2, 'expected the 2 instantiations of the bf16x3 chain kernel, found %d' % chains3)
+        chains = count(r'conv3x3_body16w_chain_kernelILi(\d+)ELi(\d+)ELi(\d+)E', total(expect),
+                       lambda m: 'chain kernel has %d loads / %d stores in its epilogues, the waits count %r', lambda m: int(m.group(3)) == 0)
+        need(len(chains) == 2, 'expected the 2 product instantiations of the chain kernel, found %d' % len(chains))
+        chains3 = count(r'conv3x3_body16w_x3_chain_kernelILi(\d+)ELi(\d+)E', total(expect3),
+                        lambda m: 'bf16x3 chain kernel has %d loads / %d stores in its epilogues, the waits count %r')
+        need(len(chains3) == 2, 'expected the 2 instantiations of the bf16x3 chain kernel, found %d' % len(chains3))
 
 
 def check_out_mfma_listing(text, src='conv3x3_out_mfma.hip'):
-    def need(cond, msg, ctx=()):
-        if not cond:
-            raise AsmContractError('%s: %s %s' % (src, msg, list(ctx)))
-
+    need = _needer(src)
     kernels = {k: v for k, v in _kernels(text).items() if 'conv3x3_out_mfma_kernel' in k}
     need(len(kernels) == 4, 'expected 4 instantiations of the output kernel, found %d' % len(kernels))
     for name, body in kernels.items():
@@ -210,10 +215,7 @@ def check_first16_listing(text, src='conv3x3_first16.hip'):
     """conv3x3_first16.hip relies on hipcc's own wait counts, which are only exact while the tile loop's body has no divergent
     branch, and on 128-bit buffer stores whose soffset is the IMMEDIATE 0 (with a register soffset gfx950 reads the store data
     late and hipcc does not pad the hazard: experiments/README.md)."""
-    def need(cond, msg, ctx=()):
-        if not cond:
-            raise AsmContractError('%s: %s %s' % (src, msg, list(ctx)))
-
+    need = _needer(src)
     kernels = {k: v for k, v in _kernels(text).items() if 'conv3x3_first16_kernel' in k}
     need(len(kernels) == 8, 'expected 8 instantiations of the kernel, found %d' % len(kernels))
     for name, body in kernels.items():
@@ -260,8 +262,7 @@ def isa_hashes(text):
     import hashlib
     out = {}
     for name, body in _kernels(text).items():
-        norm = [re.sub(r'\.L\w+', 'L', re.sub(r'\s+', ' ', ln)) for ln in body]
-        out[name] = hashlib.sha256('\n'.join(norm).encode()).hexdigest()
+        out[name] = hashlib.sha256('\n'.join(normalised(body)).encode()).hexdigest()
     return out
 
 
@@ -283,13 +284,7 @@ def check_sources(hipcc, flags, verbose=False, isa_json=None):
     listings = {}
     with tempfile.TemporaryDirectory(prefix='dsen2_asm_') as tmp:
         for src in DMA_SOURCES + ['conv3x3_out_mfma.hip', 'conv3x3_first16.hip']:
-            out = os.path.join(tmp, src + '.s')
-            cmd = [hipcc] + [f for f in flags if f not in ('-fPIC',)] + ['-S', '--cuda-device-only', os.path.join(CSRC, src), '-o', out]
-            if verbose:
-                print(' '.join(cmd), flush=True)
-            subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-            with open(out) as f:
-                listings[src] = f.read()
+            listings[src] = compile_isa(hipcc, flags, os.path.join(CSRC, src), os.path.join(tmp, src + '.s'), verbose)
             if src in DMA_SOURCES:
                 check_listing(listings[src], src)
             elif src == 'conv3x3_first16.hip':

@@ -1,16 +1,14 @@
 // conv3x3_bf16_common.h — helpers shared by the bf16 body kernels (conv3x3_body16w.hip, conv3x3_body16x.hip):
 // the inline-asm LDS-DMA statement, counted vmcnt waits and the 16 + 16 bit split of the fp32 residual stream.
 #pragma once
-#include "dsen2_internal.h"
+#include "conv3x3_items.h"
 
 namespace dsen2 {
 namespace bf16k {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 template <int N>

@@ -195,11 +195,9 @@ __device__ __forceinline__ void body16w(const ConvParams p, const int n_items, c
   int l15 = lane & 15;
   int q4 = lane >> 4;
 
-  // persistent schedule: logical ids remapped so that each XCD (blockIdx % 8) walks a contiguous run of items
+  // persistent schedule (conv3x3_items.h): items lid, lid + G, ... (CHAIN: the patches a workgroup owns)
   const int G = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = G >> 3, r8 = G & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lid = xcd_contiguous_id(blockIdx.x, G);
   // Layer-invariant values the lambdas below use.  In a CHAIN they are passed through an empty asm statement at the
   // start of every layer (begin_layer): otherwise hipcc hoists what each of the six copies of the item loop derives
   // from them out of the layer loop and keeps all of it alive across all copies — more scalars than there are SGPRs.
@@ -223,14 +221,7 @@ __device__ __forceinline__ void body16w(const ConvParams p, const int n_items, c
   }
   size_t IMGPIX_ = (size_t)p.h * p.w;
 
-  struct Tile { int img, ty0, tx0, slab; };
-  auto tile_of = [&](int item) -> Tile {
-    const int tile = item / NS;
-    const int img = tile / TPI_;
-    const int trem = tile - img * TPI_;
-    const int tyi = trem / TX_;
-    return Tile{img, tyi * TH, (trem - tyi * TX_) * TW, item - tile * NS};
-  };
+  auto tile_of = [&](int item) -> Tile { return tile_at<NS, TH, TW>(item, TPI_, TX_); };
 
   // CHAIN: state of the current layer (set by the layer loop at the end of this function)
   float* bias_cur = bias_s;                 // LDS: the bias the accumulators start from ([2][COUT] in a chain)
@@ -815,35 +806,26 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body16w_x3_chain_kernel(co
 
 template <int CINW, int COUT, int EPI, int ABL = 0, bool X3 = false>
 static hipError_t launch_body16w_one(ConvParams p, hipStream_t stream, int grid_cap) {
-  auto kern = [] {
+  constexpr auto kern = [] {
     if constexpr (X3) return conv3x3_body16w_x3_kernel<CINW, COUT, EPI>;
     else return conv3x3_body16w_kernel<CINW, COUT, EPI, ABL>;
   }();
-  static KernelOnce once;
-  int cus = 0;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), LDS_BYTES, &cus);
-  if (e != hipSuccess) return e;
   // per-image buffer descriptors (X3: of the two-plane tensors): byte offsets below 2^31 (bit 31 marks a pixel outside the image)
   if ((size_t)p.h * p.w * COUT >= ((size_t)1 << 29)) return hipErrorInvalidValue;
   p.tiles_x = (p.w + TW - 1) / TW;
   p.tiles_y = (p.h + TH - 1) / TH;
   const long long items = (long long)p.n * p.tiles_x * p.tiles_y * (COUT / 128);
-  if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-  int grid = (int)(items < cus ? items : cus);
-  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), LDS_BYTES, stream, p, (int)items);
-  return hipGetLastError();
+  return launch_persistent<kern>(LDS_BYTES, THREADS, items, 1, grid_cap, stream, p);
 }
 
 template <int CINW, int COUT, int ABL = 0, bool X3 = false>
 static hipError_t launch_body16w_chain_one(ConvParams p, ChainArgs c, hipStream_t stream) {
-  auto kern = [] {
+  constexpr auto kern = [] {
     if constexpr (X3) return conv3x3_body16w_x3_chain_kernel<CINW, COUT>;
     else return conv3x3_body16w_chain_kernel<CINW, COUT, ABL>;
   }();
-  static KernelOnce once;
   int cus = 0;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), LDS_BYTES_CHAIN, &cus);
+  const hipError_t e = prepare_kernel<kern>(LDS_BYTES_CHAIN, &cus);
   if (e != hipSuccess) return e;
   if ((size_t)p.h * p.w * COUT >= ((size_t)1 << 29)) return hipErrorInvalidValue;
   p.tiles_x = (p.w + TW - 1) / TW;
@@ -859,8 +841,7 @@ static hipError_t launch_body16w_chain_one(ConvParams p, ChainArgs c, hipStream_
   if ((unsigned long long)c.n_layers * c.layer_stride >= 0xffffffffull) return hipErrorInvalidValue;
   const int grid = (p.n + c.patches_per_wg - 1) / c.patches_per_wg;
   c.seamless = (c.patches_per_wg >= 2 || COUT == 256) ? 1 : 0;     // see the kernel's header: when no drain is needed
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), LDS_BYTES_CHAIN, stream, p, c);
-  return hipGetLastError();
+  return launch_kernel<kern>(dim3(grid), THREADS, LDS_BYTES_CHAIN, stream, p, c);
 }
 
 // Whole patches per workgroup for the chain kernel, or 0 when a chain would leave CUs idle that the per-layer kernels

@@ -30,10 +30,6 @@ namespace dsen2 {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 using dma::KC; using dma::NT; using dma::THREADS; using dma::QS; using dma::IN_BYTES; using dma::IN_BLOCKS;
 using dma::WCH; using dma::NWBUF; using dma::LDS_BYTES; using dma::wait_vmcnt;
 constexpr int KSTEPS = 4;                   // 8 channels per k-step: one ds_read_b128 feeds 4 MFMAs (k = 2 each)
@@ -69,11 +65,9 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
   const int hsel = lane >> 5;
   const int rh = l31 >> 4, c16 = l31 & 15;
 
-  // persistent schedule: logical ids remapped so that each XCD (blockIdx % 8) walks a contiguous run of items
+  // persistent schedule (conv3x3_items.h): items lid, lid + G, ...
   const int G = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = G >> 3, r8 = G & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lid = xcd_contiguous_id(blockIdx.x, G);
   if (lid >= n_items) return;
   const int my_items = (n_items - lid + G - 1) / G;
   const int tiles_per_img = p.tiles_x * p.tiles_y;
@@ -121,14 +115,10 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
   // base of the lane), validity of the lane's column
   struct OutGeom { int img; unsigned lane_eoff; int ey; bool col_ok; int chb; };
   auto out_geom = [&](int item, bool valid) -> OutGeom {
-    const int tile = item / NS, slab = item - tile * NS;
-    const int img = tile / tiles_per_img;
-    const int trem = tile - img * tiles_per_img;
-    const int tyi = trem / p.tiles_x;
-    const int ty0 = tyi * kTile, tx0 = (trem - tyi * p.tiles_x) * kTile;
-    const int chb = slab * NT + wn * 64 + 4 * hsel;
-    const int ex = tx0 + c16, ey = ty0 + 2 * wp + 8 * rh;
-    return OutGeom{img, (unsigned)((ey * p.w + ex) * COUT + chb), ey, valid && ex < p.w, chb};
+    const Tile t = tile_at<NS>(item, tiles_per_img, p.tiles_x);
+    const int chb = t.slab * NT + wn * 64 + 4 * hsel;
+    const int ex = t.tx0 + c16, ey = t.ty0 + 2 * wp + 8 * rh;
+    return OutGeom{t.img, (unsigned)((ey * p.w + ex) * COUT + chb), ey, valid && ex < p.w, chb};
   };
   auto aux_desc = [&](int img) {
     return __builtin_amdgcn_make_buffer_rsrc(
@@ -338,16 +328,8 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
 
 template <int CIN, int COUT, int EPI, int ABL = 0, int PRE = 0, bool STG = false, bool DEFER = false>
 static hipError_t launch_body32_one(const ConvParams& p, hipStream_t stream) {
-  auto kern = conv3x3_body32_kernel<CIN, COUT, EPI, ABL, PRE, STG, DEFER>;
-  static KernelOnce once;
-  int cus = 0;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), LDS_BYTES, &cus);
-  if (e != hipSuccess) return e;
   const long long items = (long long)p.n * p.tiles_x * p.tiles_y * (COUT / NT);
-  if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-  const int grid = (int)(items < cus ? items : cus);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), LDS_BYTES, stream, p, (int)items);
-  return hipGetLastError();
+  return launch_persistent<conv3x3_body32_kernel<CIN, COUT, EPI, ABL, PRE, STG, DEFER>>(LDS_BYTES, THREADS, items, 1, 0, stream, p);
 }
 
 template <int F>

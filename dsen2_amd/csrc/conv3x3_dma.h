@@ -24,7 +24,7 @@
 //     hipcc inserts for the loads it does track (it counts none of the DMAs);
 //   * a workgroup must not end with a DMA in flight (its LDS may already belong to the next one): vmcnt(0) at exit.
 #pragma once
-#include "dsen2_internal.h"
+#include "conv3x3_items.h"
 
 namespace dsen2 {
 namespace dma {
@@ -94,19 +94,15 @@ struct Stage {
 
   // the tile whose input the following issue_in() calls fetch
   __device__ __forceinline__ void set_stage_item(int item) {
-    const int tile = item / NS;
-    const int img = tile / tiles_per_img;
-    const int trem = tile - img * tiles_per_img;
-    const int tyi = trem / tiles_x;
-    const int ty0 = tyi * kTile, tx0 = (trem - tyi * tiles_x) * kTile;
-    in_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in) + (size_t)img * img_pix * CINW, 0,
+    const Tile t = tile_at<NS>(item, tiles_per_img, tiles_x);
+    in_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in) + (size_t)t.img * img_pix * CINW, 0,
                                                 (unsigned)(img_pix * CINW * 4), 0x00020000);
     if constexpr (LAZY_VOFF) {
-      st_y0 = ty0;
-      st_x0 = tx0;
+      st_y0 = t.ty0;
+      st_x0 = t.tx0;
     } else {
 #pragma unroll
-      for (int b = 0; b < IN_BLOCKS; ++b) in_voff[b] = voff_of(b, ty0, tx0);
+      for (int b = 0; b < IN_BLOCKS; ++b) in_voff[b] = voff_of(b, t.ty0, t.tx0);
     }
   }
 

@@ -20,19 +20,14 @@
 // The MFMA sequence per accumulator is exactly conv3x3_mfma_kernel's first-layer form (per tap: channels (j, 4 + j) for
 // j = 0..3, then the pairs (8, 9)(, (10, 11)); taps in order), so every output bit is the same
 // (tests/test_gpu_forward.py::test_first_layer_without_padding_mfmas_gives_the_same_bits pins it against the generic kernel).
-#include "conv3x3_bf16_common.h"
-#include "dsen2_internal.h"
+#include "conv3x3_first_common.h"
 
 namespace dsen2 {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace first {
-constexpr int THREADS = 512;                        // 8 waves: 2 (64-channel halves) x 4 (pixel quarters: 4 rows x 16)
-constexpr int NT = 128;                             // output channels per item (slab)
+using firstk::THREADS; using firstk::NT;
 constexpr int PSTR = 20;                            // floats per halo pixel in LDS: conflict-free ds_read_b128 over 16 pixels
 constexpr int IN_FLOATS = kHaloPix * PSTR;          // 6480
 constexpr int WCH = 16 * NT;                        // floats per tap of packed weights [g: 4][o: 128][j: 4]
@@ -41,6 +36,12 @@ constexpr int W_FLOATS = 9 * WCH;                   // one slab, all taps, in gl
 constexpr int W3_FLOATS = 9 * WCH3;                 // 13,824 floats = 54 KB in LDS
 constexpr size_t LDS_BYTES = (size_t)(W3_FLOATS + 2 * IN_FLOATS + NT) * sizeof(float);      // 107,648 B
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+// the gather's operand format (conv3x3_first_common.h): [halo pixel][channel], floats; a lane without an element does not write
+struct Fmt {
+  static constexpr int PITCH = PSTR;
+  static __device__ __forceinline__ int none(int, int) { return -1; }
+  static __device__ __forceinline__ bool has(int pk) { return pk >= 0; }
+};
 }  // namespace first
 
 }  // namespace
@@ -53,7 +54,6 @@ __global__ __launch_bounds__(first::THREADS, 2) void conv3x3_first_kernel(const 
   using namespace first;
   constexpr int NS = COUT / NT;
   constexpr int MB = 2, PB = 2;
-  static_assert(CREAL % 2 == 0 && CREAL > 8 && CREAL <= 16, "first-layer form");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* const w_s = smem;                                          // [9][3][128][4]
   float* const in_s = smem + W3_FLOATS;                             // [2][324][PSTR]
@@ -67,13 +67,11 @@ __global__ __launch_bounds__(first::THREADS, 2) void conv3x3_first_kernel(const 
   const int l31 = lane & 31;
   const int hsel = lane >> 5;
 
-  // persistent schedule (XCD-contiguous like the body kernels); a workgroup keeps ONE output slab: item = tile * NS + slab
+  // persistent schedule (conv3x3_items.h); a workgroup keeps ONE output slab: item = tile * NS + slab
   const int G = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = G >> 3, r8 = G & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lid = xcd_contiguous_id(blockIdx.x, G);
   if (lid >= n_items) return;
-  const int slab = lid % NS;                                        // G is a multiple of NS (launcher)
+  const int slab = lid % NS;                                        // G is a multiple of NS (launch_persistent)
   const int my_items = (n_items - lid + G - 1) / G;
   const int tiles_per_img = p.tiles_x * p.tiles_y;
   const size_t plane = (size_t)p.h * p.w;
@@ -90,56 +88,18 @@ __global__ __launch_bounds__(first::THREADS, 2) void conv3x3_first_kernel(const 
     if (tid < NT) bias_s[tid] = p.bias[slab * NT + tid];
   }
 
-  // ---- gather geometry of one halo tile (the same for every tile) ----
-  // Per input tensor T (10 m: 4 channels, 20 m: 6, 60 m: CREAL - 10) the CT x 324 values of a halo tile are fetched in
-  // rounds of 512 threads, channel outer / halo pixel inner: consecutive lanes read consecutive pixels of an 18-pixel row
-  // segment of ONE plane, through a per-image buffer descriptor (an out-of-range offset returns the zero padding).
-  // One register per round: pk = hx | hy << 5 | (channel inside its tensor) << 10 | (LDS float offset) << 13, negative = no element.
-  constexpr int C10 = 4, C20 = 6, C60 = CREAL - 10;
-  constexpr int R10 = (C10 * kHaloPix + THREADS - 1) / THREADS, R20 = (C20 * kHaloPix + THREADS - 1) / THREADS,
-                R60 = (C60 * kHaloPix + THREADS - 1) / THREADS;
-  constexpr int ROUNDS = R10 + R20 + R60;                           // 7 (10 channels) or 9 (12)
+  // ---- gather geometry of one halo tile (conv3x3_first_common.h) ----
+  using Ga = firstk::Gather<CREAL, Fmt>;
+  constexpr int ROUNDS = Ga::ROUNDS;
   int pk[ROUNDS];
-  {
-    auto setup = [&](int r0, int rounds, int ct, int cbase) __attribute__((always_inline)) {
-#pragma unroll
-      for (int r = 0; r < rounds; ++r) {
-        const int e = r * THREADS + tid;
-        const int c = e / kHaloPix, hp = e - c * kHaloPix;
-        const int hy = hp / kHalo, hx = hp - hy * kHalo;
-        const bool have = e < ct * kHaloPix;
-        pk[r0 + r] = have ? hx | hy << 5 | c << 10 | (hp * PSTR + cbase + c) << 13 : -1;
-      }
-    };
-    setup(0, R10, C10, 0);
-    setup(R10, R20, C20, C10);
-    if constexpr (R60 > 0) setup(R10 + R20, R60, C60, C10 + C20);
-  }
-  struct Tile { int img, ty0, tx0; };
-  auto tile_of = [&](int item) -> Tile {
-    const int tile = item / NS;
-    const int img = tile / tiles_per_img;
-    const int trem = tile - img * tiles_per_img;
-    const int tyi = trem / p.tiles_x;
-    return Tile{img, tyi * kTile, (trem - tyi * p.tiles_x) * kTile};
-  };
+  Ga::setup(tid, pk, Ga::X10);
+  Ga::setup(tid, pk, Ga::X20);
+  if constexpr (Ga::R60 > 0) Ga::setup(tid, pk, Ga::X60);
+  auto tile_of = [&](int item) -> Tile { return tile_at<NS>(item, tiles_per_img, p.tiles_x); };
   auto gather = [&](const Tile& t, float (&v)[ROUNDS]) __attribute__((always_inline)) {
-    auto fetch = [&](int r0, int rounds, const float* x, int ct) __attribute__((always_inline)) {
-      const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x) + (size_t)t.img * ct * plane, 0,
-                                                          (unsigned)(ct * plane * 4), 0x00020000);
-#pragma unroll
-      for (int r = 0; r < rounds; ++r) {
-        int k = pk[r0 + r];
-        asm volatile("" : "+v"(k));      // derive the addresses here, every tile: hoisted out of the item loop they are spilled
-        const int gy = t.ty0 - 1 + ((k >> 5) & 31), gx = t.tx0 - 1 + (k & 31);
-        const bool inb = k >= 0 && (unsigned)gy < (unsigned)p.h && (unsigned)gx < (unsigned)p.w;
-        const unsigned voff = inb ? (unsigned)((((k >> 10) & 7) * (int)plane + gy * p.w + gx) * 4) : 0x80000000u;
-        v[r0 + r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, 0, 0));
-      }
-    };
-    fetch(0, R10, p.in, C10);
-    fetch(R10, R20, p.aux, C20);
-    if constexpr (R60 > 0) fetch(R10 + R20, R60, f.x60, C60);
+    Ga::fetch(pk, v, Ga::X10, p.in, t, p, plane);
+    Ga::fetch(pk, v, Ga::X20, p.aux, t, p, plane);
+    if constexpr (Ga::R60 > 0) Ga::fetch(pk, v, Ga::X60, f.x60, t, p, plane);
   };
   auto scatter = [&](float* buf, const float (&v)[ROUNDS]) __attribute__((always_inline)) {
 #pragma unroll
@@ -274,44 +234,27 @@ __global__ __launch_bounds__(first::THREADS, 2) void conv3x3_first_kernel(const 
 
 template <int CREAL, int COUT, int EPI, int ABL = 0>
 static hipError_t launch_first_one(const ConvParams& p, const FirstInputs& f, hipStream_t stream) {
-  auto kern = conv3x3_first_kernel<CREAL, COUT, EPI, ABL>;
-  static KernelOnce once;
-  int cus = 0;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), first::LDS_BYTES, &cus);
-  if (e != hipSuccess) return e;
-  constexpr int NS = COUT / first::NT;
-  const long long items = (long long)p.n * p.tiles_x * p.tiles_y * NS;
-  if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-  int grid = (int)(items < cus ? items : cus);
-  grid -= grid % NS;                                   // a workgroup keeps one slab: item stride G must preserve item % NS
-  if (grid < NS) grid = NS;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(first::THREADS), first::LDS_BYTES, stream, p, f, (int)items);
-  return hipGetLastError();
+  return firstk::launch_first_kernel<conv3x3_first_kernel<CREAL, COUT, EPI, ABL>, COUT>(first::LDS_BYTES, p, f, stream);
 }
 
 // p.in = x10, p.aux = x20 (NCHW), p.wpk / p.bias: weights packed for the tile kernel (KC 16, NT 128); p.out NHWC fp32
-// (kEpiRelu only).  hipErrorNotSupported: channel counts
-// other than 10 / 12 (the generic pack_inputs + conv3x3_mfma path handles those).
+// (kEpiRelu only: the output is written through pointers, so only the inputs bound the image size).  hipErrorNotSupported:
+// see check_first_launch.
 hipError_t launch_conv3x3_first(const ConvParams& p, const FirstInputs& f, int cout, int epilogue, hipStream_t stream, int ablate) {
   const int creal = f.c10 + f.c20 + f.c60;
-  if (f.c10 != 4 || f.c20 != 6 || (f.c60 != 0 && f.c60 != 2)) return hipErrorNotSupported;      // the Sentinel-2 band groups
-  if ((size_t)p.h * p.w * 6 * 4 >= ((size_t)1 << 31)) return hipErrorNotSupported;               // 32-bit offsets inside one image
-  if (!p.in || !p.aux || (f.c60 > 0 && !f.x60) || !p.out) return hipErrorInvalidValue;
-  if ((size_t)p.h * p.w * (size_t)cout * 4 >= ((size_t)1 << 40)) return hipErrorInvalidValue;
-#define DSEN2_CASE(CR, CO) \
-  if (creal == CR && cout == CO) return launch_first_one<CR, CO, kEpiRelu>(p, f, stream);
+  const hipError_t e = firstk::check_first_launch(p, f, 0, false);
+  if (e != hipSuccess) return e;
   if (epilogue != kEpiRelu) return hipErrorInvalidValue;      // the (hi, lo) / (hi | xl, lo16) plane forms: conv3x3_first16.hip
 #ifdef DSEN2_DIAG
-  if (creal == 10 && cout == 128 && epilogue == kEpiRelu) {
-    if (ablate == 1) return launch_first_one<10, 128, kEpiRelu, 1>(p, f, stream);
-    if (ablate == 2) return launch_first_one<10, 128, kEpiRelu, 2>(p, f, stream);
-    if (ablate == 4) return launch_first_one<10, 128, kEpiRelu, 4>(p, f, stream);
-    if (ablate == 3) return launch_first_one<10, 128, kEpiRelu, 3>(p, f, stream);
-    if (ablate == 5) return launch_first_one<10, 128, kEpiRelu, 5>(p, f, stream);
-    if (ablate == 7) return launch_first_one<10, 128, kEpiRelu, 7>(p, f, stream);
-    if (ablate == 6) return launch_first_one<10, 128, kEpiRelu, 6>(p, f, stream);
+  if (creal == 10 && cout == 128) {
+#define DSEN2_ABL(M) \
+  if (ablate == M) return launch_first_one<10, 128, kEpiRelu, M>(p, f, stream);
+    DSEN2_ABL(1) DSEN2_ABL(2) DSEN2_ABL(4) DSEN2_ABL(3) DSEN2_ABL(5) DSEN2_ABL(7) DSEN2_ABL(6)
+#undef DSEN2_ABL
   }
 #endif
+#define DSEN2_CASE(CR, CO) \
+  if (creal == CR && cout == CO) return launch_first_one<CR, CO, kEpiRelu>(p, f, stream);
   DSEN2_CASE(10, 128) DSEN2_CASE(12, 128) DSEN2_CASE(10, 256) DSEN2_CASE(12, 256)
 #undef DSEN2_CASE
   return hipErrorNotSupported;

@@ -11,7 +11,7 @@
 // (268 MB at the bench batch; precision 2: 402 MB), with the gather of the 21 MB of inputs and the MFMAs underneath:
 // 139.5 -> 59 us (precision 2: 161 -> 90 us), store-bound at 4.6 TB/s (profiles/r05_first16_ab.txt).
 //
-// Structure = conv3x3_first.hip's, operand format aside:
+// Structure = conv3x3_first.hip's, operand format aside (what the two have in common word for word: conv3x3_first_common.h):
 //   * persistent, one workgroup of 8 waves per CU walks tiles lid, lid + G, ... and keeps ONE 128-channel output slab:
 //     its weights ([plane][tap][k half][o: 128][8 bf16] — the packed buffer is the LDS image) and bias go to LDS once;
 //   * the halo tile of the NEXT item is gathered from the NCHW inputs into registers (per-image buffer descriptors; the
@@ -30,8 +30,7 @@
 // DSen2_60's 12 channels) and the whole-network gates of tests/test_gpu_bf16.py / test_gpu_bf16x3.py.
 #include <string.h>
 
-#include "conv3x3_bf16_common.h"
-#include "dsen2_internal.h"
+#include "conv3x3_first_common.h"
 
 // Compile-time switches of VARIANT builds only (python -m dsen2_amd.build --variant NAME -D...; tools/ab_first16.sh): the
 // product is built with the default.  FIRST16_ABL = timing-only ablation mask (1 no stores, 2 no MFMAs, 4 no input gather;
@@ -44,14 +43,10 @@ namespace dsen2 {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 using bf16k::bf16x8;
-using bf16k::u32x4;
 
 namespace first16 {
-constexpr int THREADS = 512;                        // 8 waves: 2 (64-channel halves) x 4 (pixel quarters: 4 rows x 16)
-constexpr int NT = 128;                             // output channels per item (slab)
+using firstk::THREADS; using firstk::NT;
 constexpr int KSLOTS = 16;                          // channel slots of one MFMA (K of v_mfma_f32_32x32x16_bf16)
 constexpr int PITCH = 24;                           // bf16 per halo pixel in LDS (48 B: 16 slots + padding against bank conflicts)
 constexpr int IN_PLANE_BYTES = kHaloPix * PITCH * 2;              // 15,552
@@ -59,6 +54,15 @@ constexpr int W_PLANE_U16 = 9 * 2 * NT * 8;                       // one slab, o
 constexpr int W_PLANE_BYTES = W_PLANE_U16 * 2;                    // 36,864
 constexpr size_t lds_bytes(bool x3) { return (size_t)(x3 ? 2 : 1) * (W_PLANE_BYTES + 2 * IN_PLANE_BYTES) + NT * sizeof(float); }
 static_assert(lds_bytes(true) <= 160 * 1024, "LDS budget");
+// The gather's operand format (conv3x3_first_common.h): [halo pixel][16 channel slots + padding], bf16 index inside a plane.  A
+// lane without an element (bit 30) still loads (out of range: zero) and still WRITES — into the padding slots 16-23 of a halo
+// pixel, which no operand read covers — so that the loop body has NO divergent branch: hipcc then counts the vector-memory
+// operations in flight exactly (see the waits in the kernel).
+struct Fmt {
+  static constexpr int PITCH = first16::PITCH;
+  static __device__ __forceinline__ int none(int hp, int c) { return (hp * PITCH + KSLOTS + (c & 7)) << 13 | 1 << 30; }
+  static __device__ __forceinline__ bool has(int pk) { return (pk >> 30) == 0; }
+};
 }  // namespace first16
 
 }  // namespace
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(first16::THREADS, 2) void conv3x3_first16_kernel(co
   constexpr int NS = COUT / NT;
   constexpr int MB = 2, PB = 2;
   constexpr int PL = X3 ? 2 : 1;                    // operand planes on each side
-  static_assert(CREAL % 2 == 0 && CREAL > 8 && CREAL <= KSLOTS, "first-layer form");
+  static_assert(CREAL <= KSLOTS, "first-layer form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const w_s = smem;                                               // [PL][9][2][128][8] bf16
   char* const in_s = smem + PL * W_PLANE_BYTES;                         // [2 buffers][PL][324][PITCH] bf16
@@ -86,13 +90,11 @@ __global__ __launch_bounds__(first16::THREADS, 2) void conv3x3_first16_kernel(co
   const int l31 = lane & 31;
   const int hsel = lane >> 5;
 
-  // persistent schedule (XCD-contiguous like the body kernels); a workgroup keeps ONE output slab: item = tile * NS + slab
+  // persistent schedule (conv3x3_items.h); a workgroup keeps ONE output slab: item = tile * NS + slab
   const int G = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = G >> 3, r8 = G & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lid = xcd_contiguous_id(blockIdx.x, G);
   if (lid >= n_items) return;
-  const int slab = lid % NS;                                        // G is a multiple of NS (launcher)
+  const int slab = lid % NS;                                        // G is a multiple of NS (launch_persistent)
   const int my_items = (n_items - lid + G - 1) / G;
   const int tiles_per_img = p.tiles_x * p.tiles_y;
   const size_t plane = (size_t)p.h * p.w;
@@ -109,57 +111,18 @@ __global__ __launch_bounds__(first16::THREADS, 2) void conv3x3_first16_kernel(co
   }
   __syncthreads();
 
-  // ---- gather geometry of one halo tile (conv3x3_first.hip's): per input tensor its CT x 324 values in rounds of 512
-  // threads, channel outer / halo pixel inner.  pk = hx | hy << 5 | (channel inside its tensor) << 10 | (LDS bf16 index of
-  // the value inside a plane) << 13 | (no element) << 30.  A lane without an element still loads (out of range: zero) and
-  // still writes — into the padding slots 16-23 of a halo pixel, which no operand read covers — so that the loop body has NO
-  // divergent branch: hipcc then counts the vector-memory operations in flight exactly (see the waits below) ----
-  constexpr int C10 = 4, C20 = 6, C60 = CREAL - 10;
-  constexpr int R10 = (C10 * kHaloPix + THREADS - 1) / THREADS, R20 = (C20 * kHaloPix + THREADS - 1) / THREADS,
-                R60 = (C60 * kHaloPix + THREADS - 1) / THREADS;
-  constexpr int ROUNDS = R10 + R20 + R60;                           // 7 (10 channels) or 9 (12)
+  // ---- gather geometry of one halo tile (conv3x3_first_common.h; pk >> 13 = bf16 index inside a plane, bit 30 = no element) ----
+  using Ga = firstk::Gather<CREAL, Fmt>;
+  constexpr int ROUNDS = Ga::ROUNDS;
   int pk[ROUNDS];
-  {
-    auto setup = [&](int r0, int rounds, int ct, int cbase) __attribute__((always_inline)) {
-#pragma unroll
-      for (int r = 0; r < rounds; ++r) {
-        const int e = r * THREADS + tid;
-        const int c = e / kHaloPix, hp = e - c * kHaloPix;
-        const int hy = hp / kHalo, hx = hp - hy * kHalo;
-        const bool have = e < ct * kHaloPix;
-        pk[r0 + r] = have ? hx | hy << 5 | c << 10 | (hp * PITCH + cbase + c) << 13
-                          : (hp * PITCH + KSLOTS + (c & 7)) << 13 | 1 << 30;
-      }
-    };
-    setup(0, R10, C10, 0);
-    setup(R10, R20, C20, C10);
-    if constexpr (R60 > 0) setup(R10 + R20, R60, C60, C10 + C20);
-  }
-  struct Tile { int img, ty0, tx0; };
-  auto tile_of = [&](int item) -> Tile {
-    const int tile = item / NS;
-    const int img = tile / tiles_per_img;
-    const int trem = tile - img * tiles_per_img;
-    const int tyi = trem / p.tiles_x;
-    return Tile{img, tyi * kTile, (trem - tyi * p.tiles_x) * kTile};
-  };
+  Ga::setup(tid, pk, Ga::X10);
+  Ga::setup(tid, pk, Ga::X20);
+  if constexpr (Ga::R60 > 0) Ga::setup(tid, pk, Ga::X60);
+  auto tile_of = [&](int item) -> Tile { return tile_at<NS>(item, tiles_per_img, p.tiles_x); };
   auto gather = [&](const Tile& t, float (&v)[ROUNDS]) __attribute__((always_inline)) {
-    auto fetch = [&](int r0, int rounds, const float* x, int ct) __attribute__((always_inline)) {
-      const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x) + (size_t)t.img * ct * plane, 0,
-                                                          (unsigned)(ct * plane * 4), 0x00020000);
-#pragma unroll
-      for (int r = 0; r < rounds; ++r) {
-        int k = pk[r0 + r];
-        asm volatile("" : "+v"(k));      // derive the addresses here, every tile: hoisted out of the item loop they are spilled
-        const int gy = t.ty0 - 1 + ((k >> 5) & 31), gx = t.tx0 - 1 + (k & 31);
-        const bool inb = (k >> 30) == 0 && (unsigned)gy < (unsigned)p.h && (unsigned)gx < (unsigned)p.w;
-        const unsigned voff = inb ? (unsigned)((((k >> 10) & 7) * (int)plane + gy * p.w + gx) * 4) : 0x80000000u;
-        v[r0 + r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, 0, 0));
-      }
-    };
-    fetch(0, R10, p.in, C10);
-    fetch(R10, R20, p.aux, C20);
-    if constexpr (R60 > 0) fetch(R10 + R20, R60, f.x60, C60);
+    Ga::fetch(pk, v, Ga::X10, p.in, t, p, plane);
+    Ga::fetch(pk, v, Ga::X20, p.aux, t, p, plane);
+    if constexpr (Ga::R60 > 0) Ga::fetch(pk, v, Ga::X60, f.x60, t, p, plane);
   };
   // fp32 -> bf16 (RNE; precision 2: also the remainder's bf16) into one input buffer (PL planes, IN_PLANE_BYTES apart)
   auto scatter = [&](char* buf, const float (&v)[ROUNDS]) __attribute__((always_inline)) {
@@ -196,7 +159,7 @@ __global__ __launch_bounds__(first16::THREADS, 2) void conv3x3_first16_kernel(co
   // stores at an out-of-range offset, which the hardware drops — no divergent branch in the loop body.
   struct StoreRsrc { __amdgpu_buffer_rsrc_t out, out2; };
   auto store_rsrc = [&](const Tile& t) __attribute__((always_inline)) -> StoreRsrc {
-    const size_t plane_bytes = (size_t)(COUT / 8) * img_pix * 16;      // one image, one plane: < 2^31 (launcher)
+    const size_t plane_bytes = (size_t)(COUT / 8) * img_pix * 16;      // one image: PL planes < 2^31 (check_first_launch)
     const int img = __builtin_amdgcn_readfirstlane(t.img);
     return StoreRsrc{__builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (size_t)img * PL * plane_bytes, 0,
                                                        (unsigned)(PL * plane_bytes), 0x00020000),
@@ -240,7 +203,7 @@ __global__ __launch_bounds__(first16::THREADS, 2) void conv3x3_first16_kernel(co
     } else {
       const int cb = (slab * NT + wn * (32 * MB) + mb * 32) / 8 + g0 + hsel;      // this lane's 8-channel block
       const bool have = valid && y < p.h && x < p.w;
-      // 32-bit arithmetic: every offset inside one image's plane is below 2^31 (launcher); a select, not a branch
+      // 32-bit arithmetic: every offset inside one image's PL planes is below 2^31 (check_first_launch); a select, not a branch
       const unsigned off = have ? ((unsigned)cb * (unsigned)img_pix + (unsigned)(y * p.w + x)) * 16u : 0x80000000u;
       __builtin_amdgcn_raw_buffer_store_b128(ph, so.out, (int)off, 0, 0);
       // hx: plane 0 = hi, plane 1 = xl = bf16(x - hi), one plane further in the same image.  The plane offset goes into the
@@ -335,19 +298,7 @@ __global__ __launch_bounds__(first16::THREADS, 2) void conv3x3_first16_kernel(co
 
 template <int CREAL, int COUT, bool X3>
 static hipError_t launch_first16_one(const ConvParams& p, const FirstInputs& f, hipStream_t stream) {
-  auto kern = conv3x3_first16_kernel<CREAL, COUT, X3>;
-  static KernelOnce once;
-  int cus = 0;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), first16::lds_bytes(X3), &cus);
-  if (e != hipSuccess) return e;
-  constexpr int NS = COUT / first16::NT;
-  const long long items = (long long)p.n * p.tiles_x * p.tiles_y * NS;
-  if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-  int grid = (int)(items < cus ? items : cus);
-  grid -= grid % NS;                                   // a workgroup keeps one slab: item stride G must preserve item % NS
-  if (grid < NS) grid = NS;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(first16::THREADS), first16::lds_bytes(X3), stream, p, f, (int)items);
-  return hipGetLastError();
+  return firstk::launch_first_kernel<conv3x3_first16_kernel<CREAL, COUT, X3>, COUT>(first16::lds_bytes(X3), p, f, stream);
 }
 
 size_t first16_weight_u16(int cout, bool x3) { return (size_t)(cout / first16::NT) * (x3 ? 2 : 1) * first16::W_PLANE_U16; }
@@ -382,14 +333,12 @@ void pack_first16_weights_host(const float* k, int cin, int cout, bool x3, uint1
 }
 
 // p.in = x10, p.aux = x20 (NCHW); p.wpk = pack_first16_weights_host(.., x3); p.bias fp32 [cout].  x3 = false: p.out / p.out2 =
-// the blocked (hi, lo) planes; x3 = true: p.out = hx (hi | xl planes), p.out2 = lo16.  hipErrorNotSupported: channel counts
-// other than 4 + 6 (+ 2) (the generic pack_inputs + conv3x3_mfma path handles those).
+// the blocked (hi, lo) planes; x3 = true: p.out = hx (hi | xl planes), p.out2 = lo16.  hipErrorNotSupported: see
+// check_first_launch — p.out is the larger output tensor: 2 bytes per channel and plane.
 hipError_t launch_conv3x3_first16(const ConvParams& p, const FirstInputs& f, int cout, bool x3, hipStream_t stream) {
   const int creal = f.c10 + f.c20 + f.c60;
-  if (f.c10 != 4 || f.c20 != 6 || (f.c60 != 0 && f.c60 != 2)) return hipErrorNotSupported;      // the Sentinel-2 band groups
-  if ((size_t)p.h * p.w * 6 * 4 >= ((size_t)1 << 31)) return hipErrorNotSupported;               // 32-bit offsets inside one image
-  if (!p.in || !p.aux || (f.c60 > 0 && !f.x60) || !p.out || !p.out2 || !p.wpk || !p.bias) return hipErrorInvalidValue;
-  if ((size_t)p.h * p.w * (size_t)cout * 4 >= ((size_t)1 << 40)) return hipErrorInvalidValue;
+  const hipError_t e = firstk::check_first_launch(p, f, (size_t)(x3 ? 2 : 1) * cout * 2, true);
+  if (e != hipSuccess) return e;
 #define DSEN2_CASE(CR, CO)                                                                               \
   if (creal == CR && cout == CO) return x3 ? launch_first16_one<CR, CO, true>(p, f, stream) : launch_first16_one<CR, CO, false>(p, f, stream);
   DSEN2_CASE(10, 128) DSEN2_CASE(12, 128) DSEN2_CASE(10, 256) DSEN2_CASE(12, 256)

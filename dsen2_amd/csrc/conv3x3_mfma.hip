@@ -25,12 +25,8 @@
 #include <vector>
 
 #include "conv3x3_bf16_common.h"
-#include "dsen2_internal.h"
 
 namespace dsen2 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int CIN, int KC, int NT, int NWAVES>
 struct ConvCfg {
@@ -78,19 +74,10 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
   const int l31 = lane & 31;
   const int hsel = lane >> 5;
 
-  // workgroup -> tile.  Blocks b, b+8, b+16.. share an XCD (and its L2): give each XCD a contiguous run of
-  // tiles so neighbouring tiles' halos and the weight stream hit in that L2.  Bijective for any grid size.
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  // workgroup -> tile (conv3x3_items.h: each XCD takes a contiguous run of tiles), blockIdx.y = output slab
   const int slab = blockIdx.y;
-  const int tiles_per_img = p.tiles_x * p.tiles_y;
-  const int img = lid / tiles_per_img;
-  const int trem = lid - img * tiles_per_img;
-  const int tyi = trem / p.tiles_x;
-  const int ty0 = tyi * kTile;
-  const int tx0 = (trem - tyi * p.tiles_x) * kTile;
+  const Tile t = tile_at<1>(xcd_contiguous_id(blockIdx.x, gridDim.x), p.tiles_x * p.tiles_y, p.tiles_x);
+  const int img = t.img, ty0 = t.ty0, tx0 = t.tx0;
   const size_t img_pix = (size_t)p.h * p.w;
   const float* const in_img = p.in + (size_t)img * img_pix * CIN;
   const float* const w_slab = p.wpk + (size_t)slab * C::NCHUNK * C::WCH;
@@ -289,15 +276,12 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
 template <int CIN, int KC, int COUT, int NT, int EPI, int NWAVES = 8, int WAVES_PER_SIMD = 2, int CREAL = 0>
 static hipError_t launch_one(const ConvParams& p, hipStream_t stream) {
   using C = ConvCfg<CIN, KC, NT, NWAVES>;
-  auto kern = conv3x3_mfma_kernel<CIN, KC, COUT, NT, EPI, NWAVES, WAVES_PER_SIMD, CREAL>;
-  static KernelOnce once;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), C::LDS_BYTES, nullptr);
+  constexpr auto kern = conv3x3_mfma_kernel<CIN, KC, COUT, NT, EPI, NWAVES, WAVES_PER_SIMD, CREAL>;
+  const hipError_t e = prepare_kernel<kern>(C::LDS_BYTES, nullptr);
   if (e != hipSuccess) return e;
   const long long tiles = (long long)p.n * p.tiles_x * p.tiles_y;
   if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-  dim3 grid((unsigned)tiles, COUT / NT, 1);
-  hipLaunchKernelGGL(kern, grid, dim3(C::THREADS), C::LDS_BYTES, stream, p);
-  return hipGetLastError();
+  return launch_kernel<kern>(dim3((unsigned)tiles, COUT / NT, 1), C::THREADS, C::LDS_BYTES, stream, p);
 }
 
 template <int F>

@@ -5,11 +5,9 @@
 // 16x16x4 form (round 1's kernel: 171 us at the bench config) still 62 %.  A vector kernel pads nothing (v_fma_f32
 // with the weight as scalar operand: 78.6 TFLOP/s, half the matrix rate): 122 us, same bits.  The packed
 // v_pk_fma_f32 form and other restructurings are in experiments/README.md (bit-identical, none faster).
-#include "dsen2_internal.h"
+#include "conv3x3_items.h"
 
 namespace dsen2 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Cout <= 8 (more output channels fall back to the padded 32-wide MFMA block of conv3x3_mfma.hip).  One thread = one pixel x
 // half of the output channels (wave parity h: outputs h, h+2, h+4, ..): NSLOT accumulators, v_fma_f32 with the
@@ -47,14 +45,8 @@ __global__ __launch_bounds__(outv::THREADS, 2) void conv3x3_out_valu_kernel(cons
   // apart) every group was 2-way conflicted: SQ_LDS_BANK_CONFLICT 50 % of this kernel's LDS cycles.
   const int row = 2 * (wave >> 1) + 8 * ((lane >> 4) & 1) + (lane >> 5), col = lane & 15;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int tiles_per_img = p.tiles_x * p.tiles_y;
-  const int img = lid / tiles_per_img;
-  const int trem = lid - img * tiles_per_img;
-  const int tyi = trem / p.tiles_x;
-  const int ty0 = tyi * kTile, tx0 = (trem - tyi * p.tiles_x) * kTile;
+  const Tile t = tile_at<1>(xcd_contiguous_id(blockIdx.x, gridDim.x), p.tiles_x * p.tiles_y, p.tiles_x);
+  const int img = t.img, ty0 = t.ty0, tx0 = t.tx0;
   const size_t img_pix = (size_t)p.h * p.w;
   const float* const in_img = p.in + (size_t)img * img_pix * CIN;
 
@@ -108,7 +100,6 @@ __global__ __launch_bounds__(outv::THREADS, 2) void conv3x3_out_valu_kernel(cons
     // 18 half taps of 8 chain positions: the 32 weights of half tap k+1 are fetched (two s_load_dwordx16) while half
     // tap k's FMAs run.  The scheduling barriers keep hipcc from hoisting a whole chunk's 576 scalars at once, which
     // it then has to park in VGPR lanes (v_writelane / v_readlane per weight).
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     // constant address space + wave-uniform address = scalar loads (s_load_dwordx16) into SGPRs, whatever else the
     // optimiser believes about aliasing
     typedef const __attribute__((address_space(4))) f32x16* const_f32x16_ptr;
@@ -166,14 +157,12 @@ __global__ __launch_bounds__(outv::THREADS, 2) void conv3x3_out_valu_kernel(cons
 
 template <int CIN, int NSLOT>
 static hipError_t launch_out_valu_one(const ConvParams& p, hipStream_t stream) {
-  auto kern = conv3x3_out_valu_kernel<CIN, NSLOT>;
-  static KernelOnce once;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), outv::LDS_BYTES, nullptr);
+  constexpr auto kern = conv3x3_out_valu_kernel<CIN, NSLOT>;
+  const hipError_t e = prepare_kernel<kern>(outv::LDS_BYTES, nullptr);
   if (e != hipSuccess) return e;
   const long long tiles = (long long)p.n * p.tiles_x * p.tiles_y;
   if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(outv::THREADS), outv::LDS_BYTES, stream, p);
-  return hipGetLastError();
+  return launch_kernel<kern>(dim3((unsigned)tiles), outv::THREADS, outv::LDS_BYTES, stream, p);
 }
 
 // weights packed by pack_out_valu_weights_host

@@ -20,13 +20,9 @@
 // A workgroup takes whole images (or strips of rows with one recomputed row above and below when there are few images).
 // Bench config (512 x 32 x 32, F = 128, Cout 6): 79 us against 121 on the vector units; FETCH_SIZE = the algorithmic 281 MB.
 // What bounds it and what was tried: profiles/archive/r03_ablation.md §4, HISTORY.md §3.2.
-#include "dsen2_internal.h"
+#include "conv3x3_items.h"
 
 namespace dsen2 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace outm {
 constexpr int THREADS = 512;
@@ -387,18 +383,16 @@ static bool out_mfma_geometry(const ConvParams& p, int feat, int cus, OutMfmaGeo
 
 template <int F, int CL>
 static hipError_t launch_out_mfma_one(const ConvParams& p, hipStream_t stream, int ablate) {
-  auto kern = conv3x3_out_mfma_kernel<F, CL>;
-  static KernelOnce once;
+  constexpr auto kern = conv3x3_out_mfma_kernel<F, CL>;
   int cus = 0;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), outm::LDS_LIMIT, &cus);
+  const hipError_t e = prepare_kernel<kern>(outm::LDS_LIMIT, &cus);
   if (e != hipSuccess) return e;
   OutMfmaGeom g;
   size_t lds = 0;
   if (!out_mfma_geometry(p, F, cus, &g, &lds)) return hipErrorNotSupported;
   g.ablate = ablate;
   const unsigned grid = (unsigned)(g.njobs < cus ? g.njobs : cus);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(outm::THREADS), lds, stream, p, g);
-  return hipGetLastError();
+  return launch_kernel<kern>(dim3(grid), outm::THREADS, lds, stream, p, g);
 }
 
 // p.wpk = the weights packed by pack_out_mfma_weights_host.  hipErrorNotSupported (and nothing launched) when the shape does not

@@ -18,14 +18,11 @@
 //     to the workspace, and a second kernel adds the partials of every element in split order — no float atomics, so the
 //     result is the same bits on every run.  The bias partials come from the same staged g tiles.
 // Pixels outside the image are zeros in the staged g tile: they add exact zeros to the accumulators.
-#include "dsen2_internal.h"
+#include "conv3x3_items.h"
 
 namespace dsen2 {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWgTY = 4, kWgTX = 16, kWgPix = kWgTY * kWgTX;   // pixel tile
 constexpr int kWgHY = kWgTY + 2, kWgHX = kWgTX + 2, kWgHalo = kWgHY * kWgHX;
@@ -76,6 +73,8 @@ __global__ __launch_bounds__(kWgThreads, 1) void conv3x3_wgrad_kernel(const Wgra
 
   f32x4 ar[C::A_ROUNDS], gr[C::G_ROUNDS];
   auto load_tile = [&](long long t) {
+    // (not conv3x3_items.h's tile_at: 64-bit tile counter, and through the shared function hipcc orders this kernel's scalar
+    // code differently)
     const int img = (int)(t / tiles_per_img);
     const int trem = (int)(t - (long long)img * tiles_per_img);
     const int ty0 = (trem / p.tiles_x) * kWgTY, tx0 = (trem % p.tiles_x) * kWgTX;
@@ -220,13 +219,11 @@ bool wgrad_geom(int n, int h, int w, int ca, int cg, WgradGeom* g) {
 template <int WCO, int WCI>
 hipError_t launch_wgrad_one(const WgradParams& p, hipStream_t stream) {
   using C = WgCfg<WCO, WCI>;
-  auto kern = conv3x3_wgrad_kernel<WCO, WCI>;
-  static KernelOnce once;
-  hipError_t e = once.prepare(reinterpret_cast<const void*>(kern), C::LDS_BYTES, nullptr);
+  constexpr auto kern = conv3x3_wgrad_kernel<WCO, WCI>;
+  const hipError_t e = prepare_kernel<kern>(C::LDS_BYTES, nullptr);
   if (e != hipSuccess) return e;
-  dim3 grid((unsigned)p.splits, (unsigned)((p.cop / C::COB) * (p.cip / C::CIB)), 1);
-  hipLaunchKernelGGL(kern, grid, dim3(kWgThreads), C::LDS_BYTES, stream, p);
-  return hipGetLastError();
+  const dim3 grid((unsigned)p.splits, (unsigned)((p.cop / C::COB) * (p.cip / C::CIB)), 1);
+  return launch_kernel<kern>(grid, kWgThreads, C::LDS_BYTES, stream, p);
 }
 
 }  // namespace

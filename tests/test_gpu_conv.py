@@ -177,7 +177,8 @@ def test_delta_kernel_shifts_exactly():
         assert not other.any()
 
 
-@pytest.mark.parametrize('feat,n,h,w', [(128, 3, 21, 37), (128, 40, 32, 32), (256, 2, 32, 32), (256, 1, 19, 16)])
+@pytest.mark.parametrize('feat,n,h,w', [(128, 3, 21, 37), (128, 40, 32, 32), (256, 2, 32, 32), (256, 1, 19, 16),
+                                        (256, 1, 1, 1)])       # two items, one per slab: the smallest launch
 def test_persistent_kernel_is_bit_identical_to_the_reference_structure(feat, n, h, w):
     """The persistent DMA-fed body kernel (conv3x3_body32.hip) and the one-tile-per-workgroup kernel
     (dsen2_conv3x3_nhwc_ref) compute the same sums in the same order: bit-identical, both epilogues."""

@@ -18,7 +18,10 @@ from oracle import c_oracle
 from oracle import dsen2_oracle as do
 
 SHAPES = [((4, 6), 128, 2, 32, 32), ((4, 6, 2), 128, 1, 21, 37), ((4, 6), 256, 1, 16, 33), ((4, 6, 2), 256, 2, 5, 70),
-          ((4, 6), 128, 1, 1, 1), ((4, 6), 128, 300, 16, 16), ((4, 6), 256, 3, 48, 40)]
+          ((4, 6), 128, 1, 1, 1), ((4, 6), 128, 300, 16, 16), ((4, 6), 256, 3, 48, 40),
+          # two slabs: one tile (items = slabs = 2: the smallest grid the launcher may choose), and 300 items on 256 CUs (a
+          # workgroup keeps its slab across lid, lid + G, ...)
+          ((4, 6), 256, 1, 1, 1), ((4, 6), 256, 150, 16, 16)]
 
 
 def bf16_round(a):

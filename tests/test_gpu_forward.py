@@ -172,21 +172,24 @@ def test_a_handle_belongs_to_the_device_it_was_created_on():
         assert m.body_launches(1, 16, 16) == 2
 
 
-@pytest.mark.parametrize('bands,feat', [((4, 6), 128), ((4, 6, 2), 128), ((4, 6), 256)])
-def test_first_layer_without_padding_mfmas_gives_the_same_bits(bands, feat):
+@pytest.mark.parametrize('bands,feat,n,h,w', [((4, 6), 128, 3, 21, 37), ((4, 6, 2), 128, 3, 21, 37), ((4, 6), 256, 3, 21, 37),
+                                              ((4, 6), 256, 1, 1, 1), ((4, 6), 256, 150, 16, 16)],
+                         ids=['bands0-128', 'bands1-128', 'bands2-256', 'bands3-256-1-1-1', 'bands4-256-150-16-16'])
+def test_first_layer_without_padding_mfmas_gives_the_same_bits(bands, feat, n, h, w):
     """The model's first convolution issues MFMAs for its 10 / 12 real input channels only; the single-layer entry
     point on the SAME data zero-padded to 16 channels runs the generic kernel with all 16.  Skipping zero terms must
-    not change one bit (ragged image; a d=0 network = first convolution + output convolution)."""
+    not change one bit (ragged image; a d=0 network = first convolution + output convolution).  The last two cases are the
+    persistent launcher's grid rule with two output slabs: one tile (items = slabs = 2) and 300 items on 256 CUs."""
     from dsen2_amd.DSen2Net import conv3x3_nhwc, s2model
     cin, cout = sum(bands), bands[-1]
     flat = do.he_uniform_weights(cin, cout, 0, feat, seed=8, bias_scale=0.05)
-    xs = do.synthetic_inputs(3, 21, 37, bands, seed=8)
+    xs = do.synthetic_inputs(n, h, w, bands, seed=8)
     m = s2model(tuple((b, None, None) for b in bands), num_layers=0, feature_size=feat)
     m.set_weights_flat(flat)
     dev = [torch.from_numpy(a).cuda() for a in xs]
     y = m.forward_device(dev)
     (k0, b0), (k1, b1) = do.split_weights(flat, cin, cout, 0, feat)
-    x16 = torch.zeros((3, 21, 37, 16), device='cuda')
+    x16 = torch.zeros((n, h, w, 16), device='cuda')
     x16[..., :cin] = torch.cat(dev, dim=1).permute(0, 2, 3, 1)
     k16 = np.zeros((3, 3, 16, feat), np.float32)
     k16[:, :, :cin] = k0
