@@ -78,6 +78,14 @@ SIGNATURES = {
     'dsen2_band_errors': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'dsen2_imresize_band_errors': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                            c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_quality_workspace_bytes': (c_int, [c_int, ctypes.POINTER(c_size_t)]),
+    'dsen2_uiq_map': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'dsen2_uiq_sums': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_sam_sums': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_imresize_uiq_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                        c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_imresize_sam_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                        c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -28,29 +28,13 @@
 
 #pragma clang fp contract(off)
 
+#include "resample.h"        // as_double, resample_one, kResizeMaxTaps: shared with quality_metrics.hip
+
 namespace dsen2 {
 
 constexpr int kResizeThreads = 256;
-constexpr int kResizeMaxTaps = 256;
 constexpr int kErrMaxBands = 64;
 constexpr int kErrMaxBlocks = 4096;              // partial pairs per band: the workspace is kErrMaxBlocks * C * 2 doubles
-
-template <typename T> __device__ __forceinline__ double as_double(T v) { return (double)v; }        // exact for all three
-
-// one output: slice = in + a * N * B + b, taps of output o at w[k * M + o] / idx[k * M + o]
-template <typename T>
-__device__ __forceinline__ double resample_one(const T* __restrict__ column, const double* __restrict__ w, const int* __restrict__ idx,
-                                               int P, int M, int N, int B, unsigned o) {
-  auto term = [&](int k) {
-    int q = idx[(size_t)k * M + o];
-    q = q < 0 ? 0 : (q >= N ? N - 1 : q);
-    return __dmul_rn(as_double(column[(size_t)q * B]), w[(size_t)k * M + o]);
-  };
-  double acc = term(0);
-#pragma unroll 4
-  for (int k = 1; k < P; ++k) acc = __dadd_rn(acc, term(k));
-  return acc;
-}
 
 // the block's per-thread pairs -> one pair per band in partials[block][c][2]; blockDim.x = npix * C, band of a thread = tid % C
 __device__ __forceinline__ void block_band_sums(double sq, double sb, int C, double* __restrict__ partials) {

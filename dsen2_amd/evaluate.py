@@ -1,7 +1,7 @@
 """python -m dsen2_amd.evaluate — score the predictions of `python -m dsen2_amd.train --predict` against the ground truth, beside
 the MATLAB-bicubic baseline: the numbers the reference publishes (testing/demoDSen2.py:45-48, 70-73), computed on the GPU.
 
-    python -m dsen2_amd.evaluate --path P [--run_60] [--model_nr s2_038_] [--json OUT]
+    python -m dsen2_amd.evaluate --path P [--run_60] [--model_nr s2_038_] [--json OUT] [--uiq] [--sam] [--block_size 8]
 
 For every directory below <P>/test/ (test60/ with --run_60) that holds no_tiling/ — what `python -m dsen2_amd.create_patches
 --test_data` wrote — it loads the ground truth no_tiling/data20_gt.npy (data60_gt) and the downsampled bands no_tiling/data20.npy
@@ -16,6 +16,11 @@ For every directory below <P>/test/ (test60/ with --run_60) that holds no_tiling
 then RMSE and SRE (dB) per band, and after the last tile the mean of each column over all tiles.  --json writes every value
 unrounded.  The bicubic baseline never stores the enlarged image: the second resampling pass adds up the errors itself
 (metrics.bicubic_error_sums).  The downsampled bands are read as create_patches stores them, float32.
+
+--uiq and --sam add the paper's two further metrics (metrics.UIQ, metrics.SAM; csrc/quality_metrics.hip): a `UIQ` column per
+method in every table — the universal image quality index per band over --block_size x --block_size windows (default 8) — and a
+`SAM [deg]` line per method, the mean spectral angle; the JSON entries gain band_uiq, uiq (the mean over the bands), sam and
+sam_pixels.  The baseline's enlarged image is not stored for these either.  Without the two flags nothing changes.
 """
 import argparse
 import glob
@@ -34,6 +39,9 @@ def parse_args(argv=None):
     p.add_argument('--run_60', action='store_true', help='Score the 60->10m test sets (test60/). Default 20->10m (test/).')
     p.add_argument('--model_nr', default=MODEL_NR, help='Prefix of the prediction files: <model_nr>-predict.npy.')
     p.add_argument('--json', default=None, metavar='OUT', help='Write every value, unrounded, to this file.')
+    p.add_argument('--uiq', action='store_true', help='Also the universal image quality index (Wang & Bovik) per band.')
+    p.add_argument('--sam', action='store_true', help='Also the spectral angle mapper, in degrees.')
+    p.add_argument('--block_size', type=int, default=8, metavar='N', help='Window of the UIQ, N x N (2..16). Default 8.')
     return p.parse_args(argv)
 
 
@@ -43,24 +51,51 @@ def _entry(sums):
     return {'rmse': total, 'band_rmse': rmse.tolist(), 'band_sre': sre.tolist()}
 
 
+def _quality(entry, uiq_sums, sam_sums):
+    """Adds what --uiq / --sam computed (None: not asked for) to an entry."""
+    from . import metrics
+    if uiq_sums is not None:
+        band, mean = metrics.uiq_scores(uiq_sums)
+        entry.update(band_uiq=band.tolist(), uiq=mean)
+    if sam_sums is not None:
+        entry.update(sam=metrics.sam_score(sam_sums), sam_pixels=int(sam_sums[1]))
+    return entry
+
+
 def _table(rows, bands):
-    print('%-8s' % 'band' + ''.join('%24s' % name for name, _ in rows))
-    print('%-8s' % '' + ''.join('%12s%12s' % ('RMSE', 'SRE [dB]') for _ in rows))
+    uiq = all('band_uiq' in e for _, e in rows)
+    width = 36 if uiq else 24
+    print('%-8s' % 'band' + ''.join('%*s' % (width, name) for name, _ in rows))
+    print('%-8s' % '' + ''.join('%12s%12s' % ('RMSE', 'SRE [dB]') + ('%12s' % 'UIQ' if uiq else '') for _ in rows))
     for c in range(bands):
-        print('%-8d' % c + ''.join('%12.4f%12.4f' % (e['band_rmse'][c], e['band_sre'][c]) for _, e in rows))
+        print('%-8d' % c + ''.join('%12.4f%12.4f' % (e['band_rmse'][c], e['band_sre'][c]) + ('%12.4f' % e['band_uiq'][c] if uiq else '')
+                                  for _, e in rows))
+    if uiq:
+        print('%-8s' % 'mean' + ''.join('%24s%12.4f' % ('', e['uiq']) for _, e in rows))
+    for name, e in rows:
+        if 'sam' in e:
+            print('{} SAM [deg]: {:.4f}'.format(name, e['sam']))
 
 
-def evaluate_tile(d, run_60, model_nr):
+def evaluate_tile(d, run_60, model_nr, uiq=False, sam=False, block_size=8):
     """{'bicubic': {...}, 'dsen2': {...} or absent} of one test directory."""
     from . import metrics
     key, scale = ('data60', 6) if run_60 else ('data20', 2)
     gt = np.load(os.path.join(d, 'no_tiling', key + '_gt.npy'))
     lr = np.load(os.path.join(d, 'no_tiling', key + '.npy'))
+    if uiq or sam:
+        gt = metrics._device_image(gt)               # several metrics of the same images: one upload of each
+        lr = metrics._device_image(lr, gt.device)
     out = {}
     pred = os.path.join(d, model_nr + '-predict.npy')
     if os.path.exists(pred):
-        out['dsen2'] = _entry(metrics.error_sums(np.load(pred), gt))
-    out['bicubic'] = _entry(metrics.bicubic_error_sums(lr, gt, scale))
+        x = np.load(pred)
+        if uiq or sam:
+            x = metrics._device_image(x, gt.device)
+        out['dsen2'] = _quality(_entry(metrics.error_sums(x, gt)), metrics.uiq_sums(x, gt, block_size) if uiq else None,
+                                metrics.sam_sums(x, gt) if sam else None)
+    out['bicubic'] = _quality(_entry(metrics.bicubic_error_sums(lr, gt, scale)), metrics.bicubic_uiq_sums(lr, gt, scale, block_size) if uiq else None,
+                              metrics.bicubic_sam_sums(lr, gt, scale) if sam else None)
     return out
 
 
@@ -75,7 +110,8 @@ def main(argv=None):
     result = {'model_nr': args.model_nr, 'folder': folder, 'tiles': {}}
     for d in tiles:
         name = os.path.basename(d)
-        r = evaluate_tile(d, args.run_60, args.model_nr)
+        r = evaluate_tile(d, args.run_60, args.model_nr, args.uiq, args.sam, args.block_size) if args.uiq or args.sam else \
+            evaluate_tile(d, args.run_60, args.model_nr)
         result['tiles'][name] = r
         print(name)
         if 'dsen2' in r:
@@ -92,6 +128,10 @@ def main(argv=None):
             mean[k] = {'tiles': len(have), 'rmse': float(np.mean([e['rmse'] for e in have])),
                        'band_rmse': np.mean([e['band_rmse'] for e in have], axis=0).tolist(),
                        'band_sre': np.mean([e['band_sre'] for e in have], axis=0).tolist()}
+            if args.uiq:
+                mean[k].update(band_uiq=np.mean([e['band_uiq'] for e in have], axis=0).tolist(), uiq=float(np.mean([e['uiq'] for e in have])))
+            if args.sam:
+                mean[k].update(sam=float(np.mean([e['sam'] for e in have])))
     result['mean'] = mean
     print('Mean over {} tile(s)'.format(len(tiles)))
     for k, label in (('dsen2', 'DSen2'), ('bicubic', 'Bicubic')):

@@ -1,10 +1,19 @@
-"""Scores of the evaluation step, computed on the GPU (csrc/imresize.hip: dsen2_band_errors, dsen2_imresize_band_errors).
+"""Scores of the evaluation step, computed on the GPU (csrc/imresize.hip: dsen2_band_errors, dsen2_imresize_band_errors;
+csrc/quality_metrics.hip: dsen2_uiq_map, dsen2_uiq_sums, dsen2_sam_sums and their fused bicubic forms).
 
     RMSE(x1, x2)                   testing/demoDSen2.py:31-35 — over all elements in float64; prints 'RMSE: %.4f', returns the value
     band_errors(x, gt)             (rmse [C], sre [C]) per band of two HWC images
     bicubic_errors(lr, gt, scale)  the same for the MATLAB-bicubic enlargement of `lr` — the demo's 'Bicubic:' baseline — without
                                    ever storing the enlarged image (the second resampling pass accumulates the errors itself)
     error_sums / bicubic_error_sums   the float64 sums underneath: [C, 3] = sum (x - gt)^2, sum gt, pixels
+    UIQ(x, gt, block_size=8)       (uiq [C], mean over the bands): the universal image quality index of Wang & Bovik (img_qi.m), the mean
+                                   of the quality map over all block_size x block_size windows of a band
+    uiq_map(x, gt, block_size=8)   that map, float64 [H - block_size + 1, W - block_size + 1, C] ([.., ..] for 2-D inputs)
+    SAM(x, gt)                     the spectral angle mapper: the mean angle in degrees between the two spectra of a pixel, over the
+                                   pixels whose spectrum is zero in neither image
+    bicubic_UIQ(lr, gt, scale, block_size=8) / bicubic_SAM(lr, gt, scale)   the same for the bicubic enlargement of `lr`, never stored
+    uiq_sums / sam_sums / bicubic_uiq_sums / bicubic_sam_sums   the sums underneath: [C, 2] = sum of the map, windows; [2] = sum of
+                                   the angles, pixels counted
 
 SRE is the paper's signal-to-reconstruction error per band, 10 log10(mean(gt)^2 / mean((x - gt)^2)) in dB.  Inputs are numpy
 arrays or device tensors, [H, W, C] or [H, W]; float32 and float64 go to the kernel as they are, uint16 (a Sentinel-2 raster as the
@@ -138,3 +147,197 @@ def RMSE(x1, x2):
     rms = scores(error_sums_device(a, b).cpu().numpy())[2]
     print('RMSE: {:.4f}'.format(rms))
     return rms
+
+
+# ---- UIQ and SAM (csrc/quality_metrics.hip) ----
+
+def _shape3(a):
+    shape = tuple(a.shape)
+    if len(shape) == 2:
+        shape = shape + (1,)
+    if len(shape) != 3:
+        raise ValueError('an [H, W] or [H, W, C] image is expected, not %d dimensions' % len(shape))
+    return shape
+
+
+def _check_pair(x, gt, block_size=None):
+    """The refusals that need no GPU: shapes, bands, block size.  Returns the common [H, W, C]."""
+    shape = _shape3(x)
+    if _shape3(gt) != shape:
+        raise ValueError('images of shape %r and %r' % (tuple(x.shape), tuple(gt.shape)))
+    if min(shape) < 1 or shape[2] > 64:
+        raise ValueError('an image of shape %r: empty, or more than 64 bands' % (shape,))
+    if block_size is not None:
+        _check_block(shape, block_size)
+    return shape
+
+
+def _check_block(shape, block_size):
+    if int(block_size) != block_size or not 2 <= block_size <= 16:
+        raise ValueError('block_size %r outside 2..16' % (block_size,))
+    if shape[0] < block_size or shape[1] < block_size:
+        raise ValueError('an image of %d x %d is smaller than the %d x %d block' % (shape[0], shape[1], block_size, block_size))
+
+
+def _bicubic_shape(lr, gt, scale):
+    """The refusals of the fused bicubic forms that need no GPU; returns the enlargement's [H, W, C]."""
+    from . import imresize as ir
+    shape = _shape3(lr)
+    size = ir.plan(shape, scalar_scale=scale)[0]
+    want = (size[0], size[1], shape[2])
+    if _shape3(gt) != want:
+        raise ValueError('ground truth of shape %r for an enlargement to %r' % (tuple(gt.shape), want))
+    if shape[2] > 64:
+        raise ValueError('an image of shape %r: more than 64 bands' % (shape,))
+    return want
+
+
+def _quality_workspace(c, device):
+    import torch
+    from . import _lib
+    n = ctypes.c_size_t(0)
+    _lib.call('dsen2_quality_workspace_bytes', c, ctypes.byref(n))
+    return torch.empty(n.value, dtype=torch.uint8, device=device), n.value
+
+
+def uiq_map_device(x, gt, block_size=8):
+    """float64 device tensor [H - B + 1, W - B + 1, C] of two [H, W, C] float32 / float64 device tensors (dsen2_uiq_map)."""
+    import torch
+    from . import _lib, patches
+    h, w, c = _check_pair(x, gt, block_size)
+    out = torch.empty((h - block_size + 1, w - block_size + 1, c), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call('dsen2_uiq_map', patches._ptr(x), _lib_dtype(x), patches._ptr(gt), _lib_dtype(gt), h, w, c, int(block_size),
+                  patches._ptr(out), patches._stream(x.device))
+    return out
+
+
+def uiq_sums_device(x, gt, block_size=8):
+    """[C, 2] float64 device tensor: per band the sum of the quality map and the number of windows; the map is never stored."""
+    import torch
+    from . import _lib, patches
+    h, w, c = _check_pair(x, gt, block_size)
+    out = torch.empty((c, 2), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        work, nbytes = _quality_workspace(c, x.device)
+        _lib.call('dsen2_uiq_sums', patches._ptr(x), _lib_dtype(x), patches._ptr(gt), _lib_dtype(gt), h, w, c, int(block_size),
+                  patches._ptr(work), nbytes, patches._ptr(out), patches._stream(x.device))
+    return out
+
+
+def sam_sums_device(x, gt):
+    """[2] float64 device tensor: the sum of the spectral angles in degrees and the number of pixels counted."""
+    import torch
+    from . import _lib, patches
+    h, w, c = _check_pair(x, gt)
+    out = torch.empty((2,), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        work, nbytes = _quality_workspace(c, x.device)
+        _lib.call('dsen2_sam_sums', patches._ptr(x), _lib_dtype(x), patches._ptr(gt), _lib_dtype(gt), h, w, c, patches._ptr(work), nbytes,
+                  patches._ptr(out), patches._stream(x.device))
+    return out
+
+
+def resample_quality_sums_device(mid, axis, out_length, taps, gt, block_size=None):
+    """uiq_sums_device (block_size given) or sam_sums_device (None) of resize_axis_device(mid, axis, out_length, taps) against gt,
+    in one pass that never stores the resampled image (dsen2_imresize_uiq_sums / dsen2_imresize_sam_sums)."""
+    import torch
+    from . import _lib, patches
+    h, w, c = mid.shape
+    out = torch.empty((c, 2) if block_size is not None else (2,), dtype=torch.float64, device=mid.device)
+    with torch.cuda.device(mid.device):
+        work, nbytes = _quality_workspace(c, mid.device)
+        head = (patches._ptr(mid), _lib_dtype(mid), h, w, c, axis, out_length, patches._ptr(taps[0]), patches._ptr(taps[1]), taps[2],
+                patches._ptr(gt), _lib_dtype(gt))
+        tail = (patches._ptr(work), nbytes, patches._ptr(out), patches._stream(mid.device))
+        if block_size is not None:
+            _lib.call('dsen2_imresize_uiq_sums', *(head + (int(block_size),) + tail))
+        else:
+            _lib.call('dsen2_imresize_sam_sums', *(head + tail))
+    return out
+
+
+def _pair_on_device(x, gt, block_size=None):
+    _check_pair(np.asarray(x) if not hasattr(x, 'shape') else x, np.asarray(gt) if not hasattr(gt, 'shape') else gt, block_size)
+    x = _device_image(x)
+    return x, _device_image(gt, x.device)
+
+
+def uiq_map(x, gt, block_size=8):
+    """The UIQ quality map, float64 ndarray [H - B + 1, W - B + 1, C] (2-D inputs: [H - B + 1, W - B + 1])."""
+    flat = len(np.shape(x)) == 2
+    a, b = _pair_on_device(x, gt, block_size)
+    q = uiq_map_device(a, b, block_size).cpu().numpy()
+    return q[:, :, 0] if flat else q
+
+
+def uiq_sums(x, gt, block_size=8):
+    """[C, 2] float64 ndarray: per band the sum of the quality map and the number of windows."""
+    a, b = _pair_on_device(x, gt, block_size)
+    return uiq_sums_device(a, b, block_size).cpu().numpy()
+
+
+def sam_sums(x, gt):
+    """[2] float64 ndarray: the sum of the spectral angles in degrees, the number of pixels counted."""
+    a, b = _pair_on_device(x, gt)
+    return sam_sums_device(a, b).cpu().numpy()
+
+
+def _bicubic_quality_sums(lr, gt, scale, block_size):
+    from . import imresize as ir
+    lr = lr if hasattr(lr, 'shape') else np.asarray(lr)
+    gt = gt if hasattr(gt, 'shape') else np.asarray(gt)
+    want = _bicubic_shape(lr, gt, scale)
+    if block_size is not None:
+        _check_block(want, block_size)
+    lr = _device_image(lr)
+    gt = _device_image(gt, lr.device)
+    size, scales, order = ir.plan(lr.shape, scalar_scale=scale)
+    first, second = order
+    mid = ir.resize_axis_device(lr, first, size[first], ir.device_taps(lr.shape[first], size[first], scales[first], lr.device))
+    taps = ir.device_taps(mid.shape[second], size[second], scales[second], lr.device)
+    return resample_quality_sums_device(mid, second, size[second], taps, gt, block_size).cpu().numpy()
+
+
+def bicubic_uiq_sums(lr, gt, scale, block_size=8):
+    """uiq_sums(imresize(lr, scale), gt, block_size), the same bits, with the second resampling pass computed inside the UIQ
+    kernel's loader: the enlarged image is never stored."""
+    return _bicubic_quality_sums(lr, gt, scale, block_size)
+
+
+def bicubic_sam_sums(lr, gt, scale):
+    """sam_sums(imresize(lr, scale), gt), the same bits, without storing the enlarged image."""
+    return _bicubic_quality_sums(lr, gt, scale, None)
+
+
+def uiq_scores(sums):
+    """(uiq [C], mean over the bands) of a [C, 2] array of sums."""
+    sums = np.asarray(sums, np.float64)
+    band = sums[:, 0] / sums[:, 1]
+    return band, float(np.mean(band))
+
+
+def sam_score(sums):
+    """SAM in degrees of a [2] array of sums; nan when no pixel was counted."""
+    sums = np.asarray(sums, np.float64)
+    return float(sums[0] / sums[1]) if sums[1] else float('nan')
+
+
+def UIQ(x, gt, block_size=8):
+    """(uiq [C] float64 ndarray, its mean over the bands): the universal image quality index of two HWC images."""
+    return uiq_scores(uiq_sums(x, gt, block_size))
+
+
+def SAM(x, gt):
+    """The spectral angle mapper of two HWC images, in degrees."""
+    return sam_score(sam_sums(x, gt))
+
+
+def bicubic_UIQ(lr, gt, scale, block_size=8):
+    """UIQ of the bicubic enlargement of `lr` by `scale` against `gt`."""
+    return uiq_scores(bicubic_uiq_sums(lr, gt, scale, block_size))
+
+
+def bicubic_SAM(lr, gt, scale):
+    """SAM of the bicubic enlargement of `lr` by `scale` against `gt`, in degrees."""
+    return sam_score(bicubic_sam_sums(lr, gt, scale))

@@ -314,6 +314,36 @@ int dsen2_imresize_band_errors(const void *dev_in, int dtype, int H, int W, int 
                                const int *dev_indices, int taps, const void *dev_gt, int gt_dtype, void *dev_work,
                                size_t work_bytes, double *dev_out, void *stream);
 
+/* ---- evaluation: the paper's two further metrics, UIQ (Wang & Bovik 2002, img_qi.m) and SAM (csrc/quality_metrics.hip) ----
+ * All arithmetic is float64, every product and every sum rounded on its own, in the order DESIGN §7 writes down; the images are
+ * HWC [H,W,C], float32 or float64 each, 1 <= C <= 64, fewer than 2^31 elements.
+ * dsen2_uiq_map: per band the quality index of every block x block window (2 <= block <= 16, valid windows only, NOT sliding
+ *   sums: each window sum is `block` sequential additions along the row, then `block` along the column):
+ *   dev_map_f64 [H-block+1, W-block+1, C].  The map is a pure function of its inputs: the same bits on every run.
+ * dsen2_uiq_sums: dev_out[2c .. 2c+1] = { sum of that map over band c, number of windows } without ever storing the map; the
+ *   UIQ of band c is their quotient, the UIQ of the image the mean over the bands.
+ * dsen2_sam_sums: dev_out[0 .. 1] = { sum over the pixels of acos(clamp(<x,y> / (|x| |y|), -1, 1)) in degrees, pixels counted }; a
+ *   pixel whose spectrum is zero in either image is left out.  SAM is the quotient.
+ * dsen2_imresize_uiq_sums / dsen2_imresize_sam_sums: the same sums for x = the resampling pass dsen2_imresize_axis(dev_in, ...)
+ *   would write, against dev_gt (which has the OUTPUT's shape), computed tile by tile and never stored: the second pass of the
+ *   bicubic baseline.  The same bits as dsen2_imresize_axis followed by dsen2_uiq_sums / dsen2_sam_sums.
+ * The order of every addition depends on the shapes only (no float atomics).  dev_work: dsen2_quality_workspace_bytes(C) bytes
+ * of device scratch.  DSEN2_ERR_INVALID with nothing launched: H or W (of the image the metric sees) below block, block outside
+ * 2..16, C outside 1..64, any other dtype, a null pointer, 2^31 elements or more; DSEN2_ERR_WORKSPACE: a short workspace. */
+int dsen2_quality_workspace_bytes(int C, size_t *bytes);
+int dsen2_uiq_map(const void *dev_x, int x_dtype, const void *dev_y, int y_dtype, int H, int W, int C, int block,
+                  double *dev_map_f64, void *stream);
+int dsen2_uiq_sums(const void *dev_x, int x_dtype, const void *dev_y, int y_dtype, int H, int W, int C, int block, void *dev_work,
+                   size_t work_bytes, double *dev_out, void *stream);
+int dsen2_sam_sums(const void *dev_x, int x_dtype, const void *dev_y, int y_dtype, int H, int W, int C, void *dev_work,
+                   size_t work_bytes, double *dev_out, void *stream);
+int dsen2_imresize_uiq_sums(const void *dev_in, int dtype, int H, int W, int C, int axis, int out_len, const double *dev_weights,
+                            const int *dev_indices, int taps, const void *dev_gt, int gt_dtype, int block, void *dev_work,
+                            size_t work_bytes, double *dev_out, void *stream);
+int dsen2_imresize_sam_sums(const void *dev_in, int dtype, int H, int W, int C, int axis, int out_len, const double *dev_weights,
+                            const int *dev_indices, int taps, const void *dev_gt, int gt_dtype, void *dev_work, size_t work_bytes,
+                            double *dev_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,10 @@
 """The evaluation kernels against the HBM roofline: the two passes of the bicubic `imresize`, the per-band error reduction, and the
 fused form (second pass + reduction, nothing stored) against resize-then-reduce, at the sizes of a full Sentinel-2 tile:
   5490^2 x 6 float32 enlarged by 2  (the 20 m bands)       1830^2 x 2 float32 enlarged by 6  (the 60 m bands)
-    python tools/bench_evaluate.py [--out FILE.jsonl] [--iters N]
+and the paper's two further metrics at the enlarged sizes (csrc/quality_metrics.hip): the UIQ map, the fused UIQ sums, SAM, and
+their fused bicubic forms (second pass inside the metric's loader, nothing stored), with the numpy restatement of the UIQ
+(tests/quality_restatement.py) timed on one 2000^2 band of the host for context.
+    python tools/bench_evaluate.py [--out FILE.jsonl] [--iters N] [--numpy_band 2000]
 
 `algorithmic bytes` of a kernel = what it must read once + what it must write once (the tap tables, a few hundred KB that stay in
 L2, are left out); the roofline is those bytes over the 6.3 TB/s a float4 copy reaches on this part (8 TB/s is the HBM3E spec:
@@ -40,6 +43,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None, help='also append the JSON lines to this file')
     ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--numpy_band', type=int, default=2000, help='side of the one band the numpy restatement of the UIQ is timed on (0: skip)')
     args = ap.parse_args()
     dev = P.default_device()
     lines = []
@@ -80,7 +84,53 @@ def main():
              'stored_GB_avoided': round(on * on * c * 8 / 1e9, 3), 'max_relative_difference_of_the_sums': rel}
         lines.append(json.dumps(d))
         print(lines[-1], flush=True)
+        # UIQ (8 x 8 windows) and SAM: algorithmic bytes = each input read once (the map's float64 store is listed beside them)
+        size = '%dx%dx%d' % (on, on, c)
+        win = (on - 7) * (on - 7) * c
+        ms = timeit(lambda: metrics.uiq_map_device(full, gt), args.iters)
+        emit('uiq_map float64 vs float32 %s' % size, ms, on * on * c * 12, stored_MB=round(win * 8 / 1e6, 1), Gwindows_per_s=round(win / ms / 1e6, 2))
+        ms_u = timeit(lambda: metrics.uiq_sums_device(full, gt), args.iters)
+        emit('uiq_sums float64 vs float32 %s' % size, ms_u, on * on * c * 12, Gwindows_per_s=round(win / ms_u / 1e6, 2))
+        x32 = full.to(torch.float32)
+        ms = timeit(lambda: metrics.uiq_sums_device(x32, gt), args.iters)
+        emit('uiq_sums float32 vs float32 %s' % size, ms, on * on * c * 8, Gwindows_per_s=round(win / ms / 1e6, 2))
+        ms_s = timeit(lambda: metrics.sam_sums_device(full, gt), args.iters)
+        emit('sam_sums float64 vs float32 %s' % size, ms_s, on * on * c * 12)
+        ms = timeit(lambda: metrics.sam_sums_device(x32, gt), args.iters)
+        emit('sam_sums float32 vs float32 %s' % size, ms, on * on * c * 8)
+        del x32
+        ms_fu = timeit(lambda: metrics.resample_quality_sums_device(mid, 1, on, t1, gt, 8), args.iters)
+        emit('imresize pass 2 + uiq_sums fused %s' % tag, ms_fu, on * n * c * 8 + on * on * c * 4, taps=taps, Gwindows_per_s=round(win / ms_fu / 1e6, 2))
+        ms_fs = timeit(lambda: metrics.resample_quality_sums_device(mid, 1, on, t1, gt), args.iters)
+        emit('imresize pass 2 + sam_sums fused %s' % tag, ms_fs, on * n * c * 8 + on * on * c * 4, taps=taps)
+        same = bool(torch.equal(metrics.resample_quality_sums_device(mid, 1, on, t1, gt, 8), metrics.uiq_sums_device(full, gt))
+                    and torch.equal(metrics.resample_quality_sums_device(mid, 1, on, t1, gt), metrics.sam_sums_device(full, gt)))
+        d = {'compare': 'UIQ and SAM of the bicubic baseline of %s: resize, store, measure vs fused' % tag,
+             'uiq_store_then_measure_ms': round(ms_a + ms_b + ms_u, 4), 'uiq_fused_ms': round(ms_a + ms_fu, 4),
+             'sam_store_then_measure_ms': round(ms_a + ms_b + ms_s, 4), 'sam_fused_ms': round(ms_a + ms_fs, 4),
+             'stored_GB_avoided': round(on * on * c * 8 / 1e9, 3), 'identical_bits': same}
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
         del lr, gt, mid, full
+    if args.numpy_band:
+        # context: the numpy restatement of the UIQ on the host against the kernel, one band
+        import time
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        import quality_restatement as qr
+        nb = args.numpy_band
+        rng = np.random.RandomState(0)
+        y = (rng.rand(nb, nb) * 4000).astype(np.float32)
+        x = y + rng.normal(0, 20, y.shape).astype(np.float32)
+        t = time.time()
+        q = qr.uiq_map(x, y)
+        host_s = time.time() - t
+        tx, ty = torch.from_numpy(x[:, :, None]).to(dev), torch.from_numpy(y[:, :, None]).to(dev)
+        ms = timeit(lambda: metrics.uiq_sums_device(tx, ty), args.iters)
+        same = metrics.uiq_map_device(tx, ty).cpu().numpy()[:, :, 0].tobytes() == q.tobytes()
+        d = {'compare': 'UIQ of one %dx%d float32 band: numpy restatement on the host vs uiq_sums' % (nb, nb), 'numpy_s': round(host_s, 3),
+             'uiq_sums_ms': round(ms, 4), 'map_identical_bits': same}
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')
