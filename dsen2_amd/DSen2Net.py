@@ -282,13 +282,15 @@ class S2Model(object):
                       iters, _stream_ptr(self.device), ctypes.byref(ms))
         return ms.value
 
-    # -- training (fp32 models; include/dsen2_hip.h "training") ---------------------------------
+    # -- training (fp32 and bf16x3 models; include/dsen2_hip.h "training") -----------------------
+    TRAINABLE = ('fp32', 'bf16x3')
+
     def compile(self, optimizer='nadam', loss='mean_absolute_error', metrics=None):
         """keras Model.compile for the reference's recipe: optimizer 'nadam' or a training.Nadam, loss
         'mean_absolute_error' (MSE is always reported as the metric).  The optimizer state starts fresh."""
         from . import training
-        if self.precision != 'fp32':
-            raise ValueError('training needs an fp32 model (this one is %r)' % self.precision)
+        if self.precision not in self.TRAINABLE:
+            raise ValueError('training needs an fp32 or a bf16x3 model (this one is %r)' % self.precision)
         if loss not in ('mean_absolute_error', 'mae'):
             raise ValueError("loss must be 'mean_absolute_error', got %r" % (loss,))
         if isinstance(optimizer, str):
@@ -323,8 +325,8 @@ class S2Model(object):
     def gradients_device(self, xs, y, grad, loss2, out=None, workspace=None):
         """dsen2_model_gradients on device tensors: xs as forward_device, y [n,cout,h,w]; grad [num_params] and loss2 [2]
         receive the keras-flat gradient and (mae, mse); out (optional) the forward output."""
-        if self.precision != 'fp32':
-            raise ValueError('training needs an fp32 model (this one is %r)' % self.precision)
+        if self.precision not in self.TRAINABLE:
+            raise ValueError('training needs an fp32 or a bf16x3 model (this one is %r)' % self.precision)
         n, _, h, w = xs[0].shape
         for x, c in zip(xs, self.bands):
             if tuple(x.shape) != (n, c, h, w) or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
@@ -515,6 +517,30 @@ def split3_f32(x):
     with torch.cuda.device(x.device):
         _lib.call('dsen2_split3_f32', _ptr(x), _ptr(hx), _ptr(lo), n, h, w, c, _stream_ptr(x.device))
     return hx, lo
+
+
+def join3_f32(hx, lo):
+    """The exact inverse of split3_f32: (hx, lo16) -> fp32 NHWC (include/dsen2_hip.h: dsen2_join3_f32)."""
+    n, _, b, h, w, e = hx.shape
+    out = torch.empty((n, h, w, b * e), dtype=torch.float32, device=hx.device)
+    with torch.cuda.device(hx.device):
+        _lib.call('dsen2_join3_f32', _ptr(hx), _ptr(lo), _ptr(out), n, h, w, b * e, _stream_ptr(hx.device))
+    return out
+
+
+def conv3x3_wgrad_bf16x3(a_planes, g_planes, scale=1.0):
+    """Kernel-level entry point of the bf16x3 weight gradient (include/dsen2_hip.h: dsen2_conv3x3_wgrad_bf16x3): a_planes,
+    g_planes int16 [n, 2, feat/8, h, w, 8] two-plane operand tensors.  Returns (dw [3, 3, feat, feat] HWIO, db [feat])."""
+    n, _, b, h, w, e = a_planes.shape
+    feat = b * e
+    if tuple(g_planes.shape) != tuple(a_planes.shape) or not a_planes.is_contiguous() or not g_planes.is_contiguous():
+        raise ValueError('a_planes and g_planes must be contiguous tensors of the same shape')
+    dw = torch.empty((3, 3, feat, feat), dtype=torch.float32, device=a_planes.device)
+    db = torch.empty(feat, dtype=torch.float32, device=a_planes.device)
+    with torch.cuda.device(a_planes.device):
+        _lib.call('dsen2_conv3x3_wgrad_bf16x3', _ptr(a_planes), _ptr(g_planes), _ptr(dw), _ptr(db), n, h, w, feat, float(scale),
+                  _stream_ptr(a_planes.device))
+    return dw, db
 
 
 def conv3x3_first_planes(xs, kernel_hwio, bias, precision):

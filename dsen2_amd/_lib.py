@@ -61,6 +61,9 @@ SIGNATURES = {
     'dsen2_nadam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t] + [ctypes.c_float] * 9 + [c_void_p]),
     'dsen2_conv3x3_wgrad': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     ctypes.c_float, c_void_p]),
+    'dsen2_conv3x3_wgrad_bf16x3': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float,
+                                           c_void_p]),
+    'dsen2_join3_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'dsen2_upsample_mirror_bilinear': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_float,
                                                c_void_p]),
     'dsen2_upsample_mirror_bilinear_ref': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_float,

@@ -99,11 +99,14 @@ static int first_layer(const dsen2_model* m, const float* x10, const float* x20,
 // Precision 2, bf16x3 (conv3x3_body16w.hip, X3): fp32-grade products from three bf16 MFMAs; s0 = hx (hi | xl planes), s1 = lo16;
 // conv-A reads hx, writes t16 (hi | lo planes); conv-B reads t16, updates (hx, lo16) in place.
 // Either way the last block's conv-B writes plain fp32 out_f32 for the (fp32) output convolution.
-static int body16(const dsen2_model* m, void* s0, void* s1, void* t16, float* out_f32, int n, int h, int w, hipStream_t stream) {
+// keep_step > 0 (training, precision 2): layer by layer, t_l at t16 + (l - 1) * keep_step floats, s0 copied to xkeep + l *
+// keep_step after every block but the last.
+static int body16(const dsen2_model* m, void* s0, void* s1, void* t16, float* out_f32, int n, int h, int w, hipStream_t stream,
+                  size_t keep_step = 0, void* xkeep = nullptr) {
   const float* P = m->dev_params;
   // One persistent launch over all 2d body convolutions when every CU gets whole patches (batch >= one patch per CU,
   // e.g. BASELINE configs[4]); hipErrorNotSupported = this batch keeps more CUs busy layer by layer.
-  if (may_chain(m)) {
+  if (keep_step == 0 && may_chain(m)) {
     const Layer& L1 = m->layers[1];
     const bool x3 = L1.plan.kernel == ConvKernel::Body16x3;
     ConvParams pc = make_params(nullptr, L1.weights(P), L1.bias(P), nullptr, nullptr, n, h, w, 0, 0.1f);
@@ -120,13 +123,17 @@ static int body16(const dsen2_model* m, void* s0, void* s1, void* t16, float* ou
   for (int l = 1; l <= m->num_layers; ++l) {
     const Layer& LA = m->layers[2 * l - 1];
     const Layer& LB = m->layers[2 * l];
-    HIP_TRY(launch(LA.plan, make_params(reinterpret_cast<const float*>(s0), LA.weights(P), LA.bias(P), nullptr,
-                                        reinterpret_cast<float*>(t16), n, h, w, 0, 0.f), kEpiRelu, m->tune, stream));
+    float* const t = reinterpret_cast<float*>(t16) + (size_t)(l - 1) * keep_step;
+    HIP_TRY(launch(LA.plan, make_params(reinterpret_cast<const float*>(s0), LA.weights(P), LA.bias(P), nullptr, t, n, h, w, 0, 0.f),
+                   kEpiRelu, m->tune, stream));
     const bool last = l == m->num_layers;
-    ConvParams pb = make_params(reinterpret_cast<const float*>(t16), LB.weights(P), LB.bias(P),
+    ConvParams pb = make_params(t, LB.weights(P), LB.bias(P),
                                 reinterpret_cast<const float*>(s0), last ? out_f32 : reinterpret_cast<float*>(s0), n, h, w, 0, 0.1f);
     pb.out2 = s1;
     HIP_TRY(launch(LB.plan, pb, last ? kEpiResidualF32 : kEpiResidual, m->tune, stream));
+    if (keep_step > 0 && !last)
+      HIP_TRY(hipMemcpyAsync(reinterpret_cast<float*>(xkeep) + (size_t)l * keep_step, s0, (size_t)n * h * w * m->feat * sizeof(float),
+                             hipMemcpyDeviceToDevice, stream));
   }
   return DSEN2_OK;
 }
@@ -167,7 +174,11 @@ int forward_launches(const dsen2_model* m, const float* x10, const float* x20, c
   if (int rc = first_layer(m, x10, x20, x60, n, h, w, B, x0_packed, stream)) return rc;
   if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
   if (m->precision == 2 && d > 0) {
-    if (int rc = body16(m, B.hx, B.lo16, B.t2, B.a, n, h, w, stream)) return rc;
+    if (keep_step > 0) {
+      HIP_TRY(launch_join3_f32(B.hx, B.lo16, B.x0f, n, h, w, m->feat, stream));
+      HIP_TRY(hipMemcpyAsync(B.xkeep, B.hx, (size_t)n * h * w * m->feat * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    if (int rc = body16(m, B.hx, B.lo16, B.t2, B.a, n, h, w, stream, keep_step, B.xkeep)) return rc;
   } else if (m->precision == 1 && d > 0) {
     if (int rc = body16(m, B.hi, B.lo, B.tbf, B.a, n, h, w, stream)) return rc;
   } else {
@@ -188,7 +199,8 @@ int forward_launches(const dsen2_model* m, const float* x10, const float* x20, c
   {
     const Layer& L = m->layers.back();           // DSen2Net.py:35,38,41
     const float* skip = m->c60 > 0 ? x60 : x20;  // utils/DSen2Net.py:38,41
-    ConvParams po = make_params(B.a + (size_t)d * keep_step, L.weights(P), L.bias(P), skip, out, n, h, w, m->cout, 0.f);
+    const float* x_d = B.a + (m->precision == 0 ? (size_t)d * keep_step : 0);     // 16-bit models: the last block's fp32 output
+    ConvParams po = make_params(x_d, L.weights(P), L.bias(P), skip, out, n, h, w, m->cout, 0.f);
 #ifdef DSEN2_DIAG
     po.diag = g_diag_stamps;
 #endif
@@ -317,7 +329,7 @@ static int conv3x3_body16(int precision, const void* dev_in, const float* host_k
   });
 }
 
-// the one argument check of dsen2_split_f32 / dsen2_join_f32 / dsen2_split3_f32 (a, b, c: their three tensors)
+// the one argument check of dsen2_split_f32 / dsen2_join_f32 / dsen2_split3_f32 / dsen2_join3_f32 (a, b, c: their three tensors)
 static int check_split_args(const void* a, const void* b, const void* c_, int n, int h, int w, int c) {
   if (!a || !b || !c_ || n < 0 || h <= 0 || w <= 0 || c <= 0 || c % 8 != 0 || c > 512)
     return fail(DSEN2_ERR_INVALID, "bad argument (c must be a multiple of 8, at most 512)");
@@ -461,6 +473,7 @@ int dsen2_model_load_weights(dsen2_model* m, const float* host_flat, size_t coun
     if (!m->dev_params) HIP_TRY(hipMalloc((void**)&m->dev_params, m->dev_param_floats * sizeof(float)));
     HIP_TRY(hipMemcpy(m->dev_params, staged.data(), m->dev_param_floats * sizeof(float), hipMemcpyHostToDevice));
     m->loaded = true;
+    if (m->trains_x3()) m->host_flat.assign(host_flat, host_flat + count);
     if (m->train) return train_state_after_load(m);     // a model being trained: its master weights follow
     return DSEN2_OK;
   });
@@ -544,6 +557,15 @@ int dsen2_split3_f32(const float* dev_in, void* dev_hx, void* dev_lo, int n, int
     if (int rc = check_split_args(dev_in, dev_hx, dev_lo, n, h, w, c)) return rc;
     if (n == 0) return DSEN2_OK;
     HIP_TRY(launch_split3_f32(dev_in, dev_hx, dev_lo, n, h, w, c, (hipStream_t)stream));
+    return DSEN2_OK;
+  });
+}
+
+int dsen2_join3_f32(const void* dev_hx, const void* dev_lo16, float* dev_out, int n, int h, int w, int c, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = check_split_args(dev_hx, dev_lo16, dev_out, n, h, w, c)) return rc;
+    if (n == 0) return DSEN2_OK;
+    HIP_TRY(launch_join3_f32(dev_hx, dev_lo16, dev_out, n, h, w, c, (hipStream_t)stream));
     return DSEN2_OK;
   });
 }

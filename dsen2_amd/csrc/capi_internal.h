@@ -37,8 +37,8 @@ int guarded(F&& body) noexcept {
   }
 }
 
-// Training state of an fp32 model (capi_train.hip), created by the first training call: the master weights as a device
-// keras-flat vector and the gather maps that rebuild every packed buffer from it.
+// Training state of an fp32 or bf16x3 model (capi_train.hip), created by the first training call: the master weights as a
+// device keras-flat fp32 vector and the gather maps that rebuild every packed buffer from it.
 struct TrainState;
 void train_state_destroy(TrainState* t);
 // after dsen2_model_load_weights replaced the packed weights: bring the master vector and the dgrad weights up to date
@@ -53,6 +53,10 @@ struct dsen2_model : dsen2::NetworkPlan {   // every layer's plan and place insi
   float* dev_params;
   bool loaded;
   dsen2::TrainState* train;   // NULL until the first training call
+  // precision 2 with residual blocks: the packed planes (hi + lo, 16 significant bits) do not hold the fp32 weights, so the
+  // keras-flat vector dsen2_model_load_weights was given is kept until a training state takes it over as its master copy
+  std::vector<float> host_flat;
+  bool trains_x3() const { return precision == 2 && num_layers > 0; }
 };
 
 namespace dsen2 {
@@ -131,13 +135,19 @@ struct ForwardWs {
   float* t = nullptr;                                 // precision 0: relu(convA(x))
   void *hi = nullptr, *lo = nullptr, *tbf = nullptr;  // precision 1: the stream as two 16-bit planes; relu(convA(x)) as bf16
   void *hx = nullptr, *lo16 = nullptr, *t2 = nullptr; // precision 2: the stream as hx (hi | xl planes) and lo16; t as (hi | lo) planes
+  void* xkeep = nullptr;                              // precision 2, keep_step > 0: copies of hx, x_l at xkeep + l * keep_step floats (l < d)
+  float* x0f = nullptr;                               // precision 2, keep_step > 0: x_0 as fp32 NHWC
   size_t bytes = 0;
 };
 // the inference workspace for n images of h x w: its size and, with base != NULL, its sub-buffers
 ForwardWs forward_ws(const dsen2_model* m, int n, int h, int w, char* base);
 // Every launch of one forward pass, in stream order; no argument checks.  keep_step = 0: the blocks run in place.  keep_step
-// > 0 (precision 0 only): block l reads x_{l-1} at B.a + (l - 1) * keep_step and writes t_l at B.t + (l - 1) * keep_step and
-// x_l at B.a + l * keep_step (floats).  x0_packed: the caller has already run launch_pack_inputs into B.x0.
+// > 0, precision 0: block l reads x_{l-1} at B.a + (l - 1) * keep_step and writes t_l at B.t + (l - 1) * keep_step and
+// x_l at B.a + l * keep_step (floats).  keep_step > 0, precision 2 (with residual blocks): always layer by layer, never the
+// chain kernel; conv-A writes t_l at B.t2 + (l - 1) * keep_step; conv-B runs in place on (B.hx, B.lo16), so hx (hi | xl, what
+// the backward reads) is copied to B.xkeep + l * keep_step after the first convolution (l = 0) and after every block but the
+// last, whose output is the fp32 tensor B.a; B.x0f receives x_0 as fp32.  Precision 1 keeps nothing.
+// x0_packed: the caller has already run launch_pack_inputs into B.x0.
 // ev (optional, 4 events): recorded on the stream before the first convolution, before the first and after the last
 // residual-block convolution, and after the output convolution.
 int forward_launches(const dsen2_model* m, const float* x10, const float* x20, const float* x60, float* out, int n, int h, int w,

@@ -200,6 +200,12 @@ hipError_t launch_recompose(const float* patches, int count, int C, int P, int b
 size_t wgrad_workspace_floats(int n, int h, int w, int ca, int cg);
 hipError_t launch_conv3x3_wgrad(const float* a, int ca, const float* g, int cg, int n, int h, int w, int ci_real, int co_real,
                                 float scale, float* dw, float* db, float* ws, size_t ws_floats, hipStream_t stream);
+// The same for F -> F (F = 128, 256) as bf16x3 on the bf16 matrix cores (conv3x3_wgrad16.hip): a and g are two-plane blocked
+// operand tensors [n][2][F/8][h][w][8] bf16 (value = plane 0 + plane 1), every product a0*g0 + a0*g1 + a1*g0 in fp32; dw HWIO
+// (3,3,F,F), db[F].  Same split-K with a fixed-order reduction.
+size_t wgrad16_workspace_floats(int n, int h, int w, int feat);
+hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, int n, int h, int w, int feat, float scale, float* dw,
+                                  float* db, float* ws, size_t ws_floats, hipStream_t stream);
 // keras mean_absolute_error over NCHW out / y ([n][c][h][w], c <= 16): loss2 = (mean |e|, mean e^2), gpad = dL/dout =
 // sign(e) / (n*c*h*w) as NHWC16 (channels >= c zero).  partial: mae_loss_partial_doubles(n*h*w) doubles of scratch.
 size_t mae_loss_partial_doubles(size_t pixels);
@@ -207,10 +213,23 @@ hipError_t launch_mae_loss_grad(const float* out, const float* y, float* gpad, d
                                 int w, hipStream_t stream);
 // v = m > 0 ? v : 0 (count % 4 == 0, 16-byte aligned)
 hipError_t launch_relu_mask(float* v, const float* m, size_t count, hipStream_t stream);
+// the precision-2 residual stream (hx: hi | xl planes, lo16) -> fp32 NHWC: the exact inverse of launch_split3_f32 (xl is not read)
+hipError_t launch_join3_f32(const void* hx, const void* lo, float* out_nhwc, int n, int h, int w, int c, hipStream_t stream);
+// du = t > 0 ? v : 0 written as a two-plane operand tensor [n][2][c/8][h][w][8] (hi = RNE bf16 of the value, lo = RNE bf16 of
+// value - hi): v fp32 NHWC, t a two-plane tensor (conv-A's output of a precision-2 model)
+hipError_t launch_mask_split3(const float* v_nhwc, const void* t_planes, void* du_planes, int n, int h, int w, int c, hipStream_t stream);
 hipError_t launch_nadam(float* p, const float* g, float* m, float* v, size_t count, float lr, float b1, float b2, float eps,
                         float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, hipStream_t stream);
 // dst[i] = map[i] ? src[map[i] - 1] : 0   /   flat[map[i] - 1] = packed[i] where map[i] != 0
 hipError_t launch_gather(float* dst, const float* src, const int* map, size_t n, hipStream_t stream);
 hipError_t launch_scatter(float* flat, const float* packed, const int* map, size_t n, hipStream_t stream);
+// The repack of a precision-2 model, whose packed buffers mix bf16 (hi, lo) planes and fp32 words: one map entry per 16-bit
+// half of the `words` 32-bit words of a layer's buffer, 0 = zero, else 4 * (1 + index into the layer's keras-flat values) +
+// kind (kGatherHi = RNE bf16 of the value, kGatherLo = RNE bf16 of (value - hi), kGatherF32Low / High = the halves of the fp32
+// bit pattern) — the host packers' arithmetic (f32_to_bf16_rne).  `layers` layers with the same map: dst_stride words /
+// src_stride floats apart.
+enum : int { kGatherHi = 0, kGatherLo = 1, kGatherF32Low = 2, kGatherF32High = 3 };
+hipError_t launch_gather16(void* dst, const float* src, const int* map, size_t words, int layers, size_t dst_stride, size_t src_stride,
+                           hipStream_t stream);
 
 }  // namespace dsen2

@@ -124,6 +124,90 @@ __global__ __launch_bounds__(256) void scatter_kernel(float* __restrict__ flat, 
   if (k > 0) flat[k - 1] = packed[i];
 }
 
+// ---- precision 2 (bf16x3) ----
+// f32_to_bf16_rne (dsen2_internal.h) on the device: the host packers' rounding, the same integer arithmetic
+__device__ __forceinline__ unsigned bf16_rne(float f) {
+  unsigned u = __builtin_bit_cast(unsigned, f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+__device__ __forceinline__ float bf16_value(unsigned h16) { return __builtin_bit_cast(float, h16 << 16); }
+// element e (0..7) of a 16-byte pixel of a blocked 16-bit tensor
+__device__ __forceinline__ unsigned half_of(const uint4& v, int e) {
+  const unsigned d = e < 2 ? v.x : e < 4 ? v.y : e < 6 ? v.z : v.w;
+  return (e & 1) ? d >> 16 : d & 0xffffu;
+}
+__device__ __forceinline__ uint4 pack_halves(const unsigned* h) {
+  return make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+}
+
+// One thread per (pixel, 8-channel block), the block fastest: the fp32 side is read / written in contiguous 32-byte pieces.
+// hx [n][2][nblk][img_pix] pixels of 8 x 16 bit (plane 0 = hi, the ties-away rounding of the bit pattern), lo [n][nblk][img_pix]:
+// value bits = ((hi - (lo >> 15)) << 16) | lo, the inverse of split3_kernel (conv3x3_body16w.hip)
+__global__ __launch_bounds__(256) void join3_kernel(const uint4* __restrict__ hx, const uint4* __restrict__ lo, float* __restrict__ out,
+                                                  size_t total, int img_pix, int nblk) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int blk = (int)(i % nblk);
+  const size_t pix = i / nblk, img = pix / img_pix, px = pix % img_pix;
+  const uint4 h = hx[((img * 2) * nblk + blk) * img_pix + px];
+  const uint4 l = lo[(img * nblk + blk) * img_pix + px];
+  float v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const unsigned le = half_of(l, e);
+    const unsigned top = (half_of(h, e) - (le >> 15)) & 0xffffu;
+    v[e] = __builtin_bit_cast(float, (top << 16) | le);
+  }
+  f32x4* dst = reinterpret_cast<f32x4*>(out + (pix * nblk + blk) * 8);
+  dst[0] = f32x4{v[0], v[1], v[2], v[3]};
+  dst[1] = f32x4{v[4], v[5], v[6], v[7]};
+}
+
+// du = t > 0 ? v : 0 as (hi | lo) planes; v fp32 NHWC, t and du [n][2][nblk][img_pix] pixels of 8 bf16
+__global__ __launch_bounds__(256) void mask_split3_kernel(const float* __restrict__ v_nhwc, const uint4* __restrict__ t, uint4* __restrict__ du,
+                                                        size_t total, int img_pix, int nblk) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int blk = (int)(i % nblk);
+  const size_t pix = i / nblk, img = pix / img_pix, px = pix % img_pix;
+  const size_t hi_at = ((img * 2) * nblk + blk) * img_pix + px, lo_at = hi_at + (size_t)nblk * img_pix;
+  const uint4 th = t[hi_at], tl = t[lo_at];
+  const f32x4* src = reinterpret_cast<const f32x4*>(v_nhwc + (pix * nblk + blk) * 8);
+  const f32x4 a = src[0], b = src[1];
+  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  unsigned h[8], l[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float tv = bf16_value(half_of(th, e)) + bf16_value(half_of(tl, e));
+    const float x = tv > 0.f ? v[e] : 0.f;
+    h[e] = bf16_rne(x);
+    l[e] = bf16_rne(x - bf16_value(h[e]));
+  }
+  du[hi_at] = pack_halves(h);
+  du[lo_at] = pack_halves(l);
+}
+
+// one 32-bit word of a packed precision-2 buffer from the keras-flat values (launch_gather16)
+__device__ __forceinline__ unsigned gather16_half(const float* __restrict__ src, int entry) {
+  if (entry == 0) return 0u;
+  const float w = src[(entry >> 2) - 1];
+  const int kind = entry & 3;
+  const unsigned hi = bf16_rne(w);
+  if (kind == kGatherHi) return hi;
+  if (kind == kGatherLo) return bf16_rne(w - bf16_value(hi));
+  const unsigned u = __builtin_bit_cast(unsigned, w);
+  return kind == kGatherF32Low ? u & 0xffffu : u >> 16;
+}
+__global__ __launch_bounds__(256) void gather16_kernel(unsigned* __restrict__ dst, const float* __restrict__ src, const int* __restrict__ map,
+                                                     size_t words, size_t dst_stride, size_t src_stride) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= words) return;
+  const float* s = src + (size_t)blockIdx.y * src_stride;
+  dst[(size_t)blockIdx.y * dst_stride + i] = gather16_half(s, map[2 * i]) | (gather16_half(s, map[2 * i + 1]) << 16);
+}
+
 unsigned blocks_for(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -153,6 +237,31 @@ hipError_t launch_relu_mask(float* v, const float* m, size_t count, hipStream_t 
   if (count % 4 != 0) return hipErrorInvalidValue;
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks_for(count / 4, 256)), dim3(256), 0, stream, v, m, count / 4);
+  return hipGetLastError();
+}
+
+hipError_t launch_join3_f32(const void* hx, const void* lo, float* out_nhwc, int n, int h, int w, int c, hipStream_t stream) {
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 8 != 0 || c > 512) return hipErrorInvalidValue;
+  const size_t total = (size_t)n * h * w * (c / 8);
+  hipLaunchKernelGGL(join3_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, stream, reinterpret_cast<const uint4*>(hx),
+                     reinterpret_cast<const uint4*>(lo), out_nhwc, total, h * w, c / 8);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_split3(const float* v_nhwc, const void* t_planes, void* du_planes, int n, int h, int w, int c, hipStream_t stream) {
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 8 != 0 || c > 512) return hipErrorInvalidValue;
+  const size_t total = (size_t)n * h * w * (c / 8);
+  hipLaunchKernelGGL(mask_split3_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, stream, v_nhwc,
+                     reinterpret_cast<const uint4*>(t_planes), reinterpret_cast<uint4*>(du_planes), total, h * w, c / 8);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather16(void* dst, const float* src, const int* map, size_t words, int layers, size_t dst_stride, size_t src_stride,
+                           hipStream_t stream) {
+  if (words == 0 || layers <= 0) return hipSuccess;
+  if (layers > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather16_kernel, dim3(blocks_for(words, 256), (unsigned)layers), dim3(256), 0, stream,
+                     reinterpret_cast<unsigned*>(dst), src, map, words, dst_stride, src_stride);
   return hipGetLastError();
 }
 

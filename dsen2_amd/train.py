@@ -8,7 +8,10 @@ cooldown 20, min_lr 1e-5), best-only checkpointing on val_loss, shuffled epochs.
                                     in place of a missing .hdf5 of the same name)
   <out>/<model_nr>_lr_<lr>.txt      one line per epoch: loss, val_loss, lr
 
-fp32 models on one GPU only.  Data: <path>/train/*SAFE/{data10,data20,data20_gt}.npy (train60/ and data60, data60_gt with
+One GPU only.  --precision fp32 (default) trains in fp32; --precision bf16x3 runs the forward and the residual blocks' backward
+on the bf16 matrix cores with fp32-grade products (three bf16 MFMAs each); the master weights, the optimizer and the checkpoint
+stay fp32 either way, so a checkpoint loads into a model of any precision.
+Data: <path>/train/*SAFE/{data10,data20,data20_gt}.npy (train60/ and data60, data60_gt with
 --run_60) and val_index.npy, as `python -m dsen2_amd.create_patches` and `python -m dsen2_amd.create_random` write them (the
 counterparts of training/create_patches.py and create_random.py, whose files it reads just the same).
 
@@ -45,6 +48,8 @@ def parse_args(argv=None):
     p.add_argument('--batch_size', type=int, default=None, help='Batch size (default 128, 8 with --deep).')
     p.add_argument('--out', default=None, help='Output directory (default <path>/network_data/).')
     p.add_argument('--seed', type=int, default=None, help='Seed of the epoch shuffles.')
+    p.add_argument('--precision', choices=('fp32', 'bf16x3'), default='fp32',
+                   help='Arithmetic of the residual blocks while training (default fp32); checkpoints are fp32 either way.')
     return p.parse_args(argv)
 
 
@@ -92,15 +97,16 @@ def main(argv=None):
     path = args.path if args.path.endswith('/') else args.path + '/'
     if args.predict_file:
         bands = ((4, None, None), (6, None, None), (2, None, None)) if args.run_60 else ((4, None, None), (6, None, None))
-        return predict(s2model(bands, num_layers=32 if args.deep else 6, feature_size=256 if args.deep else 128), args, path)
+        return predict(s2model(bands, num_layers=32 if args.deep else 6, feature_size=256 if args.deep else 128,
+                               precision=args.precision), args, path)
     out = args.out if args.out is not None else path + 'network_data/'
     os.makedirs(out, exist_ok=True)
     bands = ((4, None, None), (6, None, None), (2, None, None)) if args.run_60 else ((4, None, None), (6, None, None))
     if args.deep:
-        model = s2model(bands, num_layers=32, feature_size=256)
+        model = s2model(bands, num_layers=32, feature_size=256, precision=args.precision)
         batch_size = 8
     else:
-        model = s2model(bands, num_layers=6, feature_size=128)
+        model = s2model(bands, num_layers=6, feature_size=128, precision=args.precision)
         batch_size = 128
     if args.batch_size:
         batch_size = args.batch_size

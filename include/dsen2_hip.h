@@ -198,10 +198,22 @@ int dsen2_model_time_body_conv(dsen2_model *m, int layer, const float *dev_in, c
                                float *dev_out, int n, int h, int w, int iters, void *stream,
                                float *ms_per_launch);
 
-/* ---- training (fp32 models only) ------------------------------------------------------------
+/* ---- training (fp32 and bf16x3 models) --------------------------------------------------------
  * The counterpart of training/supres_train.py's model.fit: MAE loss (keras mean_absolute_error, MSE as a metric), the
- * gradients of every parameter, keras-2 Nadam.  Every training entry returns DSEN2_ERR_INVALID ("training needs an fp32
- * model") for a precision-1 or -2 handle.  No float atomics: the same inputs give the same bits, run to run.
+ * gradients of every parameter, keras-2 Nadam.  Precision 0 and 2 handles train; every training entry returns
+ * DSEN2_ERR_INVALID ("training needs an fp32 model or a bf16x3 one") for a precision-1 handle.  No float atomics: the same
+ * inputs give the same bits, run to run.
+ * A precision-2 model trains in its own arithmetic: the forward on the bf16x3 per-layer kernels (never the chain kernel),
+ * the residual blocks' input gradients on the same kernels with flipped, transposed weights, their weight gradients on
+ * dsen2_conv3x3_wgrad_bf16x3's kernel; the first and the output convolution's gradients stay on the fp32 kernels.  The
+ * master weights, the gradient, the optimizer state and dsen2_model_get_weights' vector are fp32 keras-flat in every
+ * precision; after each dsen2_model_set_weights_device the packed (wh, wl) planes are the host packers' bits.
+ * Host memory: the packed planes of a precision-2 model with residual blocks hold 16 significant bits per weight, so
+ * dsen2_model_load_weights keeps a host copy of the fp32 vector it was given (4 * num_params bytes, 151 MB for VDSen2) for
+ * dsen2_model_get_weights and the first training call, which moves it to the device and frees it.  An inference-only
+ * precision-2 model carries that copy until dsen2_model_destroy.
+ * A precision-2 model without residual blocks (num_layers 0) is fp32 in every layer (dsen2_model_create) and trains exactly
+ * as the precision-0 model of the same shape does.
  *
  * dsen2_model_train_workspace_bytes: scratch dsen2_model_gradients needs for n patches of h x w (the saved activations
  *   x0 .. x_d and t_1 .. t_d, two gradient tensors, the weight-gradient partials; ~1 GB for DSen2 at 128 x 32 x 32).
@@ -233,6 +245,15 @@ int dsen2_nadam_step(float *p, const float *g, float *m, float *v, size_t count,
                      float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, void *stream);
 int dsen2_conv3x3_wgrad(const float *dev_a, const float *dev_g, float *dev_dw, float *dev_db, int n, int h, int w, int ca,
                         int cg, int ci, int co, float scale, void *stream);
+/* dsen2_conv3x3_wgrad_bf16x3: the weight gradient of a feat -> feat convolution (feat = 128, 256) as bf16x3 on the bf16 matrix
+ *   cores, alone (kernel-level tests).  dev_a_planes / dev_g_planes are two-plane operand tensors [n][2][feat/8][h][w][8] bf16
+ *   (value = plane 0 + plane 1: dsen2_split3_f32's dev_hx, epilogue 0's dev_out); every product is a0*g0 + a0*g1 + a1*g0 with
+ *   fp32 accumulators.  dev_dw (3,3,feat,feat) HWIO, dev_db [feat], both times `scale`.  Allocates its scratch and synchronises.
+ * dsen2_join3_f32: the exact inverse of dsen2_split3_f32: (dev_hx plane 0, dev_lo16) -> fp32 NHWC [n,h,w,c], bit for bit
+ *   (plane 1, xl, is not read). */
+int dsen2_conv3x3_wgrad_bf16x3(const void *dev_a_planes, const void *dev_g_planes, float *dev_dw, float *dev_db, int n, int h,
+                               int w, int feat, float scale, void *stream);
+int dsen2_join3_f32(const void *dev_hx, const void *dev_lo16, float *dev_out_nhwc, int n, int h, int w, int c, void *stream);
 
 /* ---- tiling / up-sampling / recomposition (utils/patches.py) --------------------------------
  * dsen2_upsample_mirror_bilinear  <->  interp_patches            utils/patches.py:11-16

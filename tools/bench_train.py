@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fine-tuning speed: one JSON line per configuration.
 
-    python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N]
+    python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N] [--precision fp32|bf16x3]
 
   step_ms            one training step on device-resident data: dsen2_model_gradients + dsen2_nadam_step + the device repack
   train_on_batch_ms  S2Model.train_on_batch from host arrays (adds the H2D copies and the loss read-back)
@@ -9,6 +9,8 @@
   patches_per_s      batch / step_ms
   wgrad_tflops       the weight-gradient kernel of one body layer (conv3x3_wgrad.hip) alone, timed with HIP events over
                      `iters` launches through dsen2_conv3x3_wgrad's kernels on device buffers (2 * 9 * F^2 * n*h*w FLOP each)
+--precision bf16x3 trains a bf16x3 model: the weight-gradient kernel timed is then conv3x3_wgrad16.hip (dsen2_conv3x3_wgrad_bf16x3
+on two-plane operand tensors), counted at three MFMAs per product (3 * 2 * 9 * F^2 * n*h*w FLOP) against the bf16 MFMA peak.
 DSen2 runs at batch 128, VDSen2 at batch 8, both on 32 x 32 patches (training/supres_train.py's batch sizes).
 """
 import argparse
@@ -21,9 +23,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dsen2_amd import _lib, training, weights  # noqa: E402
-from dsen2_amd.DSen2Net import _ptr, _stream_ptr, s2model  # noqa: E402
+from dsen2_amd.DSen2Net import _ptr, _stream_ptr, s2model, split3_f32  # noqa: E402
 
 PEAK_TF = 157.3   # fp32 MFMA peak of the MI355X (MI355X_MICROARCH.md)
+PEAK_TF_BF16 = 2500.0   # dense bf16 MFMA peak
 CONFIGS = {'dsen2': dict(d=6, F=128, batch=128), 'vdsen2': dict(d=32, F=256, batch=8)}
 
 
@@ -40,11 +43,11 @@ def timed(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters
 
 
-def run(name, iters):
+def run(name, iters, precision='fp32'):
     c = CONFIGS[name]
     d, F, n, h, w = c['d'], c['F'], c['batch'], 32, 32
     dev = torch.device('cuda', 0)
-    m = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev)
+    m = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev, precision=precision)
     m.set_weights_flat(weights.random_he_uniform(10, 6, d, F, seed=1, bias_scale=0.05))
     m.compile(training.Nadam(lr=1e-4))
     rng = np.random.default_rng(0)
@@ -67,17 +70,25 @@ def run(name, iters):
     dw = torch.empty(9 * F * F, device=dev)
     db = torch.empty(F, device=dev)
 
+    x3 = precision == 'bf16x3'
+    if x3:
+        a, g = split3_f32(a)[0], split3_f32(g)[0]
+
     def wgrad():
-        _lib.call('dsen2_conv3x3_wgrad', _ptr(a), _ptr(g), _ptr(dw), _ptr(db), n, h, w, F, F, F, F, 1.0, _stream_ptr(dev))
+        if x3:
+            _lib.call('dsen2_conv3x3_wgrad_bf16x3', _ptr(a), _ptr(g), _ptr(dw), _ptr(db), n, h, w, F, 1.0, _stream_ptr(dev))
+        else:
+            _lib.call('dsen2_conv3x3_wgrad', _ptr(a), _ptr(g), _ptr(dw), _ptr(db), n, h, w, F, F, F, F, 1.0, _stream_ptr(dev))
     # dsen2_conv3x3_wgrad allocates its scratch and synchronises on every call: its kernels' share is what a HIP-event pair
     # around the call measures minus that overhead, so the kernels are timed from a rocprofv3 kernel trace instead when one
     # is given (profiles/); here: the call's wall time, an upper bound of the kernel time
     wg_ms = timed(wgrad, iters, warm=2)
-    flop = 2.0 * 9 * F * F * n * h * w
-    res = dict(config=name, batch=n, h=h, w=w, num_layers=d, feature_size=F, step_ms=round(step_ms, 4),
+    flop = (3.0 if x3 else 1.0) * 2.0 * 9 * F * F * n * h * w
+    peak = PEAK_TF_BF16 if x3 else PEAK_TF
+    res = dict(config=name, precision=precision, batch=n, h=h, w=w, num_layers=d, feature_size=F, step_ms=round(step_ms, 4),
                train_on_batch_ms=round(tob_ms, 4), forward_ms=round(fwd_ms, 4), step_over_forward=round(step_ms / fwd_ms, 3),
                patches_per_s=round(n / step_ms * 1e3, 1), wgrad_call_ms=round(wg_ms, 4),
-               wgrad_tflops_lower_bound=round(flop / wg_ms / 1e9, 2), wgrad_fraction_of_peak_lower_bound=round(flop / wg_ms / 1e9 / PEAK_TF, 3))
+               wgrad_tflops_lower_bound=round(flop / wg_ms / 1e9, 2), wgrad_fraction_of_peak_lower_bound=round(flop / wg_ms / 1e9 / peak, 4))
     print(json.dumps(res), flush=True)
 
 
@@ -85,9 +96,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default='both', choices=['dsen2', 'vdsen2', 'both'])
     ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3'])
     args = ap.parse_args()
     for name in (['dsen2', 'vdsen2'] if args.config == 'both' else [args.config]):
-        run(name, args.iters)
+        run(name, args.iters, args.precision)
 
 
 if __name__ == '__main__':
