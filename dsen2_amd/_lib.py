@@ -20,6 +20,7 @@ c_int_p = ctypes.POINTER(ctypes.c_int)
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
 c_size_t = ctypes.c_size_t
+c_double = ctypes.c_double
 
 # name -> (restype, argtypes); every symbol include/dsen2_hip.h declares
 SIGNATURES = {
@@ -89,6 +90,12 @@ SIGNATURES = {
                                         c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'dsen2_imresize_sam_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                         c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_ssim_map': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_double, c_double,
+                               c_void_p, c_void_p]),
+    'dsen2_ssim_sums': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_double, c_double,
+                                c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_imresize_ssim_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                         ctypes.POINTER(c_double), c_int, c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 _lib = None

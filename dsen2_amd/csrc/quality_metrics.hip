@@ -33,36 +33,13 @@
 
 #pragma clang fp contract(off)
 
-#include "resample.h"
+#include "quality_common.h"       // the loaders, the finish kernel and the argument checks shared with ssim.hip
 
 namespace dsen2 {
 
-constexpr int kQThreads = 256;
-constexpr int kQWaves = kQThreads / 64;
 constexpr int kUiqTileH = 16, kUiqTileW = 32;      // windows per tile (tests/test_gpu_quality_metrics.py reads these two lines)
 constexpr int kUiqMinBlock = 2, kUiqMaxBlock = 16;
-constexpr int kQMaxBands = 64;
-constexpr int kQMaxBlocks = 4096;                  // partial pairs per band: the workspace is kQMaxBlocks * C * 2 doubles
 constexpr double kDegrees = 180.0 / 3.14159265358979323846;
-
-template <typename T>
-struct DirectImage {        // x[r][col][band] of an HWC image
-  const T* p;
-  int W, C;
-  __device__ __forceinline__ double operator()(int r, int col, int band) const { return as_double(p[((size_t)r * W + col) * C + band]); }
-};
-
-template <typename T>
-struct ResampledImage {     // the same element of the image that dsen2_imresize_axis would have written from `mid` ([A][N][B] view)
-  const T* mid;
-  const double* w;
-  const int* idx;
-  int P, M, N, B, C, axis;
-  __device__ __forceinline__ double operator()(int r, int col, int band) const {
-    if (axis == 0) return resample_one<T>(mid + (size_t)col * C + band, w, idx, P, M, N, B, (unsigned)r);
-    return resample_one<T>(mid + (size_t)r * N * B + band, w, idx, P, M, N, B, (unsigned)col);
-  }
-};
 
 // x, y: [H][W][C] through their loaders.  MAP: map[OH][OW][C] is written.  else partials[block][c] = { sum q, windows } of the block's tiles.
 template <class LX, class LY, bool MAP>
@@ -203,42 +180,11 @@ __global__ __launch_bounds__(kQThreads) void sam_kernel(LX x, LY y, int H, int W
   }
 }
 
-// one block: out[c][0 .. 1] = the sums over all blocks of partials[block][c][0 .. 1], in a fixed order
-__global__ __launch_bounds__(kQThreads) void quality_finish_kernel(const double* __restrict__ partials, int blocks, int C,
-                                                                   double* __restrict__ out) {
-  __shared__ double s[2][kQThreads];
-  const int tid = threadIdx.x;
-  for (int c = 0; c < C; ++c) {
-    double a = 0.0, b = 0.0;
-    for (int blk = tid; blk < blocks; blk += kQThreads) {
-      a = __dadd_rn(a, partials[((size_t)blk * C + c) * 2 + 0]);
-      b = __dadd_rn(b, partials[((size_t)blk * C + c) * 2 + 1]);
-    }
-    s[0][tid] = a;
-    s[1][tid] = b;
-    __syncthreads();
-    for (int half = kQThreads / 2; half > 0; half >>= 1) {
-      if (tid < half) {
-        s[0][tid] = __dadd_rn(s[0][tid], s[0][tid + half]);
-        s[1][tid] = __dadd_rn(s[1][tid], s[1][tid + half]);
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      out[c * 2 + 0] = s[0][0];
-      out[c * 2 + 1] = s[1][0];
-    }
-    __syncthreads();
-  }
-}
-
 struct QualityCall {
   int H, W, C, block;       // the shape of the two images the metric sees; block: UIQ only
   double *map, *partials, *out;
   hipStream_t stream;
 };
-
-static size_t quality_work_bytes(int C) { return (size_t)kQMaxBlocks * C * 2 * sizeof(double); }
 
 template <class LX, class LY, bool MAP>
 static hipError_t launch_uiq(const LX& x, const LY& y, const QualityCall& q) {
@@ -294,34 +240,10 @@ static hipError_t map_with_y(const T* x, const void* y, int y_dtype, const Quali
   return launch_uiq<DirectImage<T>, DirectImage<float>, true>(lx, DirectImage<float>{static_cast<const float*>(y), q.W, q.C}, q);
 }
 
-static bool float_dtype(int d) { return d == DSEN2_DTYPE_F32 || d == DSEN2_DTYPE_F64; }
-
-// the two images of a metric: pointers, dtypes, bands, and the 2^31-element limit of one launch
-static int check_images(const char* who, const void* x, int x_dtype, const void* y, int y_dtype, int H, int W, int C) {
-  if (!x || !y || H <= 0 || W <= 0) return fail(DSEN2_ERR_INVALID, "%s: bad argument", who);
-  if (C < 1 || C > kQMaxBands) return fail(DSEN2_ERR_INVALID, "%s: %d bands outside 1..%d", who, C, kQMaxBands);
-  if (!float_dtype(x_dtype) || !float_dtype(y_dtype))
-    return fail(DSEN2_ERR_INVALID, "%s: dtypes %d and %d: not supported (float32 or float64 each)", who, x_dtype, y_dtype);
-  if ((size_t)H * W * C >= ((size_t)1 << 31)) return fail(DSEN2_ERR_INVALID, "%s: image too large for one launch (2^31 elements)", who);
-  return DSEN2_OK;
-}
-
 static int check_block(const char* who, int H, int W, int block) {
   if (block < kUiqMinBlock || block > kUiqMaxBlock)
     return fail(DSEN2_ERR_INVALID, "%s: block size %d outside %d..%d", who, block, kUiqMinBlock, kUiqMaxBlock);
   if (H < block || W < block) return fail(DSEN2_ERR_INVALID, "%s: an image of %d x %d is smaller than the %d x %d block", who, H, W, block, block);
-  return DSEN2_OK;
-}
-
-static int check_work(const char* who, int C, const void* work, size_t work_bytes, const void* out) {
-  if (!work || !out) return fail(DSEN2_ERR_INVALID, "%s: bad argument", who);
-  if (work_bytes < quality_work_bytes(C))
-    return fail(DSEN2_ERR_WORKSPACE, "%s: workspace of %zu bytes, dsen2_quality_workspace_bytes asks for %zu", who, work_bytes, quality_work_bytes(C));
-  return DSEN2_OK;
-}
-
-static int launched(const char* who, hipError_t e) {
-  if (e != hipSuccess) return fail(DSEN2_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
   return DSEN2_OK;
 }
 
@@ -341,16 +263,8 @@ static int direct_metric(const char* who, Metric m, const void* x, int x_dtype, 
 static int resampled_metric(const char* who, Metric m, const void* in, int dtype, int H, int W, int C, int axis, int out_len, const double* w,
                             const int* idx, int taps, const void* gt, int gt_dtype, int block, void* work, size_t work_bytes, double* out,
                             void* stream) {
-  if (!in || !w || !idx || !gt || H <= 0 || W <= 0 || out_len <= 0) return fail(DSEN2_ERR_INVALID, "%s: bad argument", who);
-  if (C < 1 || C > kQMaxBands) return fail(DSEN2_ERR_INVALID, "%s: %d bands outside 1..%d", who, C, kQMaxBands);
-  if (dtype != DSEN2_DTYPE_U16 && !float_dtype(dtype))
-    return fail(DSEN2_ERR_INVALID, "%s: dtype %d is not supported (uint16, float32 or float64)", who, dtype);
-  if (!float_dtype(gt_dtype)) return fail(DSEN2_ERR_INVALID, "%s: dtype %d is not supported for the ground truth (float32 or float64)", who, gt_dtype);
-  if (axis != 0 && axis != 1) return fail(DSEN2_ERR_INVALID, "%s: axis %d (0 = rows, 1 = columns of an HWC image)", who, axis);
-  if (taps < 1 || taps > kResizeMaxTaps) return fail(DSEN2_ERR_INVALID, "%s: %d taps outside 1..%d", who, taps, kResizeMaxTaps);
+  if (int rc = check_resampled(who, in, dtype, H, W, C, axis, out_len, w, idx, taps, gt, gt_dtype)) return rc;
   const int OH = axis == 0 ? out_len : H, OW = axis == 0 ? W : out_len;
-  if ((size_t)H * W * C >= ((size_t)1 << 31) || (size_t)OH * OW * C >= ((size_t)1 << 31))
-    return fail(DSEN2_ERR_INVALID, "%s: image too large for one launch (2^31 elements)", who);
   if (m != Metric::Sam)
     if (int rc = check_block(who, OH, OW, block)) return rc;
   if (int rc = check_work(who, C, work, work_bytes, out)) return rc;

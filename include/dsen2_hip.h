@@ -365,6 +365,35 @@ int dsen2_imresize_sam_sums(const void *dev_in, int dtype, int H, int W, int C, 
                             const int *dev_indices, int taps, const void *dev_gt, int gt_dtype, void *dev_work, size_t work_bytes,
                             double *dev_out, void *stream);
 
+/* ---- evaluation: the structural similarity index, SSIM (Wang, Bovik, Sheikh & Simoncelli 2004, ssim_index.m without its
+ * automatic down-sampling; csrc/ssim.hip) ----
+ * Per band, over valid windows only, with a separable window of `win` normalised weights host_window[0 .. win-1] (HOST memory,
+ * read during the call; win odd, 3..15; the Gaussian of the paper is win 11, sigma 1.5) and the biased covariance.  All arithmetic
+ * is float64, every product and every sum rounded on its own, in this order.  The same filter for each of the five
+ * fields f = x, y, x*x, y*y, x*y, the products formed first:  row pass r[y][c] = w[0]*f[y][c], then r = r + w[k]*f[y][c+k] for
+ * k = 1 .. win-1 in order; column pass the same sequential sum over r[y+k][c].  With mx, my, exx, eyy, exy the filtered fields:
+ *   m11 = mx*mx  m22 = my*my  m12 = mx*my  s1 = exx - m11  s2 = eyy - m22  s12 = exy - m12
+ *   num = (2*m12 + c1)*(2*s12 + c2)   den = ((m11 + m22) + c1)*((s1 + s2) + c2)   q = num/den (an IEEE division)
+ * c1 = (K1 L)^2 and c2 = (K2 L)^2 are the caller's, L being the data range.  The images are HWC [H,W,C], float32 or float64 each
+ * (dev_in of the fused form: uint16 as well), 1 <= C <= 64, fewer than 2^31 elements.
+ * dsen2_ssim_map: dev_map_f64 [H-win+1, W-win+1, C].  A pure function of its inputs: the same bits on every run.
+ * dsen2_ssim_sums: dev_out[2c .. 2c+1] = { sum of that map over band c, number of windows } without ever storing the map; the
+ *   SSIM of band c is their quotient, the SSIM of the image the mean over the bands.
+ * dsen2_imresize_ssim_sums: the same sums for x = the resampling pass dsen2_imresize_axis(dev_in, ...) would write, against
+ *   dev_gt (which has the OUTPUT's shape), computed tile by tile and never stored.  The same bits as dsen2_imresize_axis followed
+ *   by dsen2_ssim_sums.
+ * The order of every addition depends on the shapes only (no float atomics).  dev_work: dsen2_quality_workspace_bytes(C) bytes
+ * of device scratch.  DSEN2_ERR_INVALID with nothing launched: win even or outside 3..15, H or W (of the image the metric sees)
+ * below win, C outside 1..64, any other dtype, a null pointer, 2^31 elements or more, c1 or c2 not finite or not > 0 (which keeps
+ * den > 0), a window entry that is not finite; DSEN2_ERR_WORKSPACE: a short workspace. */
+int dsen2_ssim_map(const void *dev_x, int x_dtype, const void *dev_y, int y_dtype, int H, int W, int C, const double *host_window,
+                   int win, double c1, double c2, double *dev_map_f64, void *stream);
+int dsen2_ssim_sums(const void *dev_x, int x_dtype, const void *dev_y, int y_dtype, int H, int W, int C, const double *host_window,
+                    int win, double c1, double c2, void *dev_work, size_t work_bytes, double *dev_out, void *stream);
+int dsen2_imresize_ssim_sums(const void *dev_in, int dtype, int H, int W, int C, int axis, int out_len, const double *dev_weights,
+                             const int *dev_indices, int taps, const void *dev_gt, int gt_dtype, const double *host_window, int win,
+                             double c1, double c2, void *dev_work, size_t work_bytes, double *dev_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

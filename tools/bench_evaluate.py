@@ -4,7 +4,9 @@ fused form (second pass + reduction, nothing stored) against resize-then-reduce,
   5490^2 x 6 float32 enlarged by 2  (the 20 m bands)       1830^2 x 2 float32 enlarged by 6  (the 60 m bands)
 and the paper's two further metrics at the enlarged sizes (csrc/quality_metrics.hip): the UIQ map, the fused UIQ sums, SAM, and
 their fused bicubic forms (second pass inside the metric's loader, nothing stored), with the numpy restatement of the UIQ
-(tests/quality_restatement.py) timed on one 2000^2 band of the host for context.
+(tests/quality_restatement.py) timed on one 2000^2 band of the host for context; and the SSIM (csrc/ssim.hip, Gaussian window of 11,
+L = 10000) at the same sizes: the map, the fused sums, the fused bicubic sums, beside uiq_sums at block 11 on the same images, the
+kernel with the same halo and the same staging.
     python tools/bench_evaluate.py [--out FILE.jsonl] [--iters N] [--numpy_band 2000]
 
 `algorithmic bytes` of a kernel = what it must read once + what it must write once (the tap tables, a few hundred KB that stay in
@@ -109,6 +111,27 @@ def main():
              'uiq_store_then_measure_ms': round(ms_a + ms_b + ms_u, 4), 'uiq_fused_ms': round(ms_a + ms_fu, 4),
              'sam_store_then_measure_ms': round(ms_a + ms_b + ms_s, 4), 'sam_fused_ms': round(ms_a + ms_fs, 4),
              'stored_GB_avoided': round(on * on * c * 8 / 1e9, 3), 'identical_bits': same}
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+        # SSIM, window 11: the same algorithmic bytes; uiq_sums at block 11 has the same halo tile and the same staging
+        win = (on - 10) * (on - 10) * c
+        ms = timeit(lambda: metrics.ssim_map_device(full, gt, 1e4), args.iters)
+        emit('ssim_map float64 vs float32 %s' % size, ms, on * on * c * 12, stored_MB=round(win * 8 / 1e6, 1), Gwindows_per_s=round(win / ms / 1e6, 2))
+        ms_q = timeit(lambda: metrics.ssim_sums_device(full, gt, 1e4), args.iters)
+        emit('ssim_sums float64 vs float32 %s' % size, ms_q, on * on * c * 12, Gwindows_per_s=round(win / ms_q / 1e6, 2))
+        ms_u11 = timeit(lambda: metrics.uiq_sums_device(full, gt, 11), args.iters)
+        emit('uiq_sums block 11 float64 vs float32 %s' % size, ms_u11, on * on * c * 12, Gwindows_per_s=round(win / ms_u11 / 1e6, 2))
+        x32 = full.to(torch.float32)
+        ms = timeit(lambda: metrics.ssim_sums_device(x32, gt, 1e4), args.iters)
+        emit('ssim_sums float32 vs float32 %s' % size, ms, on * on * c * 8, Gwindows_per_s=round(win / ms / 1e6, 2))
+        del x32
+        ms_fq = timeit(lambda: metrics.resample_ssim_sums_device(mid, 1, on, t1, gt, 1e4), args.iters)
+        emit('imresize pass 2 + ssim_sums fused %s' % tag, ms_fq, on * n * c * 8 + on * on * c * 4, taps=taps, Gwindows_per_s=round(win / ms_fq / 1e6, 2))
+        same = bool(torch.equal(metrics.resample_ssim_sums_device(mid, 1, on, t1, gt, 1e4), metrics.ssim_sums_device(full, gt, 1e4)))
+        d = {'compare': 'SSIM of the bicubic baseline of %s: resize, store, measure vs fused' % tag,
+             'ssim_store_then_measure_ms': round(ms_a + ms_b + ms_q, 4), 'ssim_fused_ms': round(ms_a + ms_fq, 4),
+             'ssim_sums_over_uiq_sums_block_11': round(ms_q / ms_u11, 3), 'stored_GB_avoided': round(on * on * c * 8 / 1e9, 3),
+             'identical_bits': same}
         lines.append(json.dumps(d))
         print(lines[-1], flush=True)
         del lr, gt, mid, full
