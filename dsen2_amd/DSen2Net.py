@@ -282,15 +282,24 @@ class S2Model(object):
                       iters, _stream_ptr(self.device), ctypes.byref(ms))
         return ms.value
 
-    # -- training (fp32 and bf16x3 models; include/dsen2_hip.h "training") -----------------------
+    # -- training (fp32 and bf16x3 models, fp32 ones optionally on bf16 operands; include/dsen2_hip.h "training") ------
     TRAINABLE = ('fp32', 'bf16x3')
+    MIXED_PRECISIONS = {None: 0, 'bf16': 1}     # dsen2_model_set_train_precision
 
-    def compile(self, optimizer='nadam', loss='mean_absolute_error', metrics=None):
+    def compile(self, optimizer='nadam', loss='mean_absolute_error', metrics=None, mixed_precision=None):
         """keras Model.compile for the reference's recipe: optimizer 'nadam' or a training.Nadam, loss
-        'mean_absolute_error' (MSE is always reported as the metric).  The optimizer state starts fresh."""
+        'mean_absolute_error' (MSE is always reported as the metric).  The optimizer state starts fresh.
+        mixed_precision='bf16' (fp32 models only): the training step — fit, train_on_batch, gradients_device — runs its
+        convolutions on bf16 operands with fp32 accumulation, the arithmetic of a precision='bf16' model; the weights, the
+        optimizer state, the checkpoint, predict, evaluate and fit's validation pass stay fp32.  None: the model's own
+        arithmetic."""
         from . import training
         if self.precision not in self.TRAINABLE:
             raise ValueError('training needs an fp32 or a bf16x3 model (this one is %r)' % self.precision)
+        if mixed_precision not in self.MIXED_PRECISIONS:
+            raise ValueError("mixed_precision must be None or 'bf16', got %r" % (mixed_precision,))
+        if mixed_precision is not None and self.precision != 'fp32':
+            raise ValueError('mixed_precision=%r is an option of an fp32 model (this one is %r)' % (mixed_precision, self.precision))
         if loss not in ('mean_absolute_error', 'mae'):
             raise ValueError("loss must be 'mean_absolute_error', got %r" % (loss,))
         if isinstance(optimizer, str):
@@ -299,6 +308,10 @@ class S2Model(object):
             optimizer = training.Nadam()
         if not isinstance(optimizer, training.Nadam):
             raise ValueError('optimizer must be a dsen2_amd.training.Nadam')
+        if self.precision == 'fp32':
+            with torch.cuda.device(self.device):
+                _lib.call('dsen2_model_set_train_precision', self._handle, self.MIXED_PRECISIONS[mixed_precision])
+        self.mixed_precision = mixed_precision
         self.optimizer = optimizer
         self.optimizer.reset()
         self._train = None
@@ -540,6 +553,29 @@ def conv3x3_wgrad_bf16x3(a_planes, g_planes, scale=1.0):
     with torch.cuda.device(a_planes.device):
         _lib.call('dsen2_conv3x3_wgrad_bf16x3', _ptr(a_planes), _ptr(g_planes), _ptr(dw), _ptr(db), n, h, w, feat, float(scale),
                   _stream_ptr(a_planes.device))
+    return dw, db
+
+
+def bf16_plane_f32(x):
+    """fp32 NHWC CUDA tensor -> the one-plane blocked bf16 operand tensor int16 [n, c/8, h, w, 8] of conv3x3_wgrad_bf16: the hi
+    plane of split_f32, (u + 0x8000) >> 16 of every bit pattern (exact for values that already are bf16)."""
+    return split_f32(x)[0]
+
+
+def conv3x3_wgrad_bf16(a_plane, g_plane, scale=1.0):
+    """Kernel-level entry point of the bf16 weight gradient of the mixed-precision training step (include/dsen2_hip.h:
+    dsen2_conv3x3_wgrad_bf16): a_plane, g_plane int16 / bfloat16 [n, feat/8, h, w, 8] one-plane blocked operand tensors.  Returns
+    (dw [3, 3, feat, feat] HWIO, db [feat])."""
+    n, b, h, w, e = a_plane.shape
+    feat = b * e
+    if tuple(g_plane.shape) != tuple(a_plane.shape) or not a_plane.is_contiguous() or not g_plane.is_contiguous() or \
+            a_plane.element_size() != 2 or g_plane.element_size() != 2:
+        raise ValueError('a_plane and g_plane must be contiguous 16-bit tensors of the same shape')
+    dw = torch.empty((3, 3, feat, feat), dtype=torch.float32, device=a_plane.device)
+    db = torch.empty(feat, dtype=torch.float32, device=a_plane.device)
+    with torch.cuda.device(a_plane.device):
+        _lib.call('dsen2_conv3x3_wgrad_bf16', _ptr(a_plane), _ptr(g_plane), _ptr(dw), _ptr(db), n, h, w, feat, float(scale),
+                  _stream_ptr(a_plane.device))
     return dw, db
 
 

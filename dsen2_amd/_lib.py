@@ -57,6 +57,7 @@ SIGNATURES = {
     'dsen2_model_train_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     'dsen2_model_gradients': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'dsen2_model_set_train_precision': (c_int, [c_void_p, c_int]),
     'dsen2_model_get_weights': (c_int, [c_void_p, c_void_p, c_void_p]),
     'dsen2_model_set_weights_device': (c_int, [c_void_p, c_void_p, c_void_p]),
     'dsen2_nadam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t] + [ctypes.c_float] * 9 + [c_void_p]),
@@ -64,6 +65,8 @@ SIGNATURES = {
                                     ctypes.c_float, c_void_p]),
     'dsen2_conv3x3_wgrad_bf16x3': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float,
                                            c_void_p]),
+    'dsen2_conv3x3_wgrad_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float,
+                                         c_void_p]),
     'dsen2_join3_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'dsen2_upsample_mirror_bilinear': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_float,
                                                c_void_p]),

@@ -93,14 +93,19 @@ static int first_layer(const dsen2_model* m, const float* x10, const float* x20,
   return DSEN2_OK;
 }
 
+// bytes of a 16-bit operand tensor of the model's body convolutions: two bf16 planes (precision 2) or one (precision 1)
+static size_t operand16_bytes(const dsen2_model* m, int n, int h, int w) {
+  return (size_t)n * h * w * m->feat * (m->precision == 2 ? 4 : 2);
+}
+
 // The residual blocks of a precision-1 / -2 model on the stream's tensors (s0, s1) and t16.
 // Precision 1: bf16 operands, fp32 accumulate, exact fp32 residual stream held as two 16-bit planes (s0 = hi, the bf16 operand
 // of the next convolution, s1 = lo, the low halves): conv-A reads hi, conv-B updates (hi, lo) in place.
 // Precision 2, bf16x3 (conv3x3_body16w.hip, X3): fp32-grade products from three bf16 MFMAs; s0 = hx (hi | xl planes), s1 = lo16;
 // conv-A reads hx, writes t16 (hi | lo planes); conv-B reads t16, updates (hx, lo16) in place.
 // Either way the last block's conv-B writes plain fp32 out_f32 for the (fp32) output convolution.
-// keep_step > 0 (training, precision 2): layer by layer, t_l at t16 + (l - 1) * keep_step floats, s0 copied to xkeep + l *
-// keep_step after every block but the last.
+// keep_step > 0 (training): layer by layer, t_l at t16 + (l - 1) * keep_step floats, s0 — the next conv-A's operand tensor: hx's
+// two planes (precision 2) or the one hi plane (precision 1) — copied to xkeep + l * keep_step after every block but the last.
 static int body16(const dsen2_model* m, void* s0, void* s1, void* t16, float* out_f32, int n, int h, int w, hipStream_t stream,
                   size_t keep_step = 0, void* xkeep = nullptr) {
   const float* P = m->dev_params;
@@ -132,7 +137,7 @@ static int body16(const dsen2_model* m, void* s0, void* s1, void* t16, float* ou
     pb.out2 = s1;
     HIP_TRY(launch(LB.plan, pb, last ? kEpiResidualF32 : kEpiResidual, m->tune, stream));
     if (keep_step > 0 && !last)
-      HIP_TRY(hipMemcpyAsync(reinterpret_cast<float*>(xkeep) + (size_t)l * keep_step, s0, (size_t)n * h * w * m->feat * sizeof(float),
+      HIP_TRY(hipMemcpyAsync(reinterpret_cast<float*>(xkeep) + (size_t)l * keep_step, s0, operand16_bytes(m, n, h, w),
                              hipMemcpyDeviceToDevice, stream));
   }
   return DSEN2_OK;
@@ -176,11 +181,15 @@ int forward_launches(const dsen2_model* m, const float* x10, const float* x20, c
   if (m->precision == 2 && d > 0) {
     if (keep_step > 0) {
       HIP_TRY(launch_join3_f32(B.hx, B.lo16, B.x0f, n, h, w, m->feat, stream));
-      HIP_TRY(hipMemcpyAsync(B.xkeep, B.hx, (size_t)n * h * w * m->feat * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(B.xkeep, B.hx, operand16_bytes(m, n, h, w), hipMemcpyDeviceToDevice, stream));
     }
     if (int rc = body16(m, B.hx, B.lo16, B.t2, B.a, n, h, w, stream, keep_step, B.xkeep)) return rc;
   } else if (m->precision == 1 && d > 0) {
-    if (int rc = body16(m, B.hi, B.lo, B.tbf, B.a, n, h, w, stream)) return rc;
+    if (keep_step > 0) {
+      HIP_TRY(launch_join_f32(B.hi, B.lo, B.x0f, n, h, w, m->feat, stream));
+      HIP_TRY(hipMemcpyAsync(B.xkeep, B.hi, operand16_bytes(m, n, h, w), hipMemcpyDeviceToDevice, stream));
+    }
+    if (int rc = body16(m, B.hi, B.lo, B.tbf, B.a, n, h, w, stream, keep_step, B.xkeep)) return rc;
   } else {
     // (the ablation mask is 0 in the product library; a diagnostic build that sets it times the ablated kernels in the
     // inference and in the training forward)

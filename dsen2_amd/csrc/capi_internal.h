@@ -53,10 +53,13 @@ struct dsen2_model : dsen2::NetworkPlan {   // every layer's plan and place insi
   float* dev_params;
   bool loaded;
   dsen2::TrainState* train;   // NULL until the first training call
+  int train_precision = 0;    // dsen2_model_set_train_precision: 0 = the model's own arithmetic, 1 = bf16 operands (fp32 models)
   // precision 2 with residual blocks: the packed planes (hi + lo, 16 significant bits) do not hold the fp32 weights, so the
   // keras-flat vector dsen2_model_load_weights was given is kept until a training state takes it over as its master copy
   std::vector<float> host_flat;
   bool trains_x3() const { return precision == 2 && num_layers > 0; }
+  // an fp32 model whose training step runs on a precision-1 companion plan (without residual blocks that plan is all fp32)
+  bool trains_amp() const { return precision == 0 && train_precision == 1 && num_layers > 0; }
 };
 
 namespace dsen2 {
@@ -135,8 +138,8 @@ struct ForwardWs {
   float* t = nullptr;                                 // precision 0: relu(convA(x))
   void *hi = nullptr, *lo = nullptr, *tbf = nullptr;  // precision 1: the stream as two 16-bit planes; relu(convA(x)) as bf16
   void *hx = nullptr, *lo16 = nullptr, *t2 = nullptr; // precision 2: the stream as hx (hi | xl planes) and lo16; t as (hi | lo) planes
-  void* xkeep = nullptr;                              // precision 2, keep_step > 0: copies of hx, x_l at xkeep + l * keep_step floats (l < d)
-  float* x0f = nullptr;                               // precision 2, keep_step > 0: x_0 as fp32 NHWC
+  void* xkeep = nullptr;                              // precision 1 / 2, keep_step > 0: copies of hi / hx, x_l at xkeep + l * keep_step floats (l < d)
+  float* x0f = nullptr;                               // precision 1 / 2, keep_step > 0: x_0 as fp32 NHWC
   size_t bytes = 0;
 };
 // the inference workspace for n images of h x w: its size and, with base != NULL, its sub-buffers
@@ -146,7 +149,9 @@ ForwardWs forward_ws(const dsen2_model* m, int n, int h, int w, char* base);
 // x_l at B.a + l * keep_step (floats).  keep_step > 0, precision 2 (with residual blocks): always layer by layer, never the
 // chain kernel; conv-A writes t_l at B.t2 + (l - 1) * keep_step; conv-B runs in place on (B.hx, B.lo16), so hx (hi | xl, what
 // the backward reads) is copied to B.xkeep + l * keep_step after the first convolution (l = 0) and after every block but the
-// last, whose output is the fp32 tensor B.a; B.x0f receives x_0 as fp32.  Precision 1 keeps nothing.
+// last, whose output is the fp32 tensor B.a; B.x0f receives x_0 as fp32.  keep_step > 0, precision 1 (with residual blocks; the
+// companion plan of a mixed-precision training step): the same with one-plane tensors: t_l (bf16) at B.tbf + (l - 1) *
+// keep_step, the stream's hi plane — conv-A's operand — copied to B.xkeep + l * keep_step, x_0 joined from (hi, lo) into B.x0f.
 // x0_packed: the caller has already run launch_pack_inputs into B.x0.
 // ev (optional, 4 events): recorded on the stream before the first convolution, before the first and after the last
 // residual-block convolution, and after the output convolution.

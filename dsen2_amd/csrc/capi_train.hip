@@ -22,6 +22,17 @@
 // packers digit by digit: an iota does not survive a bf16 split, but a base-128 digit d packed as the value d + 1 does (exact
 // in bf16: it lands in the hi plane, the lo plane gets 0), and packed as 1 + (d + 1) * 2^-16 it lands in the lo plane (hi = 1).
 // Three passes of each kind give every half its flat index and its kind.  The body layers share one plan and so one map.
+//
+// Mixed precision (dsen2_model_set_train_precision(m, 1) on an fp32 model with residual blocks; gradients_amp): the model, its
+// master weights and its packed fp32 buffers stay as they are, and the training state owns a COMPANION: a precision-1 plan of
+// the same network with the packed buffers a precision-1 model of these weights would hold (first16 image, bf16 body planes,
+// fp32 output layer) and its own 16-bit training state (the bf16 flipped / transposed dgrad weights), both rebuilt from the
+// one master vector by launch_gather16 after every weight change — the same maps, read off the precision-1 host packers.  The
+// step is gradients_x3 with one-plane tensors: the companion's forward layer by layer, t_l (bf16, RNE) and the stream's hi
+// plane kept; g as a precision-1 residual stream (hi, lo) = exact fp32, hi = (u + 0x8000) >> 16 the dgrads' and conv-B wgrad's
+// operand; 0.1 * dgradB(hi(g)) through the fp32 epilogue over a zero stream, du = bf16_rne of its masked value
+// (launch_mask_round16); g + dgradA(du) in place; the block weight gradients on the one-plane instance of conv3x3_wgrad16.hip
+// (db = the sum of the bf16 operand g).  Loss, output layer and first layer as in gradients_x3: fp32 kernels on fp32 tensors.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -42,17 +53,26 @@ struct TrainState {
   std::vector<size_t> dg_off;  // per layer: float offset of its dgrad weights in dg (layer 0: none)
   size_t zero_off = 0;         // feat zeros (the dgrad convolutions' bias)
   ConvPlan body_plan{}, out_plan{};   // the dgrad convolutions of a body layer (F -> F) and of the output layer (16 -> F)
-  // precision 2 with residual blocks: launch_gather16 maps of the first layer's, a body layer's and the output layer's forward
-  // buffer and of a body layer's and the output layer's dgrad weights (fwd_map / dg_map stay NULL)
-  bool x3 = false;
+  // a 16-bit plan with residual blocks (a precision-2 model; the precision-1 companion of a mixed-precision step): launch_gather16
+  // maps of the first layer's, a body layer's and the output layer's forward buffer and of a body layer's and the output layer's
+  // dgrad weights (fwd_map / dg_map stay NULL)
+  bool packed16 = false;
   int* map16[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t dg_body_stride = 0;          // floats between the dgrad weights of consecutive body layers
+  // mixed precision: the precision-1 companion plan (owned; its own state has packed16 set and borrows `master`)
+  dsen2_model* amp = nullptr;
+  bool owns_master = true;
 };
 enum { kMapFirst = 0, kMapBody = 1, kMapOut = 2, kMapDgBody = 3, kMapDgOut = 4 };
 
 void train_state_destroy(TrainState* t) {
   if (!t) return;
-  if (t->master) (void)hipFree(t->master);
+  if (t->amp) {
+    train_state_destroy(t->amp->train);
+    if (t->amp->dev_params) (void)hipFree(t->amp->dev_params);
+    delete t->amp;
+  }
+  if (t->master && t->owns_master) (void)hipFree(t->master);
   if (t->fwd_map) (void)hipFree(t->fwd_map);
   if (t->dg) (void)hipFree(t->dg);
   if (t->dg_map) (void)hipFree(t->dg_map);
@@ -138,14 +158,15 @@ int upload_map(const std::vector<int>& map, int** dev) {
   return DSEN2_OK;
 }
 
-// the training state of a precision-2 model with residual blocks
-int ensure_train_state_x3(dsen2_model* m) {
+// the training state of a 16-bit plan with residual blocks: a precision-2 model (master == NULL: its own master vector), or the
+// precision-1 companion of a mixed-precision step, which borrows its owner's
+int ensure_train_state_x3(dsen2_model* m, float* master = nullptr) {
   TrainState* t = new TrainState();
   StateGuard guard{t};
-  t->x3 = true;
+  t->packed16 = true;
   const int F = m->feat;
   const size_t L = m->layers.size();
-  if (!plan_conv(ConvRole::DgradBody, F, F, 2, m->tune, nullptr, &t->body_plan) ||
+  if (!plan_conv(ConvRole::DgradBody, F, F, m->precision, m->tune, nullptr, &t->body_plan) ||
       !plan_conv(ConvRole::DgradOutput, 16, F, 0, m->tune, nullptr, &t->out_plan))
     return fail(DSEN2_ERR_INVALID, "no dgrad kernel for feature size %d", F);
   auto iota = [](size_t count) {
@@ -179,16 +200,18 @@ int ensure_train_state_x3(dsen2_model* m) {
   t->zero_off = off;
   off += align_up((size_t)F);
   t->dg_floats = off;
-  HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
+  t->owns_master = master == nullptr;
+  t->master = master;
+  if (t->owns_master) HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
   HIP_TRY(hipMalloc((void**)&t->dg, t->dg_floats * sizeof(float)));
   HIP_TRY(hipMemset(t->dg, 0, t->dg_floats * sizeof(float)));        // the zero bias; the padding between the layers
   m->train = t;
   guard.t = nullptr;
-  if (m->loaded) return train_state_after_load(m);
+  if (t->owns_master && m->loaded) return train_state_after_load(m);
   return DSEN2_OK;
 }
 
-// the packed forward buffers (fwd) and / or the dgrad weights of a precision-2 model <- master
+// the packed forward buffers (fwd) and / or the dgrad weights of a 16-bit plan <- master
 int repack_x3(dsen2_model* m, bool fwd, hipStream_t s) {
   TrainState* t = m->train;
   const size_t L = m->layers.size();
@@ -203,6 +226,31 @@ int repack_x3(dsen2_model* m, bool fwd, hipStream_t s) {
   HIP_TRY(launch_gather16(t->dg + t->dg_off[1], t->master + L1.flat_off, t->map16[kMapDgBody], t->body_plan.weight_floats,
                           2 * m->num_layers, t->dg_body_stride, body_values, s));
   HIP_TRY(launch_gather16(t->dg + t->dg_off[L - 1], t->master + LO.flat_off, t->map16[kMapDgOut], t->out_plan.weight_floats, 1, 0, 0, s));
+  return DSEN2_OK;
+}
+
+// the precision-1 companion of a mixed-precision step: the same network planned with bf16 operands, its packed buffers allocated
+// (filled by repack_x3) and its 16-bit training state on the owner's master vector
+int create_amp_companion(const dsen2_model* m, float* master, dsen2_model** out) {
+  struct Guard {
+    dsen2_model* c;
+    ~Guard() {
+      if (!c) return;
+      train_state_destroy(c->train);
+      if (c->dev_params) (void)hipFree(c->dev_params);
+      delete c;
+    }
+  } g{new dsen2_model()};
+  dsen2_model* c = g.c;
+  c->c10 = m->c10; c->c20 = m->c20; c->c60 = m->c60; c->cin = m->cin; c->cout = m->cout;
+  c->num_layers = m->num_layers; c->feat = m->feat; c->precision = 1; c->device = m->device; c->tune = m->tune;
+  c->dev_params = nullptr; c->loaded = false; c->train = nullptr;
+  if (!plan_network(m->c10, m->c20, m->c60, m->num_layers, m->feat, 1, c->tune, c) || c->n_params != m->n_params)
+    return fail(DSEN2_ERR_INVALID, "no bf16 kernel for a layer of this network");
+  HIP_TRY(hipMalloc((void**)&c->dev_params, c->dev_param_floats * sizeof(float)));
+  if (int rc = ensure_train_state_x3(c, master)) return rc;
+  *out = c;
+  g.c = nullptr;
   return DSEN2_OK;
 }
 
@@ -228,47 +276,56 @@ int ensure_train_state(dsen2_model* m) {
     pack(Ly.plan, k.data(), k.data() + nk, buf.data());
     for (size_t i = 0; i < buf.size(); ++i) fmap[Ly.off + i] = map_value(buf[i], Ly.flat_off);
   }
-  // dgrad weights: W'[tap][c'][o'] = W[8 - tap][o'][c'] for the body layers (F -> F) and the output layer (16 -> F, the
-  // outputs zero-padded to 16 input channels); layer 0 needs no input gradient
-  t->dg_off.assign(L, 0);
-  size_t off = 0;
-  for (size_t li = 1; li < L; ++li) {
-    t->dg_off[li] = off;
-    off += align_up((li + 1 == L ? t->out_plan : t->body_plan).weight_floats);
-  }
-  t->zero_off = off;
-  off += align_up((size_t)F);
-  t->dg_floats = off;
-  std::vector<int> dmap(off, 0);
-  for (size_t li = 1; li < L; ++li) {
-    const int ci = m->layers[li].plan.cin, co = m->layers[li].plan.cout;
-    const ConvPlan& g = li + 1 == L ? t->out_plan : t->body_plan;    // the dgrad convolution: forward outputs -> forward inputs
-    k.assign((size_t)9 * g.cin * g.cout, 0.f);
-    for (int tap = 0; tap < 9; ++tap)
-      for (int c = 0; c < co; ++c)
-        for (int o = 0; o < ci; ++o)
-          k[((size_t)tap * g.cin + c) * g.cout + o] = (float)(((size_t)(8 - tap) * ci + o) * co + c + 1);
-    buf.resize(g.weight_floats);
-    pack(g, k.data(), nullptr, buf.data());
-    for (size_t i = 0; i < buf.size(); ++i) dmap[t->dg_off[li] + i] = map_value(buf[i], m->layers[li].flat_off);
+  // (mixed precision: the step runs on the companion's bf16 dgrad weights; the fp32 ones are neither built nor kept)
+  const bool own_dgrad = !m->trains_amp();
+  std::vector<int> dmap;
+  if (own_dgrad) {
+    // dgrad weights: W'[tap][c'][o'] = W[8 - tap][o'][c'] for the body layers (F -> F) and the output layer (16 -> F, the
+    // outputs zero-padded to 16 input channels); layer 0 needs no input gradient
+    t->dg_off.assign(L, 0);
+    size_t off = 0;
+    for (size_t li = 1; li < L; ++li) {
+      t->dg_off[li] = off;
+      off += align_up((li + 1 == L ? t->out_plan : t->body_plan).weight_floats);
+    }
+    t->zero_off = off;
+    off += align_up((size_t)F);
+    t->dg_floats = off;
+    dmap.assign(off, 0);
+    for (size_t li = 1; li < L; ++li) {
+      const int ci = m->layers[li].plan.cin, co = m->layers[li].plan.cout;
+      const ConvPlan& g = li + 1 == L ? t->out_plan : t->body_plan;    // the dgrad convolution: forward outputs -> forward inputs
+      k.assign((size_t)9 * g.cin * g.cout, 0.f);
+      for (int tap = 0; tap < 9; ++tap)
+        for (int c = 0; c < co; ++c)
+          for (int o = 0; o < ci; ++o)
+            k[((size_t)tap * g.cin + c) * g.cout + o] = (float)(((size_t)(8 - tap) * ci + o) * co + c + 1);
+      buf.resize(g.weight_floats);
+      pack(g, k.data(), nullptr, buf.data());
+      for (size_t i = 0; i < buf.size(); ++i) dmap[t->dg_off[li] + i] = map_value(buf[i], m->layers[li].flat_off);
+    }
   }
   HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
   HIP_TRY(hipMalloc((void**)&t->fwd_map, fmap.size() * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&t->dg, t->dg_floats * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&t->dg_map, dmap.size() * sizeof(int)));
   HIP_TRY(hipMemcpy(t->fwd_map, fmap.data(), fmap.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t->dg_map, dmap.data(), dmap.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (own_dgrad) {
+    HIP_TRY(hipMalloc((void**)&t->dg, t->dg_floats * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&t->dg_map, dmap.size() * sizeof(int)));
+    HIP_TRY(hipMemcpy(t->dg_map, dmap.data(), dmap.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (m->trains_amp())
+    if (int rc = create_amp_companion(m, t->master, &t->amp)) return rc;
   m->train = t;
   guard.t = nullptr;
   if (m->loaded) return train_state_after_load(m);
   return DSEN2_OK;
 }
 
-// master <- the packed forward weights (inverse gather), dgrad weights <- master
+// master <- the packed forward weights (inverse gather), dgrad weights (where the state has its own) <- master
 int refresh_from_packed(dsen2_model* m, hipStream_t s) {
   TrainState* t = m->train;
   HIP_TRY(launch_scatter(t->master, m->dev_params, t->fwd_map, m->dev_param_floats, s));
-  HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
+  if (t->dg) HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
   return DSEN2_OK;
 }
 
@@ -363,8 +420,125 @@ TrainWs3 carve_x3(const dsen2_model* m, int n, int h, int w, char* base) {
   return r;
 }
 
+// ---- mixed precision: an fp32 model's step on its precision-1 companion ----
+struct TrainWsAmp {
+  float *in16, *a32, *x0f, *out, *gpad, *g32, *wg, *loss2;
+  char *hi, *lo, *xkeep, *tkeep, *ghi, *glo, *du, *zhi, *zlo;     // one-plane 16-bit tensors
+  double* partial;
+  size_t keep_step;   // floats between the kept hi planes of x_l and between the kept t_l
+  size_t wg_floats;
+  size_t bytes;
+};
+
+TrainWsAmp carve_amp(const dsen2_model* m, int n, int h, int w, char* base) {
+  const size_t pix = (size_t)n * h * w, F = m->feat;
+  const size_t full = align_up(pix * F), half = align_up(pix * F / 2);     // a one-plane 16-bit tensor is `half` floats
+  size_t wg = wgrad16_workspace_floats(n, h, w, m->feat);
+  const size_t wg1 = wgrad_workspace_floats(n, h, w, 16, m->feat), wg2 = wgrad_workspace_floats(n, h, w, m->feat, 16);
+  if (wg1 > wg) wg = wg1;
+  if (wg2 > wg) wg = wg2;
+  TrainWsAmp r;
+  size_t off = 0;
+  auto take = [&](size_t floats) -> float* {
+    float* p = base ? reinterpret_cast<float*>(base) + off : nullptr;
+    off += align_up(floats);
+    return p;
+  };
+  auto take16 = [&](size_t floats) { return reinterpret_cast<char*>(take(floats)); };
+  const size_t d = (size_t)m->num_layers;
+  r.in16 = take(pix * 16);
+  r.a32 = take(full);
+  r.x0f = take(full);
+  r.hi = take16(half);
+  r.lo = take16(half);
+  r.keep_step = half;
+  r.xkeep = take16(d * half);      // hi of x_0 .. x_{d-1}
+  r.tkeep = take16(d * half);      // t_1 .. t_d
+  r.out = take(pix * m->cout);
+  r.gpad = take(pix * 16);
+  r.g32 = take(full);
+  r.ghi = take16(half);
+  r.glo = take16(half);
+  r.du = take16(half);
+  r.zhi = take16(half);
+  r.zlo = take16(half);
+  r.wg = take(wg);
+  r.wg_floats = wg;
+  r.partial = reinterpret_cast<double*>(take(2 * mae_loss_partial_doubles(pix)));
+  r.loss2 = take(2);
+  r.bytes = off * sizeof(float);
+  return r;
+}
+
 size_t train_ws_bytes(const dsen2_model* m, int n, int h, int w) {
-  return m->trains_x3() ? carve_x3(m, n, h, w, nullptr).bytes : carve(m, n, h, w, nullptr).bytes;
+  return m->trains_x3()    ? carve_x3(m, n, h, w, nullptr).bytes
+         : m->trains_amp() ? carve_amp(m, n, h, w, nullptr).bytes
+                           : carve(m, n, h, w, nullptr).bytes;
+}
+
+// dsen2_model_gradients of an fp32 model with train precision 1 (arguments checked, training state present): on the companion
+// plan c; see the file comment
+int gradients_amp(dsen2_model* m, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out, float* grad,
+                  float* loss2, int n, int h, int w, void* ws, hipStream_t s) {
+  TrainWsAmp W = carve_amp(m, n, h, w, reinterpret_cast<char*>(ws));
+  if (!dev_out) dev_out = W.out;
+  if (!loss2) loss2 = W.loss2;
+  const dsen2_model* c = m->train->amp;
+  const TrainState* t = c->train;
+  const float* zero = t->dg + t->zero_off;
+  const int F = c->feat, d = c->num_layers;
+  const size_t pix = (size_t)n * h * w;
+  const size_t fbytes = pix * F * sizeof(float);
+  const Layer& LO = c->layers.back();
+  auto kept = [&](char* base, int l) { return base + (size_t)l * W.keep_step * sizeof(float); };
+
+  // ---- forward on the precision-1 per-layer launches, t_l and the hi plane of every x_l kept ----
+  HIP_TRY(launch_pack_inputs(x10, x20, x60, c->c10, c->c20, c->c60, W.in16, n, h, w, s));
+  ForwardWs B;
+  B.x0 = W.in16; B.a = W.a32; B.hi = W.hi; B.lo = W.lo; B.tbf = W.tkeep; B.xkeep = W.xkeep; B.x0f = W.x0f;
+  if (int rc = forward_launches(c, x10, x20, x60, dev_out, n, h, w, B, W.keep_step, true, s, nullptr)) return rc;
+
+  // ---- loss, output layer (fp32 kernels) ----
+  HIP_TRY(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, c->cout, h, w, s));
+  auto wgrad32 = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly) -> hipError_t {
+    float* dw = grad + Ly.flat_off;
+    return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.plan.cin, Ly.plan.cout, 1.f, dw, dw + (size_t)9 * Ly.plan.cin * Ly.plan.cout, W.wg,
+                                W.wg_floats, s);
+  };
+  auto wgrad16 = [&](const void* a, const void* g, const Layer& Ly, float scale) -> hipError_t {
+    float* dw = grad + Ly.flat_off;
+    return launch_conv3x3_wgrad16_bf16(a, g, n, h, w, F, scale, dw, dw + (size_t)9 * F * F, W.wg, W.wg_floats, s);
+  };
+  HIP_TRY(wgrad32(W.a32, F, W.gpad, 16, LO));
+  HIP_TRY(hipMemsetAsync(W.g32, 0, fbytes, s));
+  HIP_TRY(launch(t->out_plan, make_params(W.gpad, t->dg + t->dg_off[c->layers.size() - 1], zero, W.g32, W.g32, n, h, w, 0, 1.f), kEpiResidual,
+                 c->tune, s));
+  // g as a precision-1 residual stream; the zero stream 0.1 * dgradB is added to (its fp32 epilogue never writes it)
+  HIP_TRY(launch_split_f32(W.g32, W.ghi, W.glo, n, h, w, F, s));
+  HIP_TRY(hipMemsetAsync(W.zhi, 0, fbytes / 2, s));
+  HIP_TRY(hipMemsetAsync(W.zlo, 0, fbytes / 2, s));
+  // ---- residual blocks, last to first ----
+  for (int l = d; l >= 1; --l) {
+    const Layer& LA = c->layers[2 * l - 1];
+    const Layer& LB = c->layers[2 * l];
+    const char* t_l = kept(W.tkeep, l - 1);
+    HIP_TRY(wgrad16(t_l, W.ghi, LB, 0.1f));
+    ConvParams pb = make_params(reinterpret_cast<const float*>(W.ghi), t->dg + t->dg_off[2 * l], zero, reinterpret_cast<const float*>(W.zhi),
+                                W.g32, n, h, w, 0, 0.1f);
+    pb.out2 = W.zlo;
+    HIP_TRY(launch(t->body_plan, pb, kEpiResidualF32, c->tune, s));
+    HIP_TRY(launch_mask_round16(W.g32, t_l, W.du, n, h, w, F, s));
+    HIP_TRY(wgrad16(kept(W.xkeep, l - 1), W.du, LA, 1.f));
+    ConvParams pa = make_params(reinterpret_cast<const float*>(W.du), t->dg + t->dg_off[2 * l - 1], zero, reinterpret_cast<const float*>(W.ghi),
+                                reinterpret_cast<float*>(W.ghi), n, h, w, 0, 1.f);
+    pa.out2 = W.glo;
+    HIP_TRY(launch(t->body_plan, pa, kEpiResidual, c->tune, s));
+  }
+  // ---- first convolution (fp32 kernels) ----
+  HIP_TRY(launch_join_f32(W.ghi, W.glo, W.g32, n, h, w, F, s));
+  HIP_TRY(launch_relu_mask(W.g32, W.x0f, pix * F, s));
+  HIP_TRY(wgrad32(W.in16, 16, W.g32, F, c->layers[0]));
+  return DSEN2_OK;
 }
 
 // dsen2_model_gradients of a precision-2 model (arguments checked, training state present); see the file comment
@@ -435,7 +609,7 @@ int gradients_x3(dsen2_model* m, const float* x10, const float* x20, const float
 namespace dsen2 {
 
 int train_state_after_load(dsen2_model* m) {
-  if (m->train->x3) {
+  if (m->train->packed16) {
     // the packed planes do not hold the fp32 weights: the master copy is the vector dsen2_model_load_weights was given
     if (m->host_flat.size() != m->n_params) return fail(DSEN2_ERR_INTERNAL, "the loaded weights were not kept");
     HIP_TRY(hipMemcpy(m->train->master, m->host_flat.data(), m->n_params * sizeof(float), hipMemcpyHostToDevice));
@@ -445,6 +619,10 @@ int train_state_after_load(dsen2_model* m) {
     return DSEN2_OK;
   }
   if (int rc = refresh_from_packed(m, nullptr)) return rc;
+  if (dsen2_model* c = m->train->amp) {       // the companion's packed buffers follow the master copy
+    if (int rc = repack_x3(c, true, nullptr)) return rc;
+    c->loaded = true;
+  }
   HIP_TRY(hipStreamSynchronize(nullptr));
   return DSEN2_OK;
 }
@@ -474,7 +652,8 @@ int dsen2_model_gradients(dsen2_model* m, const float* x10, const float* x20, co
     const size_t need = train_ws_bytes(m, n, h, w);
     if (ws_bytes < need) return fail(DSEN2_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
     if (int rc = ensure_train_state(m)) return rc;
-    if (m->train->x3) return gradients_x3(m, x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
+    if (m->train->packed16) return gradients_x3(m, x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
+    if (m->train->amp) return gradients_amp(m, x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
     TrainWs W = carve(m, n, h, w, reinterpret_cast<char*>(ws));
     if (!dev_out) dev_out = W.out;
     if (!loss2) loss2 = W.loss2;
@@ -546,16 +725,42 @@ int dsen2_model_set_weights_device(dsen2_model* m, const float* dev_flat, void* 
     TrainState* t = m->train;
     if (dev_flat != t->master)
       HIP_TRY(hipMemcpyAsync(t->master, dev_flat, m->n_params * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (t->x3) {
+    if (t->packed16) {
       std::vector<float>().swap(m->host_flat);
       if (int rc = repack_x3(m, true, s)) return rc;
       m->loaded = true;
       return DSEN2_OK;
     }
-    HIP_TRY(launch_gather(m->dev_params, t->master, t->fwd_map, m->dev_param_floats, s));
-    HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
+    HIP_TRY(launch_gather(m->dev_params, t->master, t->fwd_map, m->dev_param_floats, s));     // predict / evaluate read these
+    if (t->amp) {       // the step runs on the companion: its packed buffers and bf16 dgrad weights, not the fp32 dgrad weights
+      if (int rc = repack_x3(t->amp, true, s)) return rc;
+      t->amp->loaded = true;
+    } else {
+      HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
+    }
     m->loaded = true;
     return DSEN2_OK;
+  });
+}
+
+int dsen2_model_set_train_precision(dsen2_model* m, int precision) {
+  return guarded([&]() -> int {
+    if (!m) return fail(DSEN2_ERR_INVALID, "NULL model");
+    if (m->precision != 0)
+      return fail(DSEN2_ERR_INVALID, "the train precision is an option of an fp32 model (this one has precision %d)", m->precision);
+    if (precision != 0 && precision != 1)
+      return fail(DSEN2_ERR_INVALID, "train precision %d unknown (0 = the model's own arithmetic, 1 = bf16 operands)", precision);
+    if (precision == m->train_precision) return DSEN2_OK;
+    const bool had_state = m->train != nullptr;
+    if (had_state) {      // drop it (nothing may still be running on its buffers) and build the other one: the master copy is
+                          // restored from the packed fp32 weights, which hold every value exactly
+      if (int rc = check_device(m)) return rc;
+      HIP_TRY(hipDeviceSynchronize());
+      train_state_destroy(m->train);
+      m->train = nullptr;
+    }
+    m->train_precision = precision;
+    return had_state ? ensure_train_state(m) : DSEN2_OK;
   });
 }
 
@@ -582,18 +787,30 @@ int dsen2_conv3x3_wgrad(const float* dev_a, const float* dev_g, float* dev_dw, f
   });
 }
 
-int dsen2_conv3x3_wgrad_bf16x3(const void* dev_a_planes, const void* dev_g_planes, float* dev_dw, float* dev_db, int n, int h, int w,
-                               int feat, float scale, void* stream) {
+// dsen2_conv3x3_wgrad_bf16x3 (planes 2) and dsen2_conv3x3_wgrad_bf16 (planes 1): one set of checks
+static int conv3x3_wgrad16(int planes, const void* dev_a, const void* dev_g, float* dev_dw, float* dev_db, int n, int h, int w, int feat,
+                           float scale, void* stream) {
   return guarded([&]() -> int {
-    if (!dev_a_planes || !dev_g_planes || !dev_dw || !dev_db) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if (!dev_a || !dev_g || !dev_dw || !dev_db) return fail(DSEN2_ERR_INVALID, "NULL argument");
     if (feat != 128 && feat != 256) return fail(DSEN2_ERR_INVALID, "feat %d unsupported (128 or 256)", feat);
     if (int rc = check_shape(nullptr, n, h, w)) return rc;
     const size_t wf = wgrad16_workspace_floats(n, h, w, feat);
     hipStream_t s = (hipStream_t)stream;
-    return launch_once_with_temp("bf16x3 wgrad", nullptr, wf * sizeof(float), s, [&](char* dev) {
-      return launch_conv3x3_wgrad16(dev_a_planes, dev_g_planes, n, h, w, feat, scale, dev_dw, dev_db, reinterpret_cast<float*>(dev), wf, s);
+    return launch_once_with_temp(planes == 2 ? "bf16x3 wgrad" : "bf16 wgrad", nullptr, wf * sizeof(float), s, [&](char* dev) {
+      return (planes == 2 ? launch_conv3x3_wgrad16 : launch_conv3x3_wgrad16_bf16)(dev_a, dev_g, n, h, w, feat, scale, dev_dw, dev_db,
+                                                                                   reinterpret_cast<float*>(dev), wf, s);
     });
   });
+}
+
+int dsen2_conv3x3_wgrad_bf16x3(const void* dev_a_planes, const void* dev_g_planes, float* dev_dw, float* dev_db, int n, int h, int w,
+                               int feat, float scale, void* stream) {
+  return conv3x3_wgrad16(2, dev_a_planes, dev_g_planes, dev_dw, dev_db, n, h, w, feat, scale, stream);
+}
+
+int dsen2_conv3x3_wgrad_bf16(const void* dev_a, const void* dev_g, float* dev_dw, float* dev_db, int n, int h, int w, int feat,
+                             float scale, void* stream) {
+  return conv3x3_wgrad16(1, dev_a, dev_g, dev_dw, dev_db, n, h, w, feat, scale, stream);
 }
 
 }  // extern "C"

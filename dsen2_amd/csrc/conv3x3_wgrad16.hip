@@ -28,6 +28,13 @@
 //   * split-K exactly as conv3x3_wgrad.hip: contiguous tile runs, a split count that does not depend on the device, partial
 //     sums to a workspace, a second kernel adds them in split order (double) — no float atomics, the same bits on every run.
 // Pixels outside the image (ragged tiles, the halo) are staged as zeros in both planes: they add exact zeros.
+//
+// ONE-PLANE INSTANCE (PL = 1; mixed-precision training of an fp32 model, capi_train.hip gradients_amp): a and g are one-plane
+// blocked bf16 tensors [n][F/8][h][w][8] (conv-A's bf16 t, the hi plane of a residual stream, launch_mask_round16's du) and a
+// product is the one MFMA a*g: one v_mfma_f32_32x32x16_bf16 per tap and row where PL = 2 issues three; the staging registers
+// and the LDS tile are half as large (55 KiB), everything else above — block, pixel tile, transposed staging, alignbyte
+// shifts, split count, second pass, zeros outside the image — is the same code.  Resource usage and what it allows: see
+// kMinBlocks below.
 #include "conv3x3_bf16_common.h"
 
 namespace dsen2 {
@@ -47,19 +54,32 @@ constexpr int kGCh = kTY * kTX + 8;               // bf16 per channel of g: 72 (
 constexpr int kCOB = 128, kCIB = 32;
 constexpr int kThreads = 256;
 constexpr int kAPlane = kCIB * kACh, kGPlane = kCOB * kGCh;
-constexpr int kBufElems = 2 * kAPlane + 2 * kGPlane;
-constexpr size_t kLdsBytes = (size_t)2 * kBufElems * 2;
-constexpr int kAPieces = 2 * (kCIB / 8) * kHY * kAPairs;     // (plane, 8-channel block, row, pixel pair): 480
-constexpr int kGPieces = 2 * (kCOB / 8) * kTY * kGPairs;     // 1024
-constexpr int kARounds = (kAPieces + kThreads - 1) / kThreads, kGRounds = kGPieces / kThreads;
+// what depends on the number of operand planes PL (2 = bf16x3, 1 = bf16)
+template <int PL>
+struct Planes {
+  static constexpr int kBufElems = PL * kAPlane + PL * kGPlane;
+  static constexpr size_t kLdsBytes = (size_t)2 * kBufElems * 2;      // 110 KiB / 55 KiB
+  static constexpr int kAPieces = PL * (kCIB / 8) * kHY * kAPairs;    // (plane, 8-channel block, row, pixel pair): 480 / 240
+  static constexpr int kGPieces = PL * (kCOB / 8) * kTY * kGPairs;    // 1024 / 512
+  static constexpr int kARounds = (kAPieces + kThreads - 1) / kThreads, kGRounds = kGPieces / kThreads;
+  // Workgroups per CU the kernel is compiled for.  PL = 2: 148 VGPRs + 144 AGPRs and 110 KiB of LDS, one.  PL = 1: compiled
+  // for two, hipcc's resource usage is 226 registers (accumulators included, no AGPRs) with no spill and no scratch — inside
+  // the 256 a wave gets at two waves per SIMD — and 2 x 55 KiB of LDS fit the CU's 160 KiB.  A launch has at most
+  // kTargetBlocks = 256 workgroups, one per CU of a whole MI355X, and there a build for one workgroup per CU measures the same
+  // (65.5 / 65.7 us at F = 128 batch 128, 24.8 / 24.8 us at F = 256 batch 8: profiles/train_amp_bf16.md); two is kept because it
+  // costs nothing and is what a device with fewer CUs than workgroups (a compute partition) uses.  The split count is not
+  // raised to fill the slot: by byte count the partials at F = 256, batch 8 (16 splits x 2.36 MB written and read back)
+  // already outweigh the operands (2 x 4.2 MB).
+  static constexpr int kMinBlocks = PL == 1 ? 2 : 1;
+  static_assert(kGPieces % kThreads == 0, "g pieces");
+  static_assert(kLdsBytes * kMinBlocks <= 160 * 1024, "LDS budget");
+};
 constexpr int kTargetBlocks = 256;    // workgroups per launch the split count aims at; fixed, so the summation order — and
                                       // the result — does not depend on the device
-static_assert(kGPieces % kThreads == 0, "g pieces");
-static_assert(kLdsBytes <= 160 * 1024, "LDS budget");
 static_assert(kACh % 8 == 0 && kGCh % 8 == 0 && (kACh / 8) % 2 == 1 && (kGCh / 8) % 2 == 1, "16-byte rows, odd 16-byte pitch");
 
 struct Wgrad16Params {
-  const u32x4* a;      // [n][2][F/8][h][w] pixels of 8 bf16
+  const u32x4* a;      // [n][PL][F/8][h][w] pixels of 8 bf16
   const u32x4* g;
   float* part;         // [splits][9][F][F]
   float* bpart;        // [splits][2][F]
@@ -69,7 +89,10 @@ struct Wgrad16Params {
   long long tiles;
 };
 
-__global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgrad16Params p) {
+template <int PL>
+__global__ __launch_bounds__(kThreads, Planes<PL>::kMinBlocks) void conv3x3_wgrad16_kernel(const Wgrad16Params p) {
+  constexpr int kBufElems = Planes<PL>::kBufElems, kAPieces = Planes<PL>::kAPieces;
+  constexpr int kARounds = Planes<PL>::kARounds, kGRounds = Planes<PL>::kGRounds;
   extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -95,7 +118,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgra
       const int cp = pc % kAPairs, row = (pc / kAPairs) % kHY, blk = (pc / (kAPairs * kHY)) % (kCIB / 8), plane = pc / (kAPairs * kHY * (kCIB / 8));
       const int gy = ty0 - 1 + row, gx = tx0 - 2 + 2 * cp;
       const bool ok = pc < kAPieces && (unsigned)gy < (unsigned)p.h;
-      const u32x4* src = p.a + (((size_t)img * 2 + plane) * p.nblk + (cib0 >> 3) + blk) * img_pix + (size_t)(ok ? gy : 0) * p.w;
+      const u32x4* src = p.a + (((size_t)img * PL + plane) * p.nblk + (cib0 >> 3) + blk) * img_pix + (size_t)(ok ? gy : 0) * p.w;
       ar[r][0] = ok && (unsigned)gx < (unsigned)p.w ? src[gx] : zero4;
       ar[r][1] = ok && (unsigned)(gx + 1) < (unsigned)p.w ? src[gx + 1] : zero4;
     }
@@ -105,7 +128,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgra
       const int cp = pc % kGPairs, row = (pc / kGPairs) % kTY, blk = (pc / (kGPairs * kTY)) % (kCOB / 8), plane = pc / (kGPairs * kTY * (kCOB / 8));
       const int gy = ty0 + row, gx = tx0 + 2 * cp;
       const bool ok = gy < p.h;
-      const u32x4* src = p.g + (((size_t)img * 2 + plane) * p.nblk + (cob0 >> 3) + blk) * img_pix + (size_t)(ok ? gy : 0) * p.w;
+      const u32x4* src = p.g + (((size_t)img * PL + plane) * p.nblk + (cob0 >> 3) + blk) * img_pix + (size_t)(ok ? gy : 0) * p.w;
       gr[r][0] = ok && gx < p.w ? src[gx] : zero4;
       gr[r][1] = ok && gx + 1 < p.w ? src[gx + 1] : zero4;
     }
@@ -118,7 +141,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgra
   };
   auto store_tile = [&](int buf) {
     unsigned* const a_s = reinterpret_cast<unsigned*>(smem16 + buf * kBufElems);
-    unsigned* const g_s = a_s + kAPlane;         // (dwords: behind the two planes of a)
+    unsigned* const g_s = a_s + PL * kAPlane / 2;         // (dwords: behind the PL planes of a)
 #pragma unroll
     for (int r = 0; r < kARounds; ++r) {
       const int pc = r * kThreads + tid;
@@ -151,11 +174,11 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgra
     const bool more = t + 1 < t_end;
     if (more) load_tile(t + 1);
     const unsigned short* const a_l = smem16 + cur * kBufElems + l31 * kACh + 8 * khalf;
-    const unsigned short* const g_l = smem16 + cur * kBufElems + 2 * kAPlane + (wave * 32 + l31) * kGCh + 8 * khalf;
-    // the A operands of the tile: this lane's 8 pixels of every row, both planes
-    u32x4 gop[2][kTY];
+    const unsigned short* const g_l = smem16 + cur * kBufElems + PL * kAPlane + (wave * 32 + l31) * kGCh + 8 * khalf;
+    // the A operands of the tile: this lane's 8 pixels of every row, every plane
+    u32x4 gop[PL][kTY];
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
+    for (int pl = 0; pl < PL; ++pl)
 #pragma unroll
       for (int y = 0; y < kTY; ++y) gop[pl][y] = *reinterpret_cast<const u32x4*>(g_l + pl * kGPlane + y * kTX);
     if (bias_block) {
@@ -164,7 +187,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgra
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-          for (int pl = 0; pl < 2; ++pl) {
+          for (int pl = 0; pl < PL; ++pl) {
             bsum += __builtin_bit_cast(float, gop[pl][y][k] << 16);
             bsum += __builtin_bit_cast(float, gop[pl][y][k] & 0xffff0000u);
           }
@@ -172,9 +195,9 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgra
 #pragma unroll
     for (int r = 0; r < kHY; ++r) {
       // halo row r, columns 8*khalf .. + 15 (dwords w[0..7]); the operand of tap column kx is columns + kx + 1 .. + kx + 8
-      u32x4 bop[2][3];
+      u32x4 bop[PL][3];
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) {
+      for (int pl = 0; pl < PL; ++pl) {
         const u32x4 w0 = *reinterpret_cast<const u32x4*>(a_l + pl * kAPlane + r * kACols);
         const u32x4 w1 = *reinterpret_cast<const u32x4*>(a_l + pl * kAPlane + r * kACols + 8);
         const unsigned w[6] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1]};
@@ -192,11 +215,13 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wgrad16_kernel(const Wgra
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
           const int tap = 3 * ky + kx;
-          const bf16x8 g0 = __builtin_bit_cast(bf16x8, gop[0][y]), g1 = __builtin_bit_cast(bf16x8, gop[1][y]);
-          const bf16x8 a0 = __builtin_bit_cast(bf16x8, bop[0][kx]), a1 = __builtin_bit_cast(bf16x8, bop[1][kx]);
+          const bf16x8 g0 = __builtin_bit_cast(bf16x8, gop[0][y]), a0 = __builtin_bit_cast(bf16x8, bop[0][kx]);
           acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0, a0, acc[tap], 0, 0, 0);
-          acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1, a0, acc[tap], 0, 0, 0);
-          acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0, a1, acc[tap], 0, 0, 0);
+          if constexpr (PL == 2) {
+            const bf16x8 g1 = __builtin_bit_cast(bf16x8, gop[1][y]), a1 = __builtin_bit_cast(bf16x8, bop[1][kx]);
+            acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1, a0, acc[tap], 0, 0, 0);
+            acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0, a1, acc[tap], 0, 0, 0);
+          }
         }
       }
     }
@@ -259,8 +284,11 @@ size_t wgrad16_workspace_floats(int n, int h, int w, int feat) {
   return (size_t)g.splits * ((size_t)9 * feat * feat + (size_t)2 * feat);
 }
 
-hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, int n, int h, int w, int feat, float scale, float* dw,
-                                  float* db, float* ws, size_t ws_floats, hipStream_t stream) {
+namespace {
+
+template <int PL>
+hipError_t launch_wgrad16(const void* a_planes, const void* g_planes, int n, int h, int w, int feat, float scale, float* dw, float* db,
+                          float* ws, size_t ws_floats, hipStream_t stream) {
   Wgrad16Geom geo;
   if (!a_planes || !g_planes || !dw || !db || !ws || !wgrad16_geom(n, h, w, feat, &geo)) return hipErrorInvalidValue;
   if ((size_t)h * w * feat >= ((size_t)1 << 29)) return hipErrorInvalidValue;
@@ -273,7 +301,8 @@ hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, in
   p.n = n; p.h = h; p.w = w; p.nblk = feat / 8;
   p.tiles_x = geo.tiles_x; p.tiles_y = geo.tiles_y;
   p.splits = geo.splits; p.feat = feat; p.tiles = geo.tiles;
-  constexpr auto kern = conv3x3_wgrad16_kernel;
+  constexpr auto kern = conv3x3_wgrad16_kernel<PL>;
+  constexpr size_t kLdsBytes = Planes<PL>::kLdsBytes;
   hipError_t e = prepare_kernel<kern>(kLdsBytes, nullptr);
   if (e != hipSuccess) return e;
   const dim3 grid((unsigned)geo.splits, (unsigned)((feat / kCOB) * (feat / kCIB)), 1);
@@ -283,6 +312,18 @@ hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, in
   hipLaunchKernelGGL(conv3x3_wgrad16_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p.part, p.bpart,
                      dw, db, geo.splits, feat, scale);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, int n, int h, int w, int feat, float scale, float* dw,
+                                  float* db, float* ws, size_t ws_floats, hipStream_t stream) {
+  return launch_wgrad16<2>(a_planes, g_planes, n, h, w, feat, scale, dw, db, ws, ws_floats, stream);
+}
+
+hipError_t launch_conv3x3_wgrad16_bf16(const void* a, const void* g, int n, int h, int w, int feat, float scale, float* dw, float* db,
+                                       float* ws, size_t ws_floats, hipStream_t stream) {
+  return launch_wgrad16<1>(a, g, n, h, w, feat, scale, dw, db, ws, ws_floats, stream);
 }
 
 }  // namespace dsen2

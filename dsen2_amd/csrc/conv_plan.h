@@ -9,7 +9,8 @@
 namespace dsen2 {
 
 // DSen2Net.py's graph: First (Concatenate + Conv2D + ReLU), the residual blocks' BodyA (+ ReLU) / BodyB (x 0.1 + block input),
-// Output (+ skip, NCHW); training's input gradients of a body (precision 0 or 2) / of the output convolution (capi_train.hip)
+// Output (+ skip, NCHW); training's input gradients of a body (any precision: 1 is the mixed-precision step of an fp32 model) /
+// of the output convolution (capi_train.hip)
 enum class ConvRole { First, BodyA, BodyB, Output, DgradBody, DgradOutput };
 enum class ConvKernel {
   Tile,       // conv3x3_mfma.hip: weights [slab][cc][tap][g][o][j] (dsen2_internal.h) with (kc, nt)

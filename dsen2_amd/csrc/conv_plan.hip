@@ -111,7 +111,6 @@ bool plan_conv(ConvRole role, int cin, int cout, int precision, const Tuning& tu
     case ConvRole::BodyB:
     case ConvRole::DgradBody:
       if (!feat_out || cin != cout) return false;
-      if (role == ConvRole::DgradBody && precision == 1) return false;     // training: fp32 and bf16x3 models
       pl.epilogue = role == ConvRole::BodyA ? kEpiRelu : kEpiResidual;
       pl.cin_pad = cin; pl.cout_pad = cout; pl.kc = 32; pl.nt = 128;     // every fp32 structure reads the same packing
       pl.kernel = precision == 1   ? ConvKernel::Body16

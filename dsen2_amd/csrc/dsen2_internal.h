@@ -206,6 +206,10 @@ hipError_t launch_conv3x3_wgrad(const float* a, int ca, const float* g, int cg, 
 size_t wgrad16_workspace_floats(int n, int h, int w, int feat);
 hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, int n, int h, int w, int feat, float scale, float* dw,
                                   float* db, float* ws, size_t ws_floats, hipStream_t stream);
+// The one-plane instance of that kernel (mixed-precision training): a and g are one-plane blocked bf16 tensors [n][F/8][h][w][8],
+// every product is the one bf16 MFMA a*g in fp32, db = scale * sum of the bf16 values of g.  Same workspace, same reduction.
+hipError_t launch_conv3x3_wgrad16_bf16(const void* a, const void* g, int n, int h, int w, int feat, float scale, float* dw, float* db,
+                                       float* ws, size_t ws_floats, hipStream_t stream);
 // keras mean_absolute_error over NCHW out / y ([n][c][h][w], c <= 16): loss2 = (mean |e|, mean e^2), gpad = dL/dout =
 // sign(e) / (n*c*h*w) as NHWC16 (channels >= c zero).  partial: mae_loss_partial_doubles(n*h*w) doubles of scratch.
 size_t mae_loss_partial_doubles(size_t pixels);
@@ -218,6 +222,9 @@ hipError_t launch_join3_f32(const void* hx, const void* lo, float* out_nhwc, int
 // du = t > 0 ? v : 0 written as a two-plane operand tensor [n][2][c/8][h][w][8] (hi = RNE bf16 of the value, lo = RNE bf16 of
 // value - hi): v fp32 NHWC, t a two-plane tensor (conv-A's output of a precision-2 model)
 hipError_t launch_mask_split3(const float* v_nhwc, const void* t_planes, void* du_planes, int n, int h, int w, int c, hipStream_t stream);
+// du = bf16(t > 0 ? v : 0), RNE (f32_to_bf16_rne's arithmetic), written as a one-plane blocked tensor [n][c/8][h][w][8]: v fp32
+// NHWC, t a one-plane blocked bf16 tensor (conv-A's output of a precision-1 plan)
+hipError_t launch_mask_round16(const float* v_nhwc, const void* t_plane, void* du_plane, int n, int h, int w, int c, hipStream_t stream);
 hipError_t launch_nadam(float* p, const float* g, float* m, float* v, size_t count, float lr, float b1, float b2, float eps,
                         float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, hipStream_t stream);
 // dst[i] = map[i] ? src[map[i] - 1] : 0   /   flat[map[i] - 1] = packed[i] where map[i] != 0

@@ -1,6 +1,6 @@
-// train_ops.hip — the memory-bound kernels of the training step (capi_train.hip): loss and dL/dout, ReLU-gradient masks,
-// the Nadam update and the device weight repack.  Every reduction runs in a fixed order (no float atomics): the same
-// inputs give the same bits on every run.
+// train_ops.hip — the memory-bound kernels of the training step (capi_train.hip): loss and dL/dout, ReLU-gradient masks
+// (fp32, and with the bf16x3 / bf16 operand tensor of du written in the same pass), the Nadam update and the device weight
+// repack.  Every reduction runs in a fixed order (no float atomics): the same inputs give the same bits on every run.
 #include "dsen2_internal.h"
 
 namespace dsen2 {
@@ -189,6 +189,24 @@ __global__ __launch_bounds__(256) void mask_split3_kernel(const float* __restric
   du[lo_at] = pack_halves(l);
 }
 
+// du = bf16_rne(t > 0 ? v : 0) as one plane; v fp32 NHWC, t and du [n][nblk][img_pix] pixels of 8 bf16 (launch_mask_round16)
+__global__ __launch_bounds__(256) void mask_round16_kernel(const float* __restrict__ v_nhwc, const uint4* __restrict__ t, uint4* __restrict__ du,
+                                                         size_t total, int img_pix, int nblk) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int blk = (int)(i % nblk);
+  const size_t pix = i / nblk, img = pix / img_pix, px = pix % img_pix;
+  const size_t at = (img * nblk + blk) * img_pix + px;
+  const uint4 tv = t[at];
+  const f32x4* src = reinterpret_cast<const f32x4*>(v_nhwc + (pix * nblk + blk) * 8);
+  const f32x4 a = src[0], b = src[1];
+  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  unsigned h[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) h[e] = bf16_rne(bf16_value(half_of(tv, e)) > 0.f ? v[e] : 0.f);
+  du[at] = pack_halves(h);
+}
+
 // one 32-bit word of a packed precision-2 buffer from the keras-flat values (launch_gather16)
 __device__ __forceinline__ unsigned gather16_half(const float* __restrict__ src, int entry) {
   if (entry == 0) return 0u;
@@ -253,6 +271,14 @@ hipError_t launch_mask_split3(const float* v_nhwc, const void* t_planes, void* d
   const size_t total = (size_t)n * h * w * (c / 8);
   hipLaunchKernelGGL(mask_split3_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, stream, v_nhwc,
                      reinterpret_cast<const uint4*>(t_planes), reinterpret_cast<uint4*>(du_planes), total, h * w, c / 8);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_round16(const float* v_nhwc, const void* t_plane, void* du_plane, int n, int h, int w, int c, hipStream_t stream) {
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 8 != 0 || c > 512) return hipErrorInvalidValue;
+  const size_t total = (size_t)n * h * w * (c / 8);
+  hipLaunchKernelGGL(mask_round16_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, stream, v_nhwc,
+                     reinterpret_cast<const uint4*>(t_plane), reinterpret_cast<uint4*>(du_plane), total, h * w, c / 8);
   return hipGetLastError();
 }
 

@@ -9,8 +9,11 @@ cooldown 20, min_lr 1e-5), best-only checkpointing on val_loss, shuffled epochs.
   <out>/<model_nr>_lr_<lr>.txt      one line per epoch: loss, val_loss, lr
 
 One GPU only.  --precision fp32 (default) trains in fp32; --precision bf16x3 runs the forward and the residual blocks' backward
-on the bf16 matrix cores with fp32-grade products (three bf16 MFMAs each); the master weights, the optimizer and the checkpoint
-stay fp32 either way, so a checkpoint loads into a model of any precision.
+on the bf16 matrix cores with fp32-grade products (three bf16 MFMAs each).  --mixed_precision bf16 (default off, fp32 models only:
+refused together with --precision bf16x3) is ordinary mixed-precision training: the step's convolutions run on bf16 operands with
+fp32 accumulation, the arithmetic `--precision bf16` inference uses (one bf16 MFMA per product, ~1e-3 relative error per
+convolution, no loss scaling: bf16 has fp32's exponent), while validation, the model and everything stored stay fp32.  The master
+weights, the optimizer and the checkpoint are fp32 in every case, so a checkpoint loads into a model of any precision.
 Data: <path>/train/*SAFE/{data10,data20,data20_gt}.npy (train60/ and data60, data60_gt with
 --run_60) and val_index.npy, as `python -m dsen2_amd.create_patches` and `python -m dsen2_amd.create_random` write them (the
 counterparts of training/create_patches.py and create_random.py, whose files it reads just the same).
@@ -50,7 +53,12 @@ def parse_args(argv=None):
     p.add_argument('--seed', type=int, default=None, help='Seed of the epoch shuffles.')
     p.add_argument('--precision', choices=('fp32', 'bf16x3'), default='fp32',
                    help='Arithmetic of the residual blocks while training (default fp32); checkpoints are fp32 either way.')
-    return p.parse_args(argv)
+    p.add_argument('--mixed_precision', choices=('bf16',), default=None,
+                   help='Run the training step of an fp32 model on bf16 operands, fp32 accumulate (default off; not with --precision bf16x3).')
+    args = p.parse_args(argv)
+    if args.mixed_precision is not None and args.precision != 'fp32':
+        p.error('--mixed_precision %s is an option of --precision fp32 (got --precision %s)' % (args.mixed_precision, args.precision))
+    return args
 
 
 def model_number(resume_file):
@@ -122,7 +130,7 @@ def main(argv=None):
                                                          seed=args.seed if args.seed is not None else 1))
         print('Model number is {}'.format(model_nr))
     model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
-                  loss='mean_absolute_error')
+                  loss='mean_absolute_error', mixed_precision=args.mixed_precision)
 
     print('Loading the training data...')
     train, label, val_tr, val_lb = training.load_training_data(path, args.run_60, training.SCALE)

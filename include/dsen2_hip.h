@@ -214,6 +214,25 @@ int dsen2_model_time_body_conv(dsen2_model *m, int layer, const float *dev_in, c
  * precision-2 model carries that copy until dsen2_model_destroy.
  * A precision-2 model without residual blocks (num_layers 0) is fp32 in every layer (dsen2_model_create) and trains exactly
  * as the precision-0 model of the same shape does.
+ * Mixed precision: dsen2_model_set_train_precision(m, 1) makes the training step of an fp32 (precision-0) model run on bf16
+ * operands with fp32 accumulation — the arithmetic of a precision-1 model — while the model itself, its master weights, the
+ * gradient, the optimizer state, dsen2_model_get_weights' vector and dsen2_model_forward stay fp32.  0 (the default) is the
+ * model's own arithmetic.  DSEN2_ERR_INVALID for a precision-1 or precision-2 handle and for any other value.  Changing the
+ * setting drops the training state and rebuilds it (the master copy comes back from the packed fp32 weights, exactly);
+ * dsen2_model_train_workspace_bytes and dsen2_model_gradients follow it.  With train precision 1:
+ *   - the state owns a precision-1 plan of the same network, whose packed buffers (what a precision-1 model of these weights
+ *     holds: weights rounded to bf16, round to nearest even) are rebuilt from the master vector after every
+ *     dsen2_model_set_weights_device / dsen2_model_load_weights, next to the model's own fp32 buffers;
+ *   - dev_out_or_NULL receives the forward of a precision-1 model with the same weights run layer by layer: the first
+ *     convolution on bf16(x), bf16(w) (round to nearest even); each block t = bf16(relu(convA(hi(x)) + b)) (nearest even),
+ *     x += 0.1 * (convB(t) + b) in fp32, hi(x) = the stream's operand plane (u + 0x8000) >> 16 of the fp32 bit pattern u
+ *     (nearest, ties away from zero); the output convolution in fp32;
+ *   - backward through the blocks, g = dL/dx in fp32: dWB = 0.1 * wgrad(t, hi(g)), dbB = 0.1 * sum hi(g),
+ *     du = bf16([t > 0] * 0.1 * dgradB(hi(g))) (nearest even), dWA = wgrad(hi(x), du), dbA = sum du, g += dgradA(du); every
+ *     product is one bf16 MFMA with fp32 accumulation.  bf16 has fp32's exponent range: no loss scaling.
+ *   - the loss, the output convolution's gradients and the first convolution's weight gradient (on the fp32 inputs, the
+ *     ReLU mask from the fp32 x_0) are the fp32 kernels'.
+ * Without residual blocks the setting changes nothing: such a plan is fp32 in every layer.
  *
  * dsen2_model_train_workspace_bytes: scratch dsen2_model_gradients needs for n patches of h x w (the saved activations
  *   x0 .. x_d and t_1 .. t_d, two gradient tensors, the weight-gradient partials; ~1 GB for DSen2 at 128 x 32 x 32).
@@ -239,6 +258,7 @@ int dsen2_model_train_workspace_bytes(const dsen2_model *m, int n, int h, int w,
 int dsen2_model_gradients(dsen2_model *m, const float *x10, const float *x20, const float *x60, const float *target,
                           float *dev_out_or_NULL, float *dev_grad_flat, float *dev_loss2, int n, int h, int w, void *ws,
                           size_t ws_bytes, void *stream);
+int dsen2_model_set_train_precision(dsen2_model *m, int precision);
 int dsen2_model_get_weights(const dsen2_model *m, float *dev_flat, void *stream);
 int dsen2_model_set_weights_device(dsen2_model *m, const float *dev_flat, void *stream);
 int dsen2_nadam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float b1, float b2, float eps,
@@ -249,10 +269,16 @@ int dsen2_conv3x3_wgrad(const float *dev_a, const float *dev_g, float *dev_dw, f
  *   cores, alone (kernel-level tests).  dev_a_planes / dev_g_planes are two-plane operand tensors [n][2][feat/8][h][w][8] bf16
  *   (value = plane 0 + plane 1: dsen2_split3_f32's dev_hx, epilogue 0's dev_out); every product is a0*g0 + a0*g1 + a1*g0 with
  *   fp32 accumulators.  dev_dw (3,3,feat,feat) HWIO, dev_db [feat], both times `scale`.  Allocates its scratch and synchronises.
+ * dsen2_conv3x3_wgrad_bf16: the one-plane instance of that kernel (mixed-precision training), alone: dev_a / dev_g are one-plane
+ *   blocked bf16 tensors [n][feat/8][h][w][8] (dsen2_split_f32's dev_hi, dsen2_conv3x3_body_bf16's epilogue-0 dev_out); every
+ *   product is one bf16 MFMA with fp32 accumulators; dev_db = scale * the sum of dev_g's bf16 values.  The same checks and
+ *   refusals as dsen2_conv3x3_wgrad_bf16x3.
  * dsen2_join3_f32: the exact inverse of dsen2_split3_f32: (dev_hx plane 0, dev_lo16) -> fp32 NHWC [n,h,w,c], bit for bit
  *   (plane 1, xl, is not read). */
 int dsen2_conv3x3_wgrad_bf16x3(const void *dev_a_planes, const void *dev_g_planes, float *dev_dw, float *dev_db, int n, int h,
                                int w, int feat, float scale, void *stream);
+int dsen2_conv3x3_wgrad_bf16(const void *dev_a, const void *dev_g, float *dev_dw, float *dev_db, int n, int h, int w, int feat,
+                             float scale, void *stream);
 int dsen2_join3_f32(const void *dev_hx, const void *dev_lo16, float *dev_out_nhwc, int n, int h, int w, int c, void *stream);
 
 /* ---- tiling / up-sampling / recomposition (utils/patches.py) --------------------------------

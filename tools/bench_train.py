@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fine-tuning speed: one JSON line per configuration.
 
-    python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N] [--precision fp32|bf16x3]
+    python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N] [--precision fp32|bf16x3] [--mixed_precision bf16]
 
   step_ms            one training step on device-resident data: dsen2_model_gradients + dsen2_nadam_step + the device repack
   train_on_batch_ms  S2Model.train_on_batch from host arrays (adds the H2D copies and the loss read-back)
@@ -11,6 +11,11 @@
                      `iters` launches through dsen2_conv3x3_wgrad's kernels on device buffers (2 * 9 * F^2 * n*h*w FLOP each)
 --precision bf16x3 trains a bf16x3 model: the weight-gradient kernel timed is then conv3x3_wgrad16.hip (dsen2_conv3x3_wgrad_bf16x3
 on two-plane operand tensors), counted at three MFMAs per product (3 * 2 * 9 * F^2 * n*h*w FLOP) against the bf16 MFMA peak.
+--mixed_precision bf16 (with --precision fp32) trains an fp32 model with compile(mixed_precision='bf16'): the step runs on bf16
+operands.  forward_ms stays the model's own fp32 forward; bf16_forward_ms (and step_over_bf16_forward) is dsen2_model_forward of
+a precision='bf16' model with the same weights: the arithmetic of the step's forward (inference may take the chain kernel where
+the step goes layer by layer).  The weight-gradient kernel timed is the one-plane instance of conv3x3_wgrad16.hip
+(dsen2_conv3x3_wgrad_bf16), one MFMA per product (2 * 9 * F^2 * n*h*w FLOP), against the bf16 MFMA peak.
 DSen2 runs at batch 128, VDSen2 at batch 8, both on 32 x 32 patches (training/supres_train.py's batch sizes).
 """
 import argparse
@@ -23,7 +28,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dsen2_amd import _lib, training, weights  # noqa: E402
-from dsen2_amd.DSen2Net import _ptr, _stream_ptr, s2model, split3_f32  # noqa: E402
+from dsen2_amd.DSen2Net import _ptr, _stream_ptr, bf16_plane_f32, s2model, split3_f32  # noqa: E402
 
 PEAK_TF = 157.3   # fp32 MFMA peak of the MI355X (MI355X_MICROARCH.md)
 PEAK_TF_BF16 = 2500.0   # dense bf16 MFMA peak
@@ -43,13 +48,13 @@ def timed(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters
 
 
-def run(name, iters, precision='fp32'):
+def run(name, iters, precision='fp32', mixed_precision=None):
     c = CONFIGS[name]
     d, F, n, h, w = c['d'], c['F'], c['batch'], 32, 32
     dev = torch.device('cuda', 0)
     m = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev, precision=precision)
     m.set_weights_flat(weights.random_he_uniform(10, 6, d, F, seed=1, bias_scale=0.05))
-    m.compile(training.Nadam(lr=1e-4))
+    m.compile(training.Nadam(lr=1e-4), mixed_precision=mixed_precision)
     rng = np.random.default_rng(0)
     xs = [rng.uniform(0, 0.5, (n, k, h, w)).astype(np.float32) for k in (4, 6)]
     y = rng.uniform(0, 0.5, (n, 6, h, w)).astype(np.float32)
@@ -63,6 +68,13 @@ def run(name, iters, precision='fp32'):
     step_ms = timed(step, iters)
     tob_ms = timed(lambda: m.train_on_batch(xs, y), max(2, iters // 2), warm=1)
     fwd_ms = timed(lambda: m.forward_device(xs_d), iters)
+    extra = {}
+    if mixed_precision == 'bf16':
+        b16 = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev, precision='bf16')
+        b16.set_weights_flat(m.get_weights_flat())
+        b16_ms = timed(lambda: b16.forward_device(xs_d), iters)
+        extra = dict(mixed_precision=mixed_precision, bf16_forward_ms=round(b16_ms, 4), step_over_bf16_forward=round(step_ms / b16_ms, 3))
+        del b16
 
     # the weight-gradient kernel of one body layer, through the library's launcher on preallocated buffers
     a = torch.from_numpy(rng.uniform(-1, 1, (n, h, w, F)).astype(np.float32)).to(dev)
@@ -71,11 +83,16 @@ def run(name, iters, precision='fp32'):
     db = torch.empty(F, device=dev)
 
     x3 = precision == 'bf16x3'
+    amp = mixed_precision == 'bf16'
     if x3:
         a, g = split3_f32(a)[0], split3_f32(g)[0]
+    if amp:
+        a, g = bf16_plane_f32(a), bf16_plane_f32(g)
 
     def wgrad():
-        if x3:
+        if amp:
+            _lib.call('dsen2_conv3x3_wgrad_bf16', _ptr(a), _ptr(g), _ptr(dw), _ptr(db), n, h, w, F, 1.0, _stream_ptr(dev))
+        elif x3:
             _lib.call('dsen2_conv3x3_wgrad_bf16x3', _ptr(a), _ptr(g), _ptr(dw), _ptr(db), n, h, w, F, 1.0, _stream_ptr(dev))
         else:
             _lib.call('dsen2_conv3x3_wgrad', _ptr(a), _ptr(g), _ptr(dw), _ptr(db), n, h, w, F, F, F, F, 1.0, _stream_ptr(dev))
@@ -84,11 +101,12 @@ def run(name, iters, precision='fp32'):
     # is given (profiles/); here: the call's wall time, an upper bound of the kernel time
     wg_ms = timed(wgrad, iters, warm=2)
     flop = (3.0 if x3 else 1.0) * 2.0 * 9 * F * F * n * h * w
-    peak = PEAK_TF_BF16 if x3 else PEAK_TF
+    peak = PEAK_TF_BF16 if x3 or amp else PEAK_TF
     res = dict(config=name, precision=precision, batch=n, h=h, w=w, num_layers=d, feature_size=F, step_ms=round(step_ms, 4),
                train_on_batch_ms=round(tob_ms, 4), forward_ms=round(fwd_ms, 4), step_over_forward=round(step_ms / fwd_ms, 3),
                patches_per_s=round(n / step_ms * 1e3, 1), wgrad_call_ms=round(wg_ms, 4),
                wgrad_tflops_lower_bound=round(flop / wg_ms / 1e9, 2), wgrad_fraction_of_peak_lower_bound=round(flop / wg_ms / 1e9 / peak, 4))
+    res.update(extra)
     print(json.dumps(res), flush=True)
 
 
@@ -97,9 +115,12 @@ def main():
     ap.add_argument('--config', default='both', choices=['dsen2', 'vdsen2', 'both'])
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3'])
+    ap.add_argument('--mixed_precision', default=None, choices=['bf16'])
     args = ap.parse_args()
+    if args.mixed_precision and args.precision != 'fp32':
+        ap.error('--mixed_precision is an option of --precision fp32')
     for name in (['dsen2', 'vdsen2'] if args.config == 'both' else [args.config]):
-        run(name, args.iters, args.precision)
+        run(name, args.iters, args.precision, args.mixed_precision)
 
 
 if __name__ == '__main__':
