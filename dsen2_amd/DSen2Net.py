@@ -579,6 +579,20 @@ def conv3x3_wgrad_bf16(a_plane, g_plane, scale=1.0):
     return dw, db
 
 
+WGRAD_KINDS = {'fp32': 0, 'bf16x3': 1, 'bf16': 2}
+
+
+def conv3x3_wgrad_geometry(kind, n, h, w, ca, cg=None):
+    """What a launch of a weight-gradient kernel does at a shape (include/dsen2_hip.h: dsen2_conv3x3_wgrad_geometry; host code,
+    needs no device).  kind 'fp32' (ca, cg as dsen2_conv3x3_wgrad takes them), 'bf16x3' or 'bf16' (ca = cg = feat).  Returns
+    (tiles, splits, workspace_floats): run s of the splits covers tiles [tiles * s // splits, tiles * (s + 1) // splits)."""
+    cg = ca if cg is None else cg
+    tiles, splits, floats = ctypes.c_longlong(0), ctypes.c_int(0), ctypes.c_size_t(0)
+    _lib.call('dsen2_conv3x3_wgrad_geometry', WGRAD_KINDS[kind], n, h, w, ca, cg, ctypes.byref(tiles), ctypes.byref(splits),
+              ctypes.byref(floats))
+    return tiles.value, splits.value, floats.value
+
+
 def conv3x3_first_planes(xs, kernel_hwio, bias, precision):
     """Kernel-level entry point of the first convolution of a 'bf16' (precision 1) / 'bf16x3' (2) model on the bf16 matrix
     cores (include/dsen2_hip.h: dsen2_conv3x3_first_planes).  xs: the two or three NCHW float32 CUDA inputs (4 + 6 (+ 2)

@@ -67,6 +67,8 @@ SIGNATURES = {
                                            c_void_p]),
     'dsen2_conv3x3_wgrad_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float,
                                          c_void_p]),
+    'dsen2_conv3x3_wgrad_geometry': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_longlong), c_int_p,
+                                             ctypes.POINTER(c_size_t)]),
     'dsen2_join3_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'dsen2_upsample_mirror_bilinear': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_float,
                                                c_void_p]),

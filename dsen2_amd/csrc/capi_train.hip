@@ -813,4 +813,22 @@ int dsen2_conv3x3_wgrad_bf16(const void* dev_a, const void* dev_g, float* dev_dw
   return conv3x3_wgrad16(1, dev_a, dev_g, dev_dw, dev_db, n, h, w, feat, scale, stream);
 }
 
+int dsen2_conv3x3_wgrad_geometry(int kind, int n, int h, int w, int ca, int cg, long long* tiles, int* splits,
+                                 size_t* workspace_floats) {
+  return guarded([&]() -> int {
+    if (!tiles || !splits || !workspace_floats) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if (kind < 0 || kind > 2) return fail(DSEN2_ERR_INVALID, "kind %d unsupported (0 fp32, 1 bf16x3, 2 bf16)", kind);
+    if (n <= 0 || h <= 0 || w <= 0) return fail(DSEN2_ERR_INVALID, "bad shape n=%d h=%d w=%d", n, h, w);
+    if (kind == 0) {
+      if (!wgrad_geometry(n, h, w, ca, cg, tiles, splits)) return fail(DSEN2_ERR_INVALID, "no wgrad kernel for %d -> %d channels", ca, cg);
+      *workspace_floats = wgrad_workspace_floats(n, h, w, ca, cg);
+    } else {
+      if (ca != cg || (cg != 128 && cg != 256)) return fail(DSEN2_ERR_INVALID, "feat %d -> %d unsupported (128 or 256)", ca, cg);
+      if (!wgrad16_geometry(n, h, w, cg, tiles, splits)) return fail(DSEN2_ERR_INVALID, "bad shape n=%d h=%d w=%d", n, h, w);
+      *workspace_floats = wgrad16_workspace_floats(n, h, w, cg);
+    }
+    return DSEN2_OK;
+  });
+}
+
 }  // extern "C"

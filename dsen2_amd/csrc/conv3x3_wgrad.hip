@@ -234,6 +234,14 @@ size_t wgrad_workspace_floats(int n, int h, int w, int ca, int cg) {
   return (size_t)g.splits * ((size_t)9 * g.cip * g.cop + (size_t)2 * g.cop);
 }
 
+bool wgrad_geometry(int n, int h, int w, int ca, int cg, long long* tiles, int* splits) {
+  WgradGeom g;
+  if (!wgrad_geom(n, h, w, ca, cg, &g)) return false;
+  *tiles = g.tiles;
+  *splits = g.splits;
+  return true;
+}
+
 hipError_t launch_conv3x3_wgrad(const float* a, int ca, const float* g, int cg, int n, int h, int w, int ci_real, int co_real,
                                 float scale, float* dw, float* db, float* ws, size_t ws_floats, hipStream_t stream) {
   WgradGeom geo;

@@ -284,6 +284,14 @@ size_t wgrad16_workspace_floats(int n, int h, int w, int feat) {
   return (size_t)g.splits * ((size_t)9 * feat * feat + (size_t)2 * feat);
 }
 
+bool wgrad16_geometry(int n, int h, int w, int feat, long long* tiles, int* splits) {
+  Wgrad16Geom g;
+  if (!wgrad16_geom(n, h, w, feat, &g)) return false;
+  *tiles = g.tiles;
+  *splits = g.splits;
+  return true;
+}
+
 namespace {
 
 template <int PL>

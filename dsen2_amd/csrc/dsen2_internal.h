@@ -198,12 +198,15 @@ hipError_t launch_recompose(const float* patches, int count, int C, int P, int b
 // cg <= 32 with ca % 128 == 0 (output layer); ca, cg multiples of 4.  ws: wgrad_workspace_floats() floats of split-K partials
 // (0 = shape not supported).  Fixed-order reduction: the same bits on every run.
 size_t wgrad_workspace_floats(int n, int h, int w, int ca, int cg);
+// what a launch at this shape does: the number of 4 x 16 pixel tiles and of split-K runs (false = shape not supported)
+bool wgrad_geometry(int n, int h, int w, int ca, int cg, long long* tiles, int* splits);
 hipError_t launch_conv3x3_wgrad(const float* a, int ca, const float* g, int cg, int n, int h, int w, int ci_real, int co_real,
                                 float scale, float* dw, float* db, float* ws, size_t ws_floats, hipStream_t stream);
 // The same for F -> F (F = 128, 256) as bf16x3 on the bf16 matrix cores (conv3x3_wgrad16.hip): a and g are two-plane blocked
 // operand tensors [n][2][F/8][h][w][8] bf16 (value = plane 0 + plane 1), every product a0*g0 + a0*g1 + a1*g0 in fp32; dw HWIO
 // (3,3,F,F), db[F].  Same split-K with a fixed-order reduction.
 size_t wgrad16_workspace_floats(int n, int h, int w, int feat);
+bool wgrad16_geometry(int n, int h, int w, int feat, long long* tiles, int* splits);
 hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, int n, int h, int w, int feat, float scale, float* dw,
                                   float* db, float* ws, size_t ws_floats, hipStream_t stream);
 // The one-plane instance of that kernel (mixed-precision training): a and g are one-plane blocked bf16 tensors [n][F/8][h][w][8],

@@ -279,6 +279,14 @@ int dsen2_conv3x3_wgrad_bf16x3(const void *dev_a_planes, const void *dev_g_plane
                                int w, int feat, float scale, void *stream);
 int dsen2_conv3x3_wgrad_bf16(const void *dev_a, const void *dev_g, float *dev_dw, float *dev_db, int n, int h, int w, int feat,
                              float scale, void *stream);
+/* dsen2_conv3x3_wgrad_geometry: what a launch of one of the three weight-gradient kernels does at a shape, computed on the host;
+ *   nothing is launched and no device is touched.  kind 0 = dsen2_conv3x3_wgrad (ca, cg as there), 1 = dsen2_conv3x3_wgrad_bf16x3,
+ *   2 = dsen2_conv3x3_wgrad_bf16 (ca = cg = feat).  *tiles = the number of 4 x 16 pixel tiles, n * ceil(h / 4) * ceil(w / 16);
+ *   *splits = the number of contiguous tile runs, run s = tiles [tiles * s / splits, tiles * (s + 1) / splits), one per workgroup
+ *   column; *workspace_floats = the floats of partial sums the launch needs, splits * (9 * cip * cop + 2 * cop) with the
+ *   channel counts padded to the kernel's (co, ci) block.  DSEN2_ERR_INVALID for a shape the kernel refuses. */
+int dsen2_conv3x3_wgrad_geometry(int kind, int n, int h, int w, int ca, int cg, long long *tiles, int *splits,
+                                 size_t *workspace_floats);
 int dsen2_join3_f32(const void *dev_hx, const void *dev_lo16, float *dev_out_nhwc, int n, int h, int w, int c, void *stream);
 
 /* ---- tiling / up-sampling / recomposition (utils/patches.py) --------------------------------

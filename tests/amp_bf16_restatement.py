@@ -171,7 +171,10 @@ CASES = [((4, 6), 2, 128, 2, 8, 8),
          ((4, 6, 2), 1, 128, 1, 8, 8),
          ((4, 6), 1, 256, 1, 9, 21),        # ragged, F = 256
          ((4, 6), 6, 128, 1, 4, 4),         # full depth: layer indexing
-         ((4, 6), 2, 128, 3, 20, 28)]       # several tiles and images
+         ((4, 6), 2, 128, 3, 20, 28),       # several tiles and images
+         # several tiles per split-K run of the weight-gradient kernels (tests/test_gpu_train_amp.py asserts the run lengths):
+         ((4, 6), 1, 128, 20, 21, 37),      # 360 tiles: more than 5 per run in the body layers, 1-2 in the first and output layer
+         ((4, 6), 1, 256, 3, 21, 37)]       # 54 tiles over the 16 splits of F = 256
 
 
 def he_uniform(cin, cout, d, F, seed=1, bias_scale=0.05):

@@ -29,7 +29,7 @@ for p in (ROOT, os.path.join(ROOT, 'tests')):
 
 import amp_bf16_restatement as R  # noqa: E402
 from dsen2_amd import _lib, training, weights  # noqa: E402
-from dsen2_amd.DSen2Net import _ptr, _stream_ptr, bf16_plane_f32, conv3x3_wgrad_bf16, s2model  # noqa: E402
+from dsen2_amd.DSen2Net import _ptr, _stream_ptr, bf16_plane_f32, conv3x3_wgrad_bf16, conv3x3_wgrad_geometry, s2model  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -117,8 +117,20 @@ def test_wgrad_bf16_kernel_against_numpy(n, h, w, F, gscale):
 
 
 # ---- 2. whole gradients where no ReLU mask and no loss sign can flip ----
+# case -> (tiles, the split counts of the bf16 body kernel and of the fp32 kernel in the first / output layer): the cases of
+# R.CASES where a split-K run of the weight-gradient kernels holds several tiles and one workspace serves the three in turn
+MULTI_RUN = {((4, 6), 1, 128, 20, 21, 37): (360, 64, 256, 256), ((4, 6), 1, 256, 3, 21, 37): (54, 16, 54, 54)}
+assert set(MULTI_RUN) <= set(R.CASES)
+
+
 @pytest.mark.parametrize('bands,d,F,n,h,w', R.CASES)
 def test_gradients_against_the_restatement_and_float64(bands, d, F, n, h, w):
+    if (bands, d, F, n, h, w) in MULTI_RUN:
+        tiles, s_body, s_first, s_out = MULTI_RUN[(bands, d, F, n, h, w)]
+        assert conv3x3_wgrad_geometry('bf16', n, h, w, F)[:2] == (tiles, s_body)
+        assert conv3x3_wgrad_geometry('fp32', n, h, w, 16, F)[:2] == (tiles, s_first)
+        assert conv3x3_wgrad_geometry('fp32', n, h, w, F, 16)[:2] == (tiles, s_out)
+        assert tiles // s_body >= 3 and tiles % s_body != 0
     err_r = R.check_preconditions(bands, d, F, n, h, w)
     flat, xs, y, s64, sr = R.case(bands, d, F, n, h, w)
     m, _ = _model(bands, d, F, flat=flat)

@@ -21,7 +21,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from dsen2_amd import _lib, training, weights  # noqa: E402
-from dsen2_amd.DSen2Net import _ptr, _stream_ptr, conv3x3_wgrad_bf16x3, join3_f32, s2model, split3_f32  # noqa: E402
+from dsen2_amd.DSen2Net import (_ptr, _stream_ptr, conv3x3_wgrad_bf16x3, conv3x3_wgrad_geometry, join3_f32, s2model,  # noqa: E402
+                                split3_f32)
 
 pytestmark = pytest.mark.gpu
 
@@ -215,8 +216,20 @@ def test_gradients_match_float64_autograd_where_no_mask_can_flip(bands, d, F, n,
 
 
 # ---- 4. real shapes: the tensors no mask touches, and no mis-indexed layer ----
-@pytest.mark.parametrize('bands,d,F,n,h,w', [((4, 6), 6, 128, 3, 20, 28), ((4, 6), 1, 256, 2, 16, 16)])
+# case -> (tiles, the split counts of the bf16x3 body kernel and of the fp32 kernel in the first / output layer): the whole step
+# where a split-K run of the weight-gradient kernels holds several tiles (more than 5 per run in the body layers, 1-2 in the
+# first and the output layer; 3-4 per run at F = 256) and one workspace serves the three layer kinds in turn
+MULTI_RUN = {((4, 6), 1, 128, 20, 21, 37): (360, 64, 256, 256), ((4, 6), 1, 256, 3, 21, 37): (54, 16, 54, 54)}
+
+
+@pytest.mark.parametrize('bands,d,F,n,h,w', [((4, 6), 6, 128, 3, 20, 28), ((4, 6), 1, 256, 2, 16, 16)] + list(MULTI_RUN))
 def test_gradients_at_real_shapes(bands, d, F, n, h, w):
+    if (bands, d, F, n, h, w) in MULTI_RUN:
+        tiles, s_body, s_first, s_out = MULTI_RUN[(bands, d, F, n, h, w)]
+        assert conv3x3_wgrad_geometry('bf16x3', n, h, w, F)[:2] == (tiles, s_body)
+        assert conv3x3_wgrad_geometry('fp32', n, h, w, 16, F)[:2] == (tiles, s_first)
+        assert conv3x3_wgrad_geometry('fp32', n, h, w, F, 16)[:2] == (tiles, s_out)
+        assert tiles // s_body >= 3 and tiles % s_body != 0
     xs, y, g64, loss64, mse64, _ = _reference(bands, d, F, n, h, w, 2)
     m, _ = _model(bands, d, F)
     m.compile()

@@ -1,6 +1,8 @@
-"""Fine-tuning, host side (no GPU): the Nadam scalar schedule, ReduceLROnPlateau, the data loader, save_weights -> load_flat
-and the training CLI's flags."""
+"""Fine-tuning, host side (no GPU): the Nadam scalar schedule, ReduceLROnPlateau, the data loader, save_weights -> load_flat,
+the training CLI's flags, and the weight-gradient kernels' geometry query (tiles, split count, workspace)."""
+import ctypes
 import os
+import re
 import subprocess
 import sys
 
@@ -154,3 +156,62 @@ def test_train_cli_refuses_data_parallel():
     r = subprocess.run([sys.executable, '-m', 'dsen2_amd.train', '--epochs', '1'], cwd=ROOT, capture_output=True, text=True,
                        timeout=120, env=env)
     assert r.returncode != 0 and 'WORLD_SIZE' in r.stderr
+
+
+# ---- dsen2_conv3x3_wgrad_geometry: the split-K geometry of the three weight-gradient kernels, without a device ----
+def test_wgrad_geometry_is_declared_exported_and_refuses_bad_arguments():
+    from dsen2_amd import _lib, build
+    build.build()
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, 'include', 'dsen2_hip.h')).read()
+    name = 'dsen2_conv3x3_wgrad_geometry'
+    assert re.search(r'\bint %s\s*\(' % name, header) and name in _lib.SIGNATURES and hasattr(lib, name)
+    tiles, splits, floats = ctypes.c_longlong(0), ctypes.c_int(0), ctypes.c_size_t(0)
+    out = [ctypes.byref(tiles), ctypes.byref(splits), ctypes.byref(floats)]
+
+    def refused(*args):
+        assert lib.dsen2_conv3x3_wgrad_geometry(*args) == _lib.ERR_INVALID
+        return lib.dsen2_last_error().decode()
+    for k in range(3):
+        args = list(out)
+        args[k] = None
+        assert 'NULL' in refused(0, 2, 16, 16, 128, 128, *args)
+    assert 'kind' in refused(3, 2, 16, 16, 128, 128, *out)
+    assert 'kind' in refused(-1, 2, 16, 16, 128, 128, *out)
+    assert 'bad shape' in refused(0, 0, 16, 16, 128, 128, *out)
+    assert 'bad shape' in refused(1, 2, 16, -1, 128, 128, *out)
+    assert 'no wgrad kernel' in refused(0, 2, 16, 16, 128, 64, *out)       # the fp32 kernel: cg % 128 == 0, or cg <= 32 with ca % 128 == 0
+    assert 'no wgrad kernel' in refused(0, 2, 16, 16, 16, 16, *out)
+    for kind in (1, 2):
+        assert 'unsupported' in refused(kind, 2, 16, 16, 64, 64, *out)
+        assert 'unsupported' in refused(kind, 2, 16, 16, 128, 256, *out)
+        assert 'unsupported' in refused(kind, 2, 16, 16, 16, 128, *out)     # the first layer stays on the fp32 kernel
+
+
+# (kind, ca, cg, cip, cop) -> the split count once there are enough tiles: 256 / the number of (co, ci) blocks.  The fp32
+# kernel's block is 128 co x 32 ci (body, first layer) or 32 co x 128 ci (output layer), the bf16 kernels' 128 co x 32 ci.
+WGRAD_SPLITS = [
+    ('fp32', 128, 128, 128, 128, 64), ('fp32', 256, 256, 256, 256, 16),         # body
+    ('fp32', 16, 128, 32, 128, 256), ('fp32', 16, 256, 32, 256, 128),           # first layer (NHWC16 input)
+    ('fp32', 128, 16, 128, 32, 256), ('fp32', 256, 16, 256, 32, 128),           # output layer (dL/dout padded to 16)
+    ('bf16x3', 128, 128, 128, 128, 64), ('bf16x3', 256, 256, 256, 256, 16),
+    ('bf16', 128, 128, 128, 128, 64), ('bf16', 256, 256, 256, 256, 16),
+]
+
+
+@pytest.mark.parametrize('kind,ca,cg,cip,cop,splits', WGRAD_SPLITS)
+def test_wgrad_geometry_pins_tiles_splits_and_workspace(kind, ca, cg, cip, cop, splits):
+    from dsen2_amd import build
+    from dsen2_amd.DSen2Net import conv3x3_wgrad_geometry
+    build.build()
+    # the timed shapes (32 x 32 patches, batch 128 and 8), ragged ones, one image wider than it is high, fewer tiles than splits
+    for n, h, w in ((128, 32, 32), (8, 32, 32), (9, 32, 32), (7, 21, 37), (19, 21, 37), (40, 32, 32), (2, 21, 37), (1, 8, 600),
+                    (3, 20, 28), (1, 1, 1), (1, 4, 16), (1, 5, 17)):
+        want_tiles = n * ((h + 3) // 4) * ((w + 15) // 16)
+        got_tiles, got_splits, floats = conv3x3_wgrad_geometry(kind, n, h, w, ca, cg)
+        assert got_tiles == want_tiles, (n, h, w)
+        assert got_splits == min(splits, want_tiles), (n, h, w)
+        assert floats == got_splits * (9 * cip * cop + 2 * cop), (n, h, w)
+    assert conv3x3_wgrad_geometry(kind, 128, 32, 32, ca, cg)[:2] == (2048, splits)      # DSen2, batch 128
+    assert conv3x3_wgrad_geometry(kind, 8, 32, 32, ca, cg)[:2] == (128, min(splits, 128))
+
