@@ -393,13 +393,113 @@ class S2Model(object):
             out.append(torch.from_numpy(a).to(self.device))
         return out
 
-    def train_on_batch(self, x, y):
+    # -- sharded steps: gradient accumulation on one GPU, data-parallel training on several ---------------------------------
+    def _shard_rows(self, k):
+        """[k, count + 2 (+ up to 3 floats of padding)] float32 device rows of a sharded step, kept with the training state: the
+        gradient, then loss2.  The padding makes the row length a multiple of 4 floats, here and after an all-gather, so that
+        dsen2_nadam_step_shards takes 16-byte accesses; it is never read."""
+        st = self._train_state()
+        count = st['flat'].numel()
+        rows = st.get('rows')
+        if rows is None or rows.shape[0] != k:
+            stride = -(-(count + 2) // 4) * 4
+            rows = st['rows'] = torch.empty((k, stride), dtype=torch.float32, device=self.device)
+        return rows
+
+    def nadam_update_shards(self, buf, counts, g_mean=None):
+        """One optimizer step on the count-weighted mean of the gradient vectors buf[r, :num_params] (float32 device rows, counts[r]
+        samples behind row r; a row whose count is 0 is never read), added in row order: dsen2_nadam_step_shards, then the device
+        repack.  The step of train_on_batch(shards=...) and of every rank of a data-parallel group alike.  g_mean (optional,
+        [num_params]) receives the averaged gradient."""
+        st = self._train_state()
+        count = st['flat'].numel()
+        counts = [int(c) for c in counts]
+        if buf.dim() != 2 or buf.shape[0] != len(counts) or buf.shape[1] < count or buf.dtype != torch.float32 or \
+                buf.device != self.device or buf.stride(1) != 1 or (len(counts) > 1 and buf.stride(0) < count):
+            raise ValueError('buf must hold %d float32 %s rows of at least %d values, got %r strides %r'
+                             % (len(counts), self.device, count, tuple(buf.shape), buf.stride()))
+        if g_mean is not None and (g_mean.numel() != count or g_mean.dtype != torch.float32 or not g_mean.is_contiguous() or
+                                   g_mean.device != self.device):
+            raise ValueError('g_mean must be a contiguous float32 %s tensor of %d values' % (self.device, count))
+        before = (self.optimizer.iterations, self.optimizer.m_schedule)
+        s = self.optimizer.next_step()
+        try:
+            with torch.cuda.device(self.device):
+                _lib.call('dsen2_nadam_step_shards', _ptr(st['flat']), _ptr(buf), max(buf.stride(0), count), len(counts),
+                          (ctypes.c_int * len(counts))(*counts), _ptr(g_mean), _ptr(st['m']), _ptr(st['v']), count,
+                          s['lr'], s['b1'], s['b2'], s['eps'], s['mc_t'], s['mc_t1'], s['ms_new'], s['ms_next'], s['b2_pow_t'],
+                          _stream_ptr(self.device))
+        except Exception:
+            self.optimizer.iterations, self.optimizer.m_schedule = before          # a refused call is not a step
+            raise
+        self.set_weights_device(st['flat'])
+
+    @staticmethod
+    def weighted_loss(loss2, counts):
+        """[sum n_r mae_r / n, sum n_r mse_r / n] in float64, added in shard order; a shard without samples is not read."""
+        total = float(sum(counts))
+        acc = [0.0, 0.0]
+        for l2, c in zip(loss2, counts):
+            if c > 0:
+                acc[0] += float(c) * float(l2[0])
+                acc[1] += float(c) * float(l2[1])
+        return [acc[0] / total, acc[1] / total]
+
+    def _step_on_shards(self, fetch, counts, mine=None):
+        """One step on a global batch cut into contiguous shards of counts[r] samples.  fetch(first, n) returns the host arrays
+        (x, y) of samples [first, first + n) of the batch.  mine = None: every shard is computed here, one after the other (gradient
+        accumulation; the one-process restatement of a data-parallel step).  mine = r: this process is rank r of a group of
+        len(counts) and computes shard r alone; the rows are all-gathered.  Either way the same rows reach the same kernel in the
+        same order.  Returns the count-weighted [loss, mean_squared_error] of the batch."""
+        from . import dist
+        count = self._train_state()['flat'].numel()
+        rows = self._shard_rows(len(counts) if mine is None else 1)
+        first = 0
+        for r, n in enumerate(counts):
+            if n > 0 and mine in (None, r):
+                x, y = fetch(first, n)
+                _, _, h, w = np.shape(x[0])
+                xs = self._to_device(x, [(n, c, h, w) for c in self.bands])
+                yd = self._to_device([y], [(n, self.cout, h, w)])[0]
+                row = rows[r if mine is None else 0]
+                self.gradients_device(xs, yd, row[:count], row[count:count + 2])
+            first += n
+        if mine is not None:
+            rows = dist.all_gather_rows(rows[0])
+        self.nadam_update_shards(rows, counts)
+        return self.weighted_loss(rows[:, count:count + 2].cpu().numpy().astype(np.float64), counts)
+
+    def _shard_counts(self, n, shards):
+        from . import dist
+        if isinstance(shards, (int, np.integer)):
+            if shards < 1:
+                raise ValueError('shards must be at least 1, got %d' % shards)
+            return [dist.shard_range(n, r, int(shards))[1] for r in range(int(shards))]
+        counts = [int(c) for c in shards]
+        if not counts or min(counts) < 0 or sum(counts) != n:
+            raise ValueError('the shard counts %r must be non-negative and add up to the batch of %d' % (counts, n))
+        return counts
+
+    def train_on_batch(self, x, y, shards=None):
         """keras Model.train_on_batch: one Nadam step on the batch; returns [loss, mean_squared_error] of the batch
-        before the step."""
+        before the step.
+        shards (default None: the whole batch in one pass): an integer k, or a list of counts that add up to the batch — the
+        batch is cut into contiguous shards (k: dist.shard_range's cut, the one a k-rank data-parallel run makes), each goes
+        through gradients_device on its own, and ONE step follows on the count-weighted mean of the shard gradients, added in
+        shard order in double (dsen2_nadam_step_shards).  Gradient accumulation: a global batch larger than the workspace allows;
+        and the exact one-process restatement of a data-parallel step.  shards=1 is the plain step, bit for bit; k > 1 differs
+        from it by the summation order only.  The losses returned are the count-weighted float64 means of the shards'."""
         st = self._train_state()
         if len(x) != len(self.bands):
             raise ValueError('expected %d inputs, got %d' % (len(self.bands), len(x)))
         n, _, h, w = np.shape(x[0])
+        if shards is not None:
+            counts = self._shard_counts(n, shards)
+            x = [np.ascontiguousarray(a, dtype=np.float32) for a in x]
+            y = np.ascontiguousarray(y, dtype=np.float32)
+            if y.shape != (n, self.cout, h, w) or any(a.shape != (n, c, h, w) for a, c in zip(x, self.bands)):
+                raise ValueError('inputs %r and target %r do not describe one batch' % ([a.shape for a in x], y.shape))
+            return self._step_on_shards(lambda first, m: ([a[first:first + m] for a in x], y[first:first + m]), counts)
         xs = self._to_device(x, [(n, c, h, w) for c in self.bands])
         yd = self._to_device([y], [(n, self.cout, h, w)])[0]
         self.gradients_device(xs, yd, st['grad'], st['loss2'])
@@ -416,12 +516,74 @@ class S2Model(object):
         e = pred.astype(np.float64) - y.astype(np.float64)
         return [float(np.mean(np.abs(e))), float(np.mean(e * e))]
 
+    def _evaluate_shards(self, x, y, batch_size, world, mine=None):
+        """[loss, mean_squared_error] over all samples as a data-parallel group of `world` ranks forms it: shard r =
+        dist.shard_range(n, r, world) of the samples is predicted on its own and gives float64 (sum |e|, sum e^2, elements) on the
+        host, as evaluate() forms them; the triples are added in rank order.  mine = None: every shard here, one after the other;
+        mine = r: shard r alone, the triples all-gathered.  The same number on every rank."""
+        from . import dist
+        y = np.asarray(y, dtype=np.float32)
+        n = y.shape[0]
+        triples = np.zeros((world, 3), np.float64)
+        for r in range(world):
+            if mine in (None, r):
+                first, cnt = dist.shard_range(n, r, world)
+                pred = self.predict([a[first:first + cnt] for a in x], batch_size=batch_size)
+                e = pred.astype(np.float64) - y[first:first + cnt].astype(np.float64)
+                triples[r] = (np.sum(np.abs(e)), np.sum(e * e), e.size)
+        if mine is not None:
+            triples = dist.all_gather_rows(torch.from_numpy(triples[mine]).to(self.device)).cpu().numpy()
+        sa = sq = cnt = 0.0
+        for t in triples:
+            sa, sq, cnt = sa + t[0], sq + t[1], cnt + t[2]
+        return [float(sa / cnt), float(sq / cnt)]
+
+    def _data_parallel_plan(self, data_parallel, emulate_world):
+        """None: the plain fit.  Else (world, mine): the sharded steps of a group of `world` ranks, as rank `mine` of the process
+        group, or (mine None, emulate_world) with every shard computed in this process.  Without either keyword the process
+        group is not looked at."""
+        if not data_parallel and emulate_world is None:
+            return None
+        from . import dist
+        rank, world = dist.rank_world()
+        if emulate_world is not None:
+            if not data_parallel or world > 1 or int(emulate_world) < 1:
+                raise ValueError('emulate_world restates a data-parallel run in ONE process: it needs data_parallel=True, a world '
+                                 'of at least 1 and no process group of more than one rank')
+            return (int(emulate_world), None) if int(emulate_world) > 1 else None
+        return (world, rank) if data_parallel and world > 1 else None
+
+    def _data_parallel_start(self, seed):
+        """Every rank continues from rank 0's weights and draws rank 0's permutations: the keras-flat vector and the shuffle seed
+        (drawn here on rank 0 when None) travel in one broadcast.  Returns the seed."""
+        from . import dist
+        rank, _ = dist.rank_world()
+        payload = None
+        if rank == 0:
+            if seed is None:
+                seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0] >> np.uint64(1))
+            payload = np.concatenate([self.get_weights_flat(), np.array([seed], np.uint64).view(np.float32)])
+        payload = dist.broadcast_weights(payload, self.count_params() + 2, device=self.device)
+        self.set_weights_flat(payload[:-2])
+        return int(payload[-2:].view(np.uint64)[0])
+
     def fit(self, x=None, y=None, batch_size=32, epochs=1, verbose=1, callbacks=None, validation_data=None, shuffle=True,
-            initial_epoch=0, seed=None):
+            initial_epoch=0, seed=None, data_parallel=False, emulate_world=None):
         """keras Model.fit: a fresh permutation each epoch when `shuffle`, the last partial batch kept, the epoch loss the
         sample-weighted mean of the batch losses.  Returns a training.History (loss, mean_squared_error, val_loss,
-        val_mean_squared_error, lr)."""
+        val_mean_squared_error, lr).
+        data_parallel=True under a torch.distributed process group of N > 1 ranks (dist.init_from_env): `batch_size` is the GLOBAL
+        batch; every rank holds all of x and y, starts from rank 0's weights and shuffle seed, computes the gradient of its
+        dist.shard_range share of each batch, all-gathers the gradient vectors and takes the same step on their count-weighted mean,
+        added in rank order (nadam_update_shards): the weights stay bit-identical on every rank, which is checked after every
+        epoch.  The validation set is sharded the same way and its float64 sums are added in rank order, so logs, callbacks and
+        stop_training act alike on every rank.  Without a group (or with one rank) it is the plain fit, as is data_parallel=False
+        always.  emulate_world=W (with data_parallel=True, one process): the same steps and validation sums with the W shards
+        computed here one after the other — what a W-rank run computes, bit for bit."""
         from . import training
+        plan = self._data_parallel_plan(data_parallel, emulate_world)
+        if plan is not None:
+            from . import dist
         x = [np.ascontiguousarray(a, dtype=np.float32) for a in x]
         y = np.ascontiguousarray(y, dtype=np.float32)
         count = y.shape[0]
@@ -433,6 +595,8 @@ class S2Model(object):
         for cb in callbacks:
             cb.set_model(self)
             cb.on_train_begin()
+        if plan is not None:
+            seed = self._data_parallel_start(seed)
         rng = np.random.default_rng(seed)
         self.stop_training = False
         for epoch in range(initial_epoch, epochs):
@@ -440,7 +604,11 @@ class S2Model(object):
             sums = np.zeros(2)
             for i0 in range(0, count, batch_size):
                 idx = order[i0:i0 + batch_size]
-                r = self.train_on_batch([a[idx] for a in x], y[idx])
+                if plan is None:
+                    r = self.train_on_batch([a[idx] for a in x], y[idx])
+                else:
+                    r = self._step_on_shards(lambda first, m: ([a[idx[first:first + m]] for a in x], y[idx[first:first + m]]),
+                                             self._shard_counts(len(idx), plan[0]), plan[1])
                 sums += np.asarray(r) * len(idx)
                 if verbose:
                     sys.stdout.write('\rEpoch %d/%d %d/%d loss %.4e' % (epoch + 1, epochs, min(i0 + batch_size, count), count,
@@ -448,7 +616,10 @@ class S2Model(object):
                     sys.stdout.flush()
             logs = {'loss': sums[0] / count, 'mean_squared_error': sums[1] / count}
             if validation_data is not None:
-                vl = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size)
+                if plan is None:
+                    vl = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size)
+                else:
+                    vl = self._evaluate_shards(validation_data[0], validation_data[1], batch_size, plan[0], plan[1])
                 logs['val_loss'], logs['val_mean_squared_error'] = vl
             logs['lr'] = self.optimizer.lr
             if verbose:
@@ -457,6 +628,8 @@ class S2Model(object):
             for cb in callbacks:
                 cb.on_epoch_end(epoch, logs)
             history.append(epoch, logs)
+            if plan is not None and plan[1] is not None:
+                dist.assert_replicas_identical(self._train['flat'])
             if self.stop_training:
                 break
         return history

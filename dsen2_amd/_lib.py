@@ -61,6 +61,8 @@ SIGNATURES = {
     'dsen2_model_get_weights': (c_int, [c_void_p, c_void_p, c_void_p]),
     'dsen2_model_set_weights_device': (c_int, [c_void_p, c_void_p, c_void_p]),
     'dsen2_nadam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t] + [ctypes.c_float] * 9 + [c_void_p]),
+    'dsen2_nadam_step_shards': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int_p, c_void_p, c_void_p, c_void_p, c_size_t] +
+                                [ctypes.c_float] * 9 + [c_void_p]),
     'dsen2_conv3x3_wgrad': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     ctypes.c_float, c_void_p]),
     'dsen2_conv3x3_wgrad_bf16x3': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float,

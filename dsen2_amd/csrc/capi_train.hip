@@ -773,6 +773,28 @@ int dsen2_nadam_step(float* p, const float* g, float* m, float* v, size_t count,
   });
 }
 
+int dsen2_nadam_step_shards(float* p, const float* dev_g_shards, size_t shard_stride, int shards, const int* host_counts,
+                            float* dev_g_mean, float* m, float* v, size_t count, float lr, float b1, float b2, float eps, float mc_t,
+                            float mc_t1, float ms_new, float ms_next, float b2_pow_t, void* stream) {
+  return guarded([&]() -> int {
+    if (!host_counts || (count > 0 && (!p || !dev_g_shards || !m || !v))) return fail(DSEN2_ERR_INVALID, "NULL argument");
+    if (shards < 1 || shards > kMaxShards) return fail(DSEN2_ERR_INVALID, "shards %d outside 1..%d", shards, kMaxShards);
+    if (shard_stride < count) return fail(DSEN2_ERR_INVALID, "shard_stride %zu < count %zu", shard_stride, count);
+    ShardCounts counts{};
+    long long total = 0;
+    for (int r = 0; r < shards; ++r) {
+      if (host_counts[r] < 0) return fail(DSEN2_ERR_INVALID, "negative sample count %d of shard %d", host_counts[r], r);
+      if (host_counts[r] >= (1 << 24)) return fail(DSEN2_ERR_INVALID, "sample count %d of shard %d is not below 2^24", host_counts[r], r);
+      counts.n[r] = host_counts[r];
+      total += host_counts[r];
+    }
+    if (total <= 0) return fail(DSEN2_ERR_INVALID, "the sample counts of the %d shards add up to zero", shards);
+    HIP_TRY(launch_nadam_shards(p, dev_g_shards, shard_stride, shards, counts, dev_g_mean, m, v, count, lr, b1, b2, eps, mc_t, mc_t1,
+                                ms_new, ms_next, b2_pow_t, (hipStream_t)stream));
+    return DSEN2_OK;
+  });
+}
+
 int dsen2_conv3x3_wgrad(const float* dev_a, const float* dev_g, float* dev_dw, float* dev_db, int n, int h, int w, int ca, int cg,
                         int ci, int co, float scale, void* stream) {
   return guarded([&]() -> int {

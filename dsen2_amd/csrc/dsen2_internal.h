@@ -230,6 +230,17 @@ hipError_t launch_mask_split3(const float* v_nhwc, const void* t_planes, void* d
 hipError_t launch_mask_round16(const float* v_nhwc, const void* t_plane, void* du_plane, int n, int h, int w, int c, hipStream_t stream);
 hipError_t launch_nadam(float* p, const float* g, float* m, float* v, size_t count, float lr, float b1, float b2, float eps,
                         float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, hipStream_t stream);
+// The data-parallel / gradient-accumulation step: g = (float)(sum over r, in order, of counts.n[r] * g_shards[r * shard_stride + i],
+// in double, / the sum of the counts), then launch_nadam's arithmetic on g; g_mean (or NULL) receives g.  A shard whose count is
+// 0 is never read.  The counts travel as a kernel argument.  The caller has checked the arguments (dsen2_nadam_step_shards:
+// shards in 1..kMaxShards, every count in [0, 2^24), a positive total, shard_stride >= count); nothing is checked again here.
+constexpr int kMaxShards = 64;
+struct ShardCounts {
+  int n[kMaxShards];
+};
+hipError_t launch_nadam_shards(float* p, const float* g_shards, size_t shard_stride, int shards, const ShardCounts& counts, float* g_mean,
+                               float* m, float* v, size_t count, float lr, float b1, float b2, float eps, float mc_t, float mc_t1,
+                               float ms_new, float ms_next, float b2_pow_t, hipStream_t stream);
 // dst[i] = map[i] ? src[map[i] - 1] : 0   /   flat[map[i] - 1] = packed[i] where map[i] != 0
 hipError_t launch_gather(float* dst, const float* src, const int* map, size_t n, hipStream_t stream);
 hipError_t launch_scatter(float* flat, const float* packed, const int* map, size_t n, hipStream_t stream);

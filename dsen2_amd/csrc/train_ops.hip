@@ -1,6 +1,7 @@
 // train_ops.hip — the memory-bound kernels of the training step (capi_train.hip): loss and dL/dout, ReLU-gradient masks
 // (fp32, and with the bf16x3 / bf16 operand tensor of du written in the same pass), the Nadam update and the device weight
-// repack.  Every reduction runs in a fixed order (no float atomics): the same inputs give the same bits on every run.
+// repack, and the count-weighted sum of sharded gradients with Nadam in one pass.  Every reduction runs in a fixed order (no
+// float atomics): the same inputs give the same bits on every run.
 #include "dsen2_internal.h"
 
 namespace dsen2 {
@@ -103,6 +104,71 @@ __global__ __launch_bounds__(256) void nadam_kernel(float* __restrict__ p, const
   p[i] = (float)((double)p[i] - (double)lr * mbar / (sqrt(vp) + (double)eps));
   m[i] = mt;
   v[i] = vt;
+}
+
+// nadam_kernel's arithmetic on one parameter, operation by operation, for a gradient already held in double
+struct NadamScalars {
+  float lr, b1, b2, eps, mc_t, mc_t1, ms_new, ms_next, b2_pow_t;
+};
+__device__ __forceinline__ void nadam_one(double gi, float& p, float& m, float& v, const NadamScalars& s) {
+  const double gp = gi / (1.0 - (double)s.ms_new);
+  const float mt = (float)((double)s.b1 * m + (1.0 - (double)s.b1) * gi);
+  const float vt = (float)((double)s.b2 * v + (1.0 - (double)s.b2) * gi * gi);
+  const double mp = (double)mt / (1.0 - (double)s.ms_next);
+  const double vp = (double)vt / (1.0 - (double)s.b2_pow_t);
+  const double mbar = (1.0 - (double)s.mc_t) * gp + (double)s.mc_t1 * mp;
+  p = (float)((double)p - (double)s.lr * mbar / (sqrt(vp) + (double)s.eps));
+  m = mt;
+  v = vt;
+}
+
+// The count-weighted mean of `shards` gradient vectors, added in shard order in double, and the Nadam update on it, one pass
+// (launch_nadam_shards).  A shard whose count is 0 is never read.  count * g is exact in double (count < 2^24), so an FMA and a
+// multiply followed by an add round alike.  W floats per access (W = 4: 16 bytes) on elements [0, W * units), the last count % W
+// elements by the first threads of block 0; W = 1: one element per unit.  One unit per thread: a grid capped at 2048 blocks ran
+// 10 % slower at VDSen2's 37.8 M parameters, the uncapped one at nadam_kernel's rate (profiles/train_data_parallel.md).  The
+// stride of the loop is a guard only: it keeps a count beyond kShardsMaxBlocks * 256 units (2^38) inside the grid's range.
+template <int W>
+__global__ __launch_bounds__(256) void nadam_shards_kernel(float* __restrict__ p, const float* __restrict__ g, size_t stride, int shards,
+                                                         ShardCounts counts, double total, float* __restrict__ g_mean,
+                                                         float* __restrict__ m, float* __restrict__ v, size_t count, NadamScalars s) {
+  typedef float vec __attribute__((ext_vector_type(W)));
+  const size_t units = count / W;
+  for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (size_t)gridDim.x * blockDim.x) {
+    double acc[W];
+#pragma unroll
+    for (int e = 0; e < W; ++e) acc[e] = 0.0;
+    for (int r = 0; r < shards; ++r) {
+      const int c = counts.n[r];
+      if (c <= 0) continue;
+      const vec a = reinterpret_cast<const vec*>(g + (size_t)r * stride)[u];
+#pragma unroll
+      for (int e = 0; e < W; ++e) acc[e] = acc[e] + (double)c * (double)a[e];
+    }
+    vec pv = reinterpret_cast<vec*>(p)[u], mv = reinterpret_cast<vec*>(m)[u], vv = reinterpret_cast<vec*>(v)[u], gm;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+      gm[e] = (float)(acc[e] / total);
+      float pe = pv[e], me = mv[e], ve = vv[e];
+      nadam_one((double)gm[e], pe, me, ve, s);
+      pv[e] = pe; mv[e] = me; vv[e] = ve;
+    }
+    if (g_mean) reinterpret_cast<vec*>(g_mean)[u] = gm;
+    reinterpret_cast<vec*>(p)[u] = pv;
+    reinterpret_cast<vec*>(m)[u] = mv;
+    reinterpret_cast<vec*>(v)[u] = vv;
+  }
+  if (W > 1 && blockIdx.x == 0 && units * W + threadIdx.x < count) {
+    const size_t i = units * W + threadIdx.x;
+    double acc = 0.0;
+    for (int r = 0; r < shards; ++r) {
+      const int c = counts.n[r];
+      if (c > 0) acc = acc + (double)c * (double)g[(size_t)r * stride + i];
+    }
+    const float gm = (float)(acc / total);
+    if (g_mean) g_mean[i] = gm;
+    nadam_one((double)gm, p[i], m[i], v[i], s);
+  }
 }
 
 // dst[i] = src[map[i] - 1], 0 where map[i] == 0 (padding)
@@ -227,6 +293,8 @@ __global__ __launch_bounds__(256) void gather16_kernel(unsigned* __restrict__ ds
 }
 
 unsigned blocks_for(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+constexpr int kShardsWide = 4;                      // floats per access of nadam_shards_kernel's wide form
+constexpr size_t kShardsMaxBlocks = (size_t)1 << 30;
 
 }  // namespace
 
@@ -296,6 +364,28 @@ hipError_t launch_nadam(float* p, const float* g, float* m, float* v, size_t cou
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(nadam_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, stream, p, g, m, v, count, lr, b1, b2, eps, mc_t,
                      mc_t1, ms_new, ms_next, b2_pow_t);
+  return hipGetLastError();
+}
+
+hipError_t launch_nadam_shards(float* p, const float* g_shards, size_t shard_stride, int shards, const ShardCounts& counts, float* g_mean,
+                               float* m, float* v, size_t count, float lr, float b1, float b2, float eps, float mc_t, float mc_t1,
+                               float ms_new, float ms_next, float b2_pow_t, hipStream_t stream) {
+  long long total = 0;
+  for (int r = 0; r < shards; ++r) total += counts.n[r];
+  if (count == 0) return hipSuccess;
+  const NadamScalars s{lr, b1, b2, eps, mc_t, mc_t1, ms_new, ms_next, b2_pow_t};
+  // 16-byte accesses need every vector's start on a 16-byte boundary: the bases and, for the shards, the stride
+  const uintptr_t bases = (uintptr_t)p | (uintptr_t)g_shards | (uintptr_t)g_mean | (uintptr_t)m | (uintptr_t)v;
+  const bool wide = bases % 16 == 0 && (shards == 1 || shard_stride % 4 == 0) && count >= (size_t)kShardsWide;
+  const size_t units = wide ? count / kShardsWide : count;
+  const size_t want = (units + 255) / 256;
+  const unsigned blocks = (unsigned)(want > kShardsMaxBlocks ? kShardsMaxBlocks : want);
+  if (wide)
+    hipLaunchKernelGGL(nadam_shards_kernel<kShardsWide>, dim3(blocks), dim3(256), 0, stream, p, g_shards, shard_stride, shards, counts,
+                       (double)total, g_mean, m, v, count, s);
+  else
+    hipLaunchKernelGGL(nadam_shards_kernel<1>, dim3(blocks), dim3(256), 0, stream, p, g_shards, shard_stride, shards, counts,
+                       (double)total, g_mean, m, v, count, s);
   return hipGetLastError();
 }
 

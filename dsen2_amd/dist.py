@@ -1,11 +1,15 @@
 """Patch sharding across the GPUs of one node: one process per GPU, torch.distributed over RCCL.
 
-The forward pass has no exchange step (patches are independent), so there are exactly two
+The forward pass has no exchange step (patches are independent), so inference has exactly two
 collectives and neither is on the per-layer path:
   C1  broadcast_weights : rank 0 reads the checkpoint once, everyone receives the flat float32 vector
                           (7.16 MB DSen2, 151 MB VDSen2) with one broadcast
   C2  gather_to_root    : each rank's (inner-cropped) predictions go to rank 0 with ONE gather into views of one
                           pre-sized buffer (the "gather of outputs over xGMI"); no other rank receives anything
+Data-parallel training (S2Model.fit(data_parallel=True)) adds one per step:
+  C3  all_gather_rows   : every rank's gradient vector (+ its two loss values) to every rank, in rank order; the sum is NOT the
+                          library's (an all-reduce's order belongs to its ring): dsen2_nadam_step_shards adds the rows in rank
+                          order, so every rank computes the same bits.  assert_replicas_identical checks that they did.
 Partitioning: contiguous ranges of the row-major patch index, ceil(N/R) per rank (last ranks may be
 short or empty).  With backend "nccl" (= RCCL on ROCm) tensors stay on the GPU; with "gloo" (CPU tests)
 they are staged through host memory.
@@ -211,6 +215,41 @@ def gather_to_root(send, total, dst=0):
         return out if out.device == send.device else out.to(send.device)
     td.gather(src, None, dst=dst)
     return None
+
+
+def all_gather_rows(send):
+    """C3, the exchange of a data-parallel training step: every rank passes a 1-D tensor of the same length and dtype (its gradient
+    vector followed by its two loss values) and every rank returns the [world, length] tensor of all of them, in rank order, on
+    `send`'s device.  RCCL: one all_gather_into_tensor on the device; gloo: staged through host memory.  A single process
+    returns send[None] (a view)."""
+    _, world = rank_world()
+    if world == 1:
+        return send[None]
+    assert send.dim() == 1, tuple(send.shape)
+    cdev = _collective_device(send)
+    src = (send if send.device == cdev else send.to(cdev)).contiguous()
+    recv = torch.empty(world * src.numel(), dtype=src.dtype, device=cdev)       # flat: the form both backends take
+    td.all_gather_into_tensor(recv, src)
+    recv = recv.view(world, src.numel())
+    return recv if recv.device == send.device else recv.to(send.device)
+
+
+def weights_checksum(flat):
+    """The int64 sum of the int32 view of a float32 tensor: a checksum of the weights' BITS (any one flipped bit changes it)."""
+    return flat.contiguous().view(torch.int32).sum(dtype=torch.int64).reshape(1)
+
+
+def assert_replicas_identical(flat):
+    """Every rank holds the same float32 vector `flat`, by weights_checksum: the checksums are all-gathered, and EVERY rank
+    raises RuntimeError naming the first rank that differs from rank 0 when one does."""
+    rank, world = rank_world()
+    if world == 1:
+        return
+    sums = all_gather_rows(weights_checksum(flat))[:, 0].cpu().tolist()
+    bad = [r for r in range(world) if sums[r] != sums[0]]
+    if bad:
+        raise RuntimeError('data-parallel replicas have diverged: the weights of rank %d differ from rank 0 (bit checksums %s; '
+                           'this is rank %d)' % (bad[0], sums, rank))
 
 
 def chunk_bounds(per, chunks):

@@ -8,7 +8,7 @@ cooldown 20, min_lr 1e-5), best-only checkpointing on val_loss, shuffled epochs.
                                     in place of a missing .hdf5 of the same name)
   <out>/<model_nr>_lr_<lr>.txt      one line per epoch: loss, val_loss, lr
 
-One GPU only.  --precision fp32 (default) trains in fp32; --precision bf16x3 runs the forward and the residual blocks' backward
+One GPU unless --data_parallel is given (below).  --precision fp32 (default) trains in fp32; --precision bf16x3 runs the forward and the residual blocks' backward
 on the bf16 matrix cores with fp32-grade products (three bf16 MFMAs each).  --mixed_precision bf16 (default off, fp32 models only:
 refused together with --precision bf16x3) is ordinary mixed-precision training: the step's convolutions run on bf16 operands with
 fp32 accumulation, the arithmetic `--precision bf16` inference uses (one bf16 MFMA per product, ~1e-3 relative error per
@@ -17,6 +17,17 @@ weights, the optimizer and the checkpoint are fp32 in every case, so a checkpoin
 Data: <path>/train/*SAFE/{data10,data20,data20_gt}.npy (train60/ and data60, data60_gt with
 --run_60) and val_index.npy, as `python -m dsen2_amd.create_patches` and `python -m dsen2_amd.create_random` write them (the
 counterparts of training/create_patches.py and create_random.py, whose files it reads just the same).
+
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N -m dsen2_amd.train --data_parallel [--backend nccl|gloo] ...
+trains on N GPUs, one process each (S2Model.fit(data_parallel=True)): --batch_size is the GLOBAL batch, of which every rank
+takes its dist.shard_range share; the ranks all-gather their gradient vectors and take the same step on the count-weighted mean,
+added in rank order, so every rank holds the same weights bit for bit and an N-rank run writes the files a one-process run of
+fit(data_parallel=True, emulate_world=N) writes, byte for byte.  --resume is read by rank 0 alone; the checkpoint, the epoch log
+and the progress line are rank 0's; ReduceLROnPlateau runs on every rank, on identical numbers.  Every rank loads the whole
+training set into host memory (a global permutation can ask any rank for any sample), and the all-gather is not overlapped with
+the backward pass.  --backend gloo rehearses the control flow with ranks sharing GPUs.  Without --data_parallel a launch with
+WORLD_SIZE > 1 is refused; with it, a single process trains exactly as without.  --data_parallel --emulate_world N in a single
+process is fit(data_parallel=True, emulate_world=N): the N-rank run restated on one GPU (its files, without its speed).
 
     python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] --path P
 is that script's predict branch: for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
@@ -55,7 +66,15 @@ def parse_args(argv=None):
                    help='Arithmetic of the residual blocks while training (default fp32); checkpoints are fp32 either way.')
     p.add_argument('--mixed_precision', choices=('bf16',), default=None,
                    help='Run the training step of an fp32 model on bf16 operands, fp32 accumulate (default off; not with --precision bf16x3).')
+    p.add_argument('--data_parallel', action='store_true',
+                   help='Data-parallel training under torch.distributed.run: one process per GPU, --batch_size is the global batch.')
+    p.add_argument('--backend', choices=('nccl', 'gloo'), default='nccl',
+                   help='Collectives of --data_parallel: nccl (RCCL, default) or gloo (a rehearsal with ranks sharing GPUs).')
+    p.add_argument('--emulate_world', type=int, default=None, metavar='N',
+                   help='With --data_parallel in ONE process: compute what an N-rank run computes, bit for bit, shard after shard.')
     args = p.parse_args(argv)
+    if args.emulate_world is not None and (not args.data_parallel or args.emulate_world < 1):
+        p.error('--emulate_world N (N >= 1) restates a --data_parallel run in one process: pass --data_parallel too')
     if args.mixed_precision is not None and args.precision != 'fp32':
         p.error('--mixed_precision %s is an option of --precision fp32 (got --precision %s)' % (args.mixed_precision, args.precision))
     return args
@@ -96,11 +115,25 @@ def predict(model, args, path):
 
 def main(argv=None):
     args = parse_args(argv)
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.stderr.write('dsen2_amd.train runs on one GPU: data-parallel training (WORLD_SIZE > 1) is not supported\n')
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    if world > 1 and not (args.data_parallel and not args.predict_file and args.emulate_world is None):
+        sys.stderr.write('dsen2_amd.train runs on one GPU: data-parallel training (WORLD_SIZE > 1) is not supported unless asked '
+                         'for: pass --data_parallel (training only)\n')
         return 2
+    rank = 0
+    if args.data_parallel and world > 1:
+        from . import dist
+        rank, world, _ = dist.init_from_env(args.backend)        # before anything touches HIP
+    rc = run(args, rank, world)
+    if args.data_parallel and world > 1:
+        dist.finalize()                # barrier, then leave the group (a rank that raised skips the barrier: its peers are
+    return rc                          # stuck in a collective, and torch.distributed.run ends them; as dsen2_amd.cli does)
+
+
+def run(args, rank, world):
     from . import training
     from .DSen2Net import s2model
+    say = print if rank == 0 else (lambda *a, **k: None)      # one rank talks
 
     path = args.path if args.path.endswith('/') else args.path + '/'
     if args.predict_file:
@@ -108,7 +141,8 @@ def main(argv=None):
         return predict(s2model(bands, num_layers=32 if args.deep else 6, feature_size=256 if args.deep else 128,
                                precision=args.precision), args, path)
     out = args.out if args.out is not None else path + 'network_data/'
-    os.makedirs(out, exist_ok=True)
+    if rank == 0:
+        os.makedirs(out, exist_ok=True)
     bands = ((4, None, None), (6, None, None), (2, None, None)) if args.run_60 else ((4, None, None), (6, None, None))
     if args.deep:
         model = s2model(bands, num_layers=32, feature_size=256, precision=args.precision)
@@ -120,25 +154,31 @@ def main(argv=None):
         batch_size = args.batch_size
     model_nr = MODEL_NR
     if args.resume_file:
-        print('Will resume from the weights {}'.format(args.resume_file))
-        model.load_weights(args.resume_file)
+        say('Will resume from the weights {}'.format(args.resume_file))
+        if world > 1:
+            from . import dist
+            model.set_weights_flat(dist.load_weights_on_root(args.resume_file, model.cin, model.cout, model.num_layers,
+                                                             model.feature_size, device=model.device))
+        else:
+            model.load_weights(args.resume_file)
         model_nr = model_number(args.resume_file)
-        print('Changing the model number to: {}'.format(model_nr))
+        say('Changing the model number to: {}'.format(model_nr))
     else:
         from . import weights
         model.set_weights_flat(weights.random_he_uniform(model.cin, model.cout, model.num_layers, model.feature_size,
                                                          seed=args.seed if args.seed is not None else 1))
-        print('Model number is {}'.format(model_nr))
+        say('Model number is {}'.format(model_nr))
     model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
                   loss='mean_absolute_error', mixed_precision=args.mixed_precision)
 
-    print('Loading the training data...')
+    say('Loading the training data...')
     train, label, val_tr, val_lb = training.load_training_data(path, args.run_60, training.SCALE)
-    print('Loaded {} patches for training, {} for validation.'.format(label.shape[0], val_lb.shape[0]))
+    say('Loaded {} patches for training, {} for validation.'.format(label.shape[0], val_lb.shape[0]))
 
     ckpt = os.path.join(out, model_nr + 'lr_{:.0e}.npy'.format(args.lr))
     log_path = os.path.join(out, model_nr + '_lr_{:.1e}.txt'.format(args.lr))
-    open(log_path, 'w').close()
+    if rank == 0:
+        open(log_path, 'w').close()
 
     class EpochLog(training.Callback):
         def on_epoch_end(self, epoch, logs=None):
@@ -146,13 +186,15 @@ def main(argv=None):
                 f.write('Finished epoch {:5d}: loss {:.3e}, valid: {:.3e}, lr: {:.1e}\n'
                         .format(epoch, logs.get('loss'), logs.get('val_loss'), self.model.optimizer.lr))
 
-    callbacks = [training.ModelCheckpoint(ckpt, monitor='val_loss', verbose=1, save_best_only=True), EpochLog(),
-                 training.ReduceLROnPlateau(monitor='val_loss', factor=0.5, patience=5, verbose=1, min_delta=1e-6,
-                                            cooldown=20, min_lr=1e-5)]
-    print('Training starts...')
-    model.fit(x=train, y=label, batch_size=batch_size, epochs=args.epochs, verbose=1, callbacks=callbacks,
-              validation_data=(val_tr, val_lb), shuffle=True, seed=args.seed)
-    print('best weights: {}\nlog: {}'.format(ckpt, log_path))
+    # the files and the progress line are rank 0's; the learning-rate schedule runs everywhere, on identical numbers
+    files = [training.ModelCheckpoint(ckpt, monitor='val_loss', verbose=1, save_best_only=True), EpochLog()] if rank == 0 else []
+    callbacks = files + [training.ReduceLROnPlateau(monitor='val_loss', factor=0.5, patience=5, verbose=int(rank == 0), min_delta=1e-6,
+                                                    cooldown=20, min_lr=1e-5)]
+    say('Training starts...')
+    model.fit(x=train, y=label, batch_size=batch_size, epochs=args.epochs, verbose=int(rank == 0), callbacks=callbacks,
+              validation_data=(val_tr, val_lb), shuffle=True, seed=args.seed, data_parallel=args.data_parallel,
+              emulate_world=args.emulate_world)
+    say('best weights: {}\nlog: {}'.format(ckpt, log_path))
     return 0
 
 

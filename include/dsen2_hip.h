@@ -250,6 +250,19 @@ int dsen2_model_time_body_conv(dsen2_model *m, int layer, const float *dev_in, c
  *     ms_next = ms_new * mc_t1,  b2_pow_t = b2^t;
  *   g' = g / (1 - ms_new), m = b1 m + (1 - b1) g, m' = m / (1 - ms_next), v = b2 v + (1 - b2) g^2, v' = v / (1 - b2_pow_t),
  *   p -= lr ((1 - mc_t) g' + mc_t1 m') / (sqrt(v') + eps).
+ * dsen2_nadam_step_shards: the step of data-parallel training and of gradient accumulation: the count-weighted mean of `shards`
+ *   gradient vectors and dsen2_nadam_step on it, in one pass.  dev_g_shards holds the vectors, `count` floats each, vector r at
+ *   dev_g_shards + r * shard_stride (shard_stride >= count, in floats); host_counts[r] >= 0 (host memory, copied into the launch:
+ *   it may be reused at once) is the number of samples behind vector r, total = their sum > 0.  Per parameter i, in this order:
+ *     acc = 0 (double);  for r = 0 .. shards-1 with host_counts[r] > 0:  acc = acc + (double)host_counts[r] * (double)g_r[i];
+ *     g = (float)(acc / (double)total);  then dsen2_nadam_step's arithmetic on g.
+ *   The order is fixed, so the same inputs give the same bits on every run and on every rank of a data-parallel group.  A count
+ *   below 2^24 times a float is exact in double, so a fused multiply-add and a multiply followed by an add round alike.  With one
+ *   shard acc / total is g_0[i] for any count: the call is dsen2_nadam_step, bit for bit.  A vector whose count is 0 is never
+ *   read: its slot may hold anything.  dev_g_mean_or_NULL [count] receives g.  dev_g_shards is not modified.  16-byte accesses
+ *   are used when every pointer is 16-byte aligned and (with more than one shard) shard_stride is a multiple of 4; any other
+ *   alignment and stride gives the same bits, more slowly.  DSEN2_ERR_INVALID, nothing launched: shards outside 1..64, a negative
+ *   count, a count >= 2^24, a zero total, shard_stride < count, a NULL pointer.
  * dsen2_conv3x3_wgrad: the weight-gradient kernel alone (kernel-level tests): dev_dw (3,3,ci,co) = scale * sum over all pixels
  *   of a[p + tap][c] g[p][o], dev_db [co] = scale * sum g[p][o]; dev_a NHWC [n,h,w,ca], dev_g NHWC [n,h,w,cg]; ci <= ca, co <= cg.
  *   Shapes: cg a multiple of 128 (ca a multiple of 4), or cg <= 32 with ca a multiple of 128.  Allocates its scratch and
@@ -263,6 +276,9 @@ int dsen2_model_get_weights(const dsen2_model *m, float *dev_flat, void *stream)
 int dsen2_model_set_weights_device(dsen2_model *m, const float *dev_flat, void *stream);
 int dsen2_nadam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float b1, float b2, float eps,
                      float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, void *stream);
+int dsen2_nadam_step_shards(float *p, const float *dev_g_shards, size_t shard_stride, int shards, const int *host_counts,
+                            float *dev_g_mean_or_NULL, float *m, float *v, size_t count, float lr, float b1, float b2, float eps,
+                            float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, void *stream);
 int dsen2_conv3x3_wgrad(const float *dev_a, const float *dev_g, float *dev_dw, float *dev_db, int n, int h, int w, int ca,
                         int cg, int ci, int co, float scale, void *stream);
 /* dsen2_conv3x3_wgrad_bf16x3: the weight gradient of a feat -> feat convolution (feat = 128, 256) as bf16x3 on the bf16 matrix

@@ -2,6 +2,7 @@
 """Fine-tuning speed: one JSON line per configuration.
 
     python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N] [--precision fp32|bf16x3] [--mixed_precision bf16]
+                                [--shards K [K ...]]
 
   step_ms            one training step on device-resident data: dsen2_model_gradients + dsen2_nadam_step + the device repack
   train_on_batch_ms  S2Model.train_on_batch from host arrays (adds the H2D copies and the loss read-back)
@@ -16,6 +17,9 @@ operands.  forward_ms stays the model's own fp32 forward; bf16_forward_ms (and s
 a precision='bf16' model with the same weights: the arithmetic of the step's forward (inference may take the chain kernel where
 the step goes layer by layer).  The weight-gradient kernel timed is the one-plane instance of conv3x3_wgrad16.hip
 (dsen2_conv3x3_wgrad_bf16), one MFMA per product (2 * 9 * F^2 * n*h*w FLOP), against the bf16 MFMA peak.
+--shards K ...: beside the plain step, shards_step_ms[K] = the same global batch as K shards on device-resident data (K x
+dsen2_model_gradients at batch / K, one dsen2_nadam_step_shards, the repack: what train_on_batch(shards=K) and one rank-local
+batch of a K-rank data-parallel run cost in kernel efficiency), and train_on_batch_shards_ms[K] from host arrays.
 DSen2 runs at batch 128, VDSen2 at batch 8, both on 32 x 32 patches (training/supres_train.py's batch sizes).
 """
 import argparse
@@ -48,7 +52,7 @@ def timed(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters
 
 
-def run(name, iters, precision='fp32', mixed_precision=None):
+def run(name, iters, precision='fp32', mixed_precision=None, shards=()):
     c = CONFIGS[name]
     d, F, n, h, w = c['d'], c['F'], c['batch'], 32, 32
     dev = torch.device('cuda', 0)
@@ -69,11 +73,26 @@ def run(name, iters, precision='fp32', mixed_precision=None):
     tob_ms = timed(lambda: m.train_on_batch(xs, y), max(2, iters // 2), warm=1)
     fwd_ms = timed(lambda: m.forward_device(xs_d), iters)
     extra = {}
+    count = m.count_params()
+    for k in shards:
+        counts = m._shard_counts(n, k)
+        firsts = np.cumsum([0] + counts)
+        rows = m._shard_rows(k)
+
+        def shard_step():
+            for r, c in enumerate(counts):
+                if c:
+                    f = int(firsts[r])
+                    m.gradients_device([t[f:f + c] for t in xs_d], y_d[f:f + c], rows[r, :count], rows[r, count:count + 2])
+            m.nadam_update_shards(rows, counts)
+        extra.setdefault('shards_step_ms', {})[str(k)] = round(timed(shard_step, iters), 4)
+        extra.setdefault('train_on_batch_shards_ms', {})[str(k)] = round(timed(lambda: m.train_on_batch(xs, y, shards=k),
+                                                                                  max(2, iters // 2), warm=1), 4)
     if mixed_precision == 'bf16':
         b16 = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev, precision='bf16')
         b16.set_weights_flat(m.get_weights_flat())
         b16_ms = timed(lambda: b16.forward_device(xs_d), iters)
-        extra = dict(mixed_precision=mixed_precision, bf16_forward_ms=round(b16_ms, 4), step_over_bf16_forward=round(step_ms / b16_ms, 3))
+        extra.update(mixed_precision=mixed_precision, bf16_forward_ms=round(b16_ms, 4), step_over_bf16_forward=round(step_ms / b16_ms, 3))
         del b16
 
     # the weight-gradient kernel of one body layer, through the library's launcher on preallocated buffers
@@ -116,11 +135,12 @@ def main():
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3'])
     ap.add_argument('--mixed_precision', default=None, choices=['bf16'])
+    ap.add_argument('--shards', type=int, nargs='+', default=[], help='also time the step as K shards of the same global batch')
     args = ap.parse_args()
     if args.mixed_precision and args.precision != 'fp32':
         ap.error('--mixed_precision is an option of --precision fp32')
     for name in (['dsen2', 'vdsen2'] if args.config == 'both' else [args.config]):
-        run(name, args.iters, args.precision, args.mixed_precision)
+        run(name, args.iters, args.precision, args.mixed_precision, args.shards)
 
 
 if __name__ == '__main__':
