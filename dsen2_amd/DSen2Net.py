@@ -30,6 +30,63 @@ def _stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+# -- the 8 flips and rotations of a patch (include/dsen2_hip.h, "dihedral") ------------------------------------------------------
+# op = k + 4 f: D_op(a) = np.rot90(a[..., ::-1] if f else a, k, axes=(-2, -1)); odd k swaps H and W.
+def ensemble_mask(ensemble):
+    """The 8-bit member mask of dsen2_model_forward_ensemble: False / None -> 0 (no ensemble), True -> 255 (all 8 members), an
+    iterable of ops 0..7 -> their bits."""
+    if ensemble is None or ensemble is False:
+        return 0
+    if ensemble is True:
+        return 255
+    mask = 0
+    for op in ensemble:
+        if int(op) != op or not 0 <= int(op) <= 7:
+            raise ValueError('an ensemble member must be an op 0..7, got %r' % (op,))
+        mask |= 1 << int(op)
+    if mask == 0:
+        raise ValueError('an ensemble needs at least one member')
+    return mask
+
+
+def dihedral(x, op=None, ops=None, inverse=False, out=None):
+    """D_op(x), or D_op^-1(x) when `inverse`, of a contiguous float32 CUDA tensor [n, c, h, w] (dsen2_dihedral_nchw): one op for
+    the whole tensor (`op`, 0..7), or one per sample (`ops`: n values 0..7, a sequence or an int32 CUDA tensor; square images
+    only).  Returns `out` (allocated when None): [n, c, w, h] for odd op & 3."""
+    if not torch.cuda.is_available():
+        raise RuntimeError('dsen2_amd needs a ROCm GPU (gfx950); there is no CPU fallback')
+    if (op is None) == (ops is None):
+        raise ValueError('give either op (one for the tensor) or ops (one per sample)')
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError('x must be a contiguous float32 CUDA tensor [n, c, h, w], got %r %s %s' % (tuple(x.shape), x.dtype, x.device))
+    n, c, h, w = x.shape
+    ops_dev = None
+    if ops is not None:
+        if h != w:
+            raise ValueError('per-sample ops need square images (an odd rotation swaps H and W), got %dx%d' % (h, w))
+        if isinstance(ops, torch.Tensor):
+            ops_dev = ops
+        else:
+            host = np.ascontiguousarray(ops, dtype=np.int32)
+            if host.size and (host.min() < 0 or host.max() > 7):
+                raise ValueError('ops must be 0..7, got %r' % (host.tolist(),))
+            ops_dev = torch.from_numpy(host).to(x.device)
+        if tuple(ops_dev.shape) != (n,) or ops_dev.dtype != torch.int32 or not ops_dev.is_contiguous() or ops_dev.device != x.device:
+            raise ValueError('ops must hold one int32 per sample (%d) on %s' % (n, x.device))
+        op = 0
+    elif int(op) != op or not 0 <= int(op) <= 7:
+        raise ValueError('op must be 0..7, got %r' % (op,))
+    shape = (n, c, w, h) if int(op) & 1 else (n, c, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError('out must be a contiguous float32 %s tensor of shape %r, got %r %s' % (x.device, shape, tuple(out.shape), out.dtype))
+    with torch.cuda.device(x.device):
+        _lib.call('dsen2_dihedral_nchw', _ptr(x), _ptr(out), n, c, h, w, int(op), _ptr(ops_dev), int(bool(inverse)),
+                  _stream_ptr(x.device))
+    return out
+
+
 class S2Model(object):
     """What keras' Model is to the reference: built by s2model(), then load_weights() and predict()."""
 
@@ -76,9 +133,15 @@ class S2Model(object):
     def load_weights(self, path):
         self.set_weights_flat(_weights.load_flat(path, self.cin, self.cout, self.num_layers, self.feature_size))
 
-    def workspace_bytes(self, n, h, w):
+    def workspace_bytes(self, n, h, w, ensemble=False):
+        """Scratch of one forward of n patches of h x w; ensemble (True, or the member ops): of the self-ensemble forward, which
+        also holds the turned inputs and one member's output."""
         out = ctypes.c_size_t(0)
-        _lib.call('dsen2_model_workspace_bytes', self._handle, n, h, w, ctypes.byref(out))
+        mask = ensemble_mask(ensemble)
+        if mask:
+            _lib.call('dsen2_model_ensemble_workspace_bytes', self._handle, n, h, w, mask, ctypes.byref(out))
+        else:
+            _lib.call('dsen2_model_workspace_bytes', self._handle, n, h, w, ctypes.byref(out))
         return out.value
 
     def _get_workspace(self, nbytes):
@@ -116,6 +179,30 @@ class S2Model(object):
         with torch.cuda.device(self.device):
             _lib.call('dsen2_model_forward', self._handle, _ptr(xs[0]), _ptr(xs[1]),
                       _ptr(xs[2]) if len(xs) == 3 else ctypes.c_void_p(0), _ptr(out), n, h, w,
+                      _ptr(ws), ws.numel(), _stream_ptr(self.device))
+        return out
+
+    def forward_device_ensemble(self, xs, out=None, ops=range(8)):
+        """The geometric self-ensemble of one batch on the device (dsen2_model_forward_ensemble): the mean over the member ops
+        (default all 8) of D_op^-1(forward(D_op xs)), members in ascending op order, summed in fp32, then divided by their number.
+        ops=[0] is forward_device bit for bit.  xs and out as forward_device."""
+        ops = list(range(8)) if ops is True else list(ops)
+        mask = ensemble_mask(ops)
+        if len(xs) != len(self.bands):
+            raise ValueError('expected %d inputs, got %d' % (len(self.bands), len(xs)))
+        n, _, h, w = xs[0].shape
+        for x, c in zip(xs, self.bands):
+            if tuple(x.shape) != (n, c, h, w) or x.dtype != torch.float32 or not x.is_contiguous() or \
+                    x.device != self.device:
+                raise ValueError('input must be a contiguous float32 %s tensor of shape %r, got %r %s %s'
+                                 % (self.device, (n, c, h, w), tuple(x.shape), x.dtype, x.device))
+        out = self._check_out(out, n, h, w)
+        if n == 0:
+            return out
+        ws = self._get_workspace(self.workspace_bytes(n, h, w, ensemble=ops))
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_model_forward_ensemble', self._handle, _ptr(xs[0]), _ptr(xs[1]),
+                      _ptr(xs[2]) if len(xs) == 3 else ctypes.c_void_p(0), _ptr(out), n, h, w, mask,
                       _ptr(ws), ws.numel(), _stream_ptr(self.device))
         return out
 
@@ -169,29 +256,35 @@ class S2Model(object):
             raise _lib.DSen2Error(r, _lib.load().dsen2_last_error().decode())
         return r
 
-    def batch_limit(self, h, w):
-        per = self.workspace_bytes(1, h, w)
+    def batch_limit(self, h, w, ensemble=False):
+        per = self.workspace_bytes(1, h, w, ensemble=ensemble)
         return max(1, int(self.max_workspace_bytes // per))
 
-    def preferred_batch(self, h, w):
+    def preferred_batch(self, h, w, ensemble=False):
         """The batch the tile path and predict() cut their work into: batch_limit() for fp32 and for large patches; in the
         bf16 modes, for patches the chain kernel takes (up to 64 x 64: there it is 1-3 % ahead of the per-layer launches and
         bit-identical to them; profiles/r04_k_chain_vs_layerwise.txt), the largest batch below the limit that runs ALL
         residual-block convolutions in one chain launch (body_launches() == 1: a multiple of the CU count).  Results never
-        depend on the batch size."""
-        limit = self.batch_limit(h, w)
+        depend on the batch size.  ensemble (True, or the member ops): the same under the self-ensemble's larger workspace, the
+        chain launch asked of the turned orientation as well."""
+        # (off: the two-argument call, as before — a stand-in for batch_limit need not know the keyword)
+        limit = self.batch_limit(h, w, ensemble=ensemble) if ensemble_mask(ensemble) else self.batch_limit(h, w)
         if self.precision == 'fp32' or self.num_layers <= 0:
             return limit
+        turned = h != w and ensemble_mask(ensemble) & 0xAA       # an odd rotation among the members: w x h forwards too
         cus = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
         n = (limit // cus) * cus
         while n >= cus:
-            if self.body_launches(n, h, w) == 1:
+            if self.body_launches(n, h, w) == 1 and (not turned or self.body_launches(n, w, h) == 1):
                 return n
             n -= cus
         return limit
 
-    def predict(self, x, batch_size=None, verbose=0):
+    def predict(self, x, batch_size=None, verbose=0, ensemble=False):
         """keras Model.predict: list of NCHW float32 ndarrays -> ndarray [N, cout, H, W].
+
+        ``ensemble`` (not in keras; default off): True, or an iterable of ops 0..7 — every batch goes through
+        forward_device_ensemble, the geometric self-ensemble over those members (True: all 8), at about as many times the cost.
 
         ``batch_size`` only bounds device memory (results do not depend on it); default: as many
         patches as fit ``max_workspace_bytes``.  Host<->device copies go through page-locked buffers on their own
@@ -206,7 +299,12 @@ class S2Model(object):
         for a, c in zip(xs, self.bands):
             if a.shape != (n, c, h, w):
                 raise ValueError('input of shape %r where %r is expected' % (a.shape, (n, c, h, w)))
-        bs = self.preferred_batch(h, w) if batch_size is None else int(batch_size)
+        mask = ensemble_mask(ensemble if isinstance(ensemble, bool) or ensemble is None else list(ensemble))
+        members = [op for op in range(8) if (mask >> op) & 1]
+        if batch_size is not None:
+            bs = int(batch_size)
+        else:
+            bs = self.preferred_batch(h, w, ensemble=members) if members else self.preferred_batch(h, w)
         out = np.empty((n, self.cout, h, w), np.float32)
         if n == 0:
             return self._progress_end(verbose, out)
@@ -247,7 +345,10 @@ class S2Model(object):
                         slot['dev_in'][k][:m].copy_(slot['pin_in'][k][:m], non_blocking=True)
                     slot['ev_in'].record(h2d)
                 comp.wait_event(slot['ev_in'])
-                self.forward_device([t[:m] for t in slot['dev_in']], out=slot['dev_out'][:m])
+                if members:
+                    self.forward_device_ensemble([t[:m] for t in slot['dev_in']], out=slot['dev_out'][:m], ops=members)
+                else:
+                    self.forward_device([t[:m] for t in slot['dev_in']], out=slot['dev_out'][:m])
                 slot['ev_comp'].record(comp)
                 with torch.cuda.stream(d2h):
                     d2h.wait_event(slot['ev_comp'])
@@ -445,12 +546,32 @@ class S2Model(object):
                 acc[1] += float(c) * float(l2[1])
         return [acc[0] / total, acc[1] / total]
 
-    def _step_on_shards(self, fetch, counts, mine=None):
+    @staticmethod
+    def _check_augment_ops(augment_ops, n, h, w):
+        """One op 0..7 per sample of the batch as an int32 array (None stays None: no augmentation)."""
+        if augment_ops is None:
+            return None
+        ops = np.ascontiguousarray(augment_ops, dtype=np.int32)
+        if ops.shape != (n,) or (n and (ops.min() < 0 or ops.max() > 7)):
+            raise ValueError('augment_ops must hold one op 0..7 for each of the %d samples, got %r' % (n, np.asarray(augment_ops).tolist()))
+        if h != w:
+            raise ValueError('augmentation turns every sample by its own op: it needs square patches, got %dx%d' % (h, w))
+        return ops
+
+    def _augment_device(self, tensors, ops):
+        """Every tensor [n, c, h, w] turned sample by sample: D_ops[s] of sample s (ops None: as they are)."""
+        if ops is None:
+            return tensors
+        ops_dev = torch.from_numpy(ops).to(self.device)
+        return [dihedral(t, ops=ops_dev) for t in tensors]
+
+    def _step_on_shards(self, fetch, counts, mine=None, augment_ops=None):
         """One step on a global batch cut into contiguous shards of counts[r] samples.  fetch(first, n) returns the host arrays
         (x, y) of samples [first, first + n) of the batch.  mine = None: every shard is computed here, one after the other (gradient
         accumulation; the one-process restatement of a data-parallel step).  mine = r: this process is rank r of a group of
         len(counts) and computes shard r alone; the rows are all-gathered.  Either way the same rows reach the same kernel in the
-        same order.  Returns the count-weighted [loss, mean_squared_error] of the batch."""
+        same order.  augment_ops (or None): the checked ops of the GLOBAL batch, sliced like the samples.  Returns the
+        count-weighted [loss, mean_squared_error] of the batch."""
         from . import dist
         count = self._train_state()['flat'].numel()
         rows = self._shard_rows(len(counts) if mine is None else 1)
@@ -461,6 +582,8 @@ class S2Model(object):
                 _, _, h, w = np.shape(x[0])
                 xs = self._to_device(x, [(n, c, h, w) for c in self.bands])
                 yd = self._to_device([y], [(n, self.cout, h, w)])[0]
+                if augment_ops is not None:
+                    *xs, yd = self._augment_device(xs + [yd], self._check_augment_ops(augment_ops[first:first + n], n, h, w))
                 row = rows[r if mine is None else 0]
                 self.gradients_device(xs, yd, row[:count], row[count:count + 2])
             first += n
@@ -480,9 +603,13 @@ class S2Model(object):
             raise ValueError('the shard counts %r must be non-negative and add up to the batch of %d' % (counts, n))
         return counts
 
-    def train_on_batch(self, x, y, shards=None):
+    def train_on_batch(self, x, y, shards=None, augment_ops=None):
         """keras Model.train_on_batch: one Nadam step on the batch; returns [loss, mean_squared_error] of the batch
         before the step.
+        augment_ops (default None: the data as given): one op 0..7 per sample (include/dsen2_hip.h, "dihedral": a flip and / or a
+        rotation by a multiple of 90 degrees); the inputs and the target of sample s are turned by D_ops[s] on the device after the
+        upload — the step is bit for bit the step on data turned on the host.  Square patches only.  With shards, every shard
+        takes its slice of the ops.
         shards (default None: the whole batch in one pass): an integer k, or a list of counts that add up to the batch — the
         batch is cut into contiguous shards (k: dist.shard_range's cut, the one a k-rank data-parallel run makes), each goes
         through gradients_device on its own, and ONE step follows on the count-weighted mean of the shard gradients, added in
@@ -493,15 +620,18 @@ class S2Model(object):
         if len(x) != len(self.bands):
             raise ValueError('expected %d inputs, got %d' % (len(self.bands), len(x)))
         n, _, h, w = np.shape(x[0])
+        ops = self._check_augment_ops(augment_ops, n, h, w)
         if shards is not None:
             counts = self._shard_counts(n, shards)
             x = [np.ascontiguousarray(a, dtype=np.float32) for a in x]
             y = np.ascontiguousarray(y, dtype=np.float32)
             if y.shape != (n, self.cout, h, w) or any(a.shape != (n, c, h, w) for a, c in zip(x, self.bands)):
                 raise ValueError('inputs %r and target %r do not describe one batch' % ([a.shape for a in x], y.shape))
-            return self._step_on_shards(lambda first, m: ([a[first:first + m] for a in x], y[first:first + m]), counts)
+            return self._step_on_shards(lambda first, m: ([a[first:first + m] for a in x], y[first:first + m]), counts,
+                                        augment_ops=ops)
         xs = self._to_device(x, [(n, c, h, w) for c in self.bands])
         yd = self._to_device([y], [(n, self.cout, h, w)])[0]
+        *xs, yd = self._augment_device(xs + [yd], ops)
         self.gradients_device(xs, yd, st['grad'], st['loss2'])
         self.nadam_update(st['grad'])
         loss = st['loss2'].cpu().numpy().astype(np.float64)
@@ -568,7 +698,7 @@ class S2Model(object):
         return int(payload[-2:].view(np.uint64)[0])
 
     def fit(self, x=None, y=None, batch_size=32, epochs=1, verbose=1, callbacks=None, validation_data=None, shuffle=True,
-            initial_epoch=0, seed=None, data_parallel=False, emulate_world=None):
+            initial_epoch=0, seed=None, data_parallel=False, emulate_world=None, augment=False):
         """keras Model.fit: a fresh permutation each epoch when `shuffle`, the last partial batch kept, the epoch loss the
         sample-weighted mean of the batch losses.  Returns a training.History (loss, mean_squared_error, val_loss,
         val_mean_squared_error, lr).
@@ -579,7 +709,12 @@ class S2Model(object):
         epoch.  The validation set is sharded the same way and its float64 sums are added in rank order, so logs, callbacks and
         stop_training act alike on every rank.  Without a group (or with one rank) it is the plain fit, as is data_parallel=False
         always.  emulate_world=W (with data_parallel=True, one process): the same steps and validation sums with the W shards
-        computed here one after the other — what a W-rank run computes, bit for bit."""
+        computed here one after the other — what a W-rank run computes, bit for bit.
+        augment=True (default off; square patches): every training sample of every step is flipped and / or rotated by a
+        multiple of 90 degrees, inputs and target alike, on the device (train_on_batch(augment_ops=...)).  The ops of a step are
+        training.AugmentOps(seed).draw(batch): a generator derived from `seed` but separate from the shuffle's, so the
+        permutations are those of the un-augmented fit.  Under data_parallel every rank draws the ops of the GLOBAL batch from
+        the broadcast seed and takes its shard's slice.  Validation is never augmented."""
         from . import training
         plan = self._data_parallel_plan(data_parallel, emulate_world)
         if plan is not None:
@@ -598,17 +733,19 @@ class S2Model(object):
         if plan is not None:
             seed = self._data_parallel_start(seed)
         rng = np.random.default_rng(seed)
+        aug = training.AugmentOps(seed) if augment else None
         self.stop_training = False
         for epoch in range(initial_epoch, epochs):
             order = rng.permutation(count) if shuffle else np.arange(count)
             sums = np.zeros(2)
             for i0 in range(0, count, batch_size):
                 idx = order[i0:i0 + batch_size]
+                ops = aug.draw(len(idx)) if aug is not None else None
                 if plan is None:
-                    r = self.train_on_batch([a[idx] for a in x], y[idx])
+                    r = self.train_on_batch([a[idx] for a in x], y[idx], augment_ops=ops)
                 else:
                     r = self._step_on_shards(lambda first, m: ([a[idx[first:first + m]] for a in x], y[idx[first:first + m]]),
-                                             self._shard_counts(len(idx), plan[0]), plan[1])
+                                             self._shard_counts(len(idx), plan[0]), plan[1], augment_ops=ops)
                 sums += np.asarray(r) * len(idx)
                 if verbose:
                     sys.stdout.write('\rEpoch %d/%d %d/%d loss %.4e' % (epoch + 1, epochs, min(i0 + batch_size, count), count,

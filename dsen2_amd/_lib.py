@@ -35,6 +35,11 @@ SIGNATURES = {
     'dsen2_model_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                     c_void_p, c_size_t, c_void_p]),
     'dsen2_model_body_launches': (c_int, [c_void_p, c_int, c_int, c_int]),
+    'dsen2_dihedral_nchw': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'dsen2_dihedral_accumulate': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'dsen2_model_ensemble_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    'dsen2_model_forward_ensemble': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_size_t, c_void_p]),
     'dsen2_model_forward_timed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                           c_void_p, c_size_t, c_void_p, c_int, c_float_p]),
     'dsen2_model_forward_profile': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -367,6 +367,111 @@ static int recompose_rows(const float* dev_patches, int count, int C, int P, int
   return DSEN2_OK;
 }
 
+// ---- flips and rotations, the geometric self-ensemble --------------------------------------------------------------------------
+// the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
+static bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + b_bytes && y < x + a_bytes;
+}
+
+// the one argument check of dsen2_dihedral_nchw / dsen2_dihedral_accumulate; *elems = n * c * h * w
+static int check_dihedral_args(const void* in, const void* out, int n, int c, int h, int w, int op, size_t* elems) {
+  if (!in || !out) return fail(DSEN2_ERR_INVALID, "NULL argument");
+  if (n < 0 || c <= 0 || h <= 0 || w <= 0) return fail(DSEN2_ERR_INVALID, "bad shape n=%d c=%d h=%d w=%d", n, c, h, w);
+  if (op < 0 || op > 7) return fail(DSEN2_ERR_INVALID, "op %d outside 0..7", op);
+  *elems = (size_t)n * c * h * w;
+  if (*elems >= ((size_t)1 << 31)) return fail(DSEN2_ERR_INVALID, "tensor of %zu elements (2^31 or more)", *elems);
+  if (*elems > 0 && overlaps(in, *elems * sizeof(float), out, *elems * sizeof(float))) return fail(DSEN2_ERR_INVALID, "the output aliases the input");
+  return DSEN2_OK;
+}
+
+namespace {
+// The ensemble's workspace: the forward's | the turned inputs | one member's output (the last two only where a member other
+// than the plain forward is asked for).
+struct EnsembleWs {
+  char* fwd = nullptr;
+  size_t fwd_bytes = 0;
+  float *x10 = nullptr, *x20 = nullptr, *x60 = nullptr, *y = nullptr;
+  size_t bytes = 0;
+};
+}  // namespace
+
+static EnsembleWs ensemble_ws(const dsen2_model* m, int n, int h, int w, int mask, char* base) {
+  const size_t pix = (size_t)n * h * w;
+  EnsembleWs r;
+  r.fwd = base;
+  r.fwd_bytes = forward_ws(m, n, h, w, nullptr).bytes;       // (a function of n * h * w: the same for h x w and w x h)
+  size_t off = r.fwd_bytes / sizeof(float);
+  auto take = [&](size_t floats) -> float* {
+    float* p = base ? reinterpret_cast<float*>(base) + off : nullptr;
+    off += align_up(floats);
+    return p;
+  };
+  if (mask & ~1) {
+    r.x10 = take(pix * m->c10);
+    r.x20 = take(pix * m->c20);
+    if (m->c60 > 0) r.x60 = take(pix * m->c60);
+    r.y = take(pix * m->cout);
+  }
+  r.bytes = off * sizeof(float);
+  return r;
+}
+
+static int check_ensemble_shape(const dsen2_model* m, int n, int h, int w, int mask) {
+  if (mask <= 0 || mask > 255) return fail(DSEN2_ERR_INVALID, "ensemble mask %d outside 1..255", mask);
+  if (int rc = check_shape(m, n, h, w)) return rc;
+  if (int rc = check_shape(m, n, w, h)) return rc;           // the turned orientation
+  int cmax = m->cout;
+  for (int c : {m->c10, m->c20, m->c60}) cmax = c > cmax ? c : cmax;
+  if ((size_t)n * h * w * cmax >= ((size_t)1 << 31))
+    return fail(DSEN2_ERR_INVALID, "batch of %d images of %dx%d: a tensor of 2^31 elements or more", n, h, w);
+  return DSEN2_OK;
+}
+
+static int forward_ensemble(dsen2_model* m, const float* x10, const float* x20, const float* x60, float* out, int n, int h, int w,
+                            int mask, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!m || !x10 || !x20 || !out || !workspace) return fail(DSEN2_ERR_INVALID, "NULL argument");
+  if ((m->c60 > 0) != (x60 != nullptr)) return fail(DSEN2_ERR_INVALID, "x60 must be given iff the model has a 60 m input");
+  if (mask <= 0 || mask > 255) return fail(DSEN2_ERR_INVALID, "ensemble mask %d outside 1..255", mask);
+  if (n == 0) return DSEN2_OK;
+  if (!m->loaded) return fail(DSEN2_ERR_NO_WEIGHTS, "dsen2_model_load_weights has not been called");
+  if (int rc = check_ensemble_shape(m, n, h, w, mask)) return rc;
+  if (int rc = check_device(m)) return rc;
+  const size_t pix = (size_t)n * h * w;
+  const float* const ins[3] = {x10, x20, x60};
+  const int cs[3] = {m->c10, m->c20, m->c60};
+  for (int k = 0; k < 3; ++k)
+    if (ins[k] && overlaps(ins[k], pix * cs[k] * sizeof(float), out, pix * m->cout * sizeof(float)))
+      return fail(DSEN2_ERR_INVALID, "the output aliases an input");
+  const EnsembleWs E = ensemble_ws(m, n, h, w, mask, reinterpret_cast<char*>(workspace));
+  if (workspace_bytes < E.bytes) return fail(DSEN2_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, E.bytes);
+  hipStream_t stream = (hipStream_t)stream_;
+  int count = 0;
+  for (int op = 0; op < 8; ++op) count += (mask >> op) & 1;
+  int done = 0;
+  for (int op = 0; op < 8; ++op) {
+    if (!((mask >> op) & 1)) continue;
+    const bool first = done == 0, last = done + 1 == count;
+    if (op == 0) {
+      // the plain forward, straight into out (always the first member)
+      const ForwardWs B = forward_ws(m, n, h, w, E.fwd);
+      if (int rc = forward_launches(m, x10, x20, x60, out, n, h, w, B, 0, false, stream, nullptr)) return rc;
+    } else {
+      const bool tr = op & 1;
+      const int th = tr ? w : h, tw = tr ? h : w;                // the turned images
+      float* const turned[3] = {E.x10, E.x20, E.x60};
+      for (int k = 0; k < 3; ++k)
+        if (ins[k]) HIP_TRY(launch_dihedral(ins[k], turned[k], n, cs[k], h, w, op, nullptr, false, stream));
+      const ForwardWs B = forward_ws(m, n, th, tw, E.fwd);
+      if (int rc = forward_launches(m, E.x10, E.x20, E.x60, E.y, n, th, tw, B, 0, false, stream, nullptr)) return rc;
+      if (first) HIP_TRY(launch_dihedral(E.y, out, n, m->cout, th, tw, op, nullptr, true, stream));
+      else HIP_TRY(launch_dihedral_accumulate(E.y, out, n, m->cout, h, w, op, last ? count : 0, stream));
+    }
+    ++done;
+  }
+  return DSEN2_OK;
+}
+
 extern "C" {
 
 const char* dsen2_version(void) {
@@ -694,6 +799,43 @@ int dsen2_recompose(const float* dev_patches, int count, int C, int P, int borde
 int dsen2_recompose_rows(const float* dev_patches, int count, int C, int P, int border, float* dev_img, int H, int W, float scale,
                          int row0, int row1, void* stream) {
   return guarded([&] { return recompose_rows(dev_patches, count, C, P, border, dev_img, H, W, scale, row0, row1, stream); });
+}
+
+int dsen2_dihedral_nchw(const float* dev_in, float* dev_out, int n, int c, int h, int w, int op, const int* dev_ops, int inverse,
+                        void* stream) {
+  return guarded([&]() -> int {
+    size_t elems = 0;
+    if (int rc = check_dihedral_args(dev_in, dev_out, n, c, h, w, op, &elems)) return rc;
+    if (dev_ops && h != w) return fail(DSEN2_ERR_INVALID, "per-sample ops need square images (an odd rotation swaps H and W), got %dx%d", h, w);
+    if (elems == 0) return DSEN2_OK;
+    HIP_TRY(launch_dihedral(dev_in, dev_out, n, c, h, w, op, dev_ops, inverse != 0, (hipStream_t)stream));
+    return DSEN2_OK;
+  });
+}
+
+int dsen2_dihedral_accumulate(const float* dev_in, float* dev_acc, int n, int c, int h, int w, int op, int count, void* stream) {
+  return guarded([&]() -> int {
+    size_t elems = 0;
+    if (int rc = check_dihedral_args(dev_in, dev_acc, n, c, h, w, op, &elems)) return rc;
+    if (count < 0) return fail(DSEN2_ERR_INVALID, "count %d is negative", count);
+    if (elems == 0) return DSEN2_OK;
+    HIP_TRY(launch_dihedral_accumulate(dev_in, dev_acc, n, c, h, w, op, count, (hipStream_t)stream));
+    return DSEN2_OK;
+  });
+}
+
+int dsen2_model_ensemble_workspace_bytes(const dsen2_model* m, int n, int h, int w, int mask, size_t* bytes) {
+  if (!m || !bytes) return fail(DSEN2_ERR_INVALID, "NULL argument");
+  if (int rc = check_ensemble_shape(m, n, h, w, mask)) return rc;
+  *bytes = ensemble_ws(m, n, h, w, mask, nullptr).bytes;
+  return DSEN2_OK;
+}
+
+int dsen2_model_forward_ensemble(dsen2_model* m, const float* dev_x10, const float* dev_x20, const float* dev_x60, float* dev_out,
+                                 int n, int h, int w, int mask, void* dev_workspace, size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    return forward_ensemble(m, dev_x10, dev_x20, dev_x60, dev_out, n, h, w, mask, dev_workspace, workspace_bytes, stream);
+  });
 }
 
 }  // extern "C"

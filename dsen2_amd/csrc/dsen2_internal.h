@@ -192,6 +192,14 @@ hipError_t launch_tile_gather(const float* img, int H, int W, int C, int border,
 hipError_t launch_recompose(const float* patches, int count, int C, int P, int border, float* img, int H, int W,
                             float scale, int row0, int row1, hipStream_t stream);
 
+// ---- flips and rotations (dihedral.hip) ------------------------------------------------------------
+// out = D_op(in) (inverse: D_op^-1(in)) on n * c planes of ih x iw; out's planes are iw x ih for odd op & 3.  dev_ops (or NULL;
+// needs ih == iw): int32 [n], sample s takes dev_ops[s] & 7 and `op` is not used.  No argument checks (dsen2_dihedral_nchw).
+hipError_t launch_dihedral(const float* in, float* out, int n, int c, int ih, int iw, int op, const int* dev_ops, bool inverse,
+                           hipStream_t stream);
+// acc (n * c planes of h x w) = acc + D_op^-1(in); count > 0: = (acc + D_op^-1(in)) / (float)count, a correctly rounded divide
+hipError_t launch_dihedral_accumulate(const float* in, float* acc, int n, int c, int h, int w, int op, int count, hipStream_t stream);
+
 // ---- training (conv3x3_wgrad.hip, train_ops.hip) --------------------------------------------------
 // Weight / bias gradient of a 3x3 'same' convolution: dw (HWIO (3,3,ci_real,co_real)) = scale * sum_p a[p + tap][ci] g[p][co],
 // db[co_real] = scale * sum_p g[p][co]; a NHWC with ca channels, g NHWC with cg.  Shapes: cg % 128 == 0 (body, first layer), or

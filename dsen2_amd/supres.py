@@ -32,6 +32,10 @@ MDL_PATH = '../models/'
 # 'bf16x3' (every fp32 operand as two bf16 numbers, three bf16 MFMAs per product: ~1e-5 rmse in the normalised domain —
 # inside the 1e-4 gate — at ~3x the fp32 rate).
 PRECISION = os.environ.get('DSEN2_PRECISION', 'fp32')
+# Not in the reference either: the geometric self-ensemble ("EDSR+").  On: every patch is predicted in its 8 flips and rotations,
+# each prediction is turned back and the 8 are averaged (S2Model.forward_device_ensemble) — about 8 x the network time of a tile;
+# tiling, up-sampling, recomposition and the sharding over ranks are untouched (the ensemble is per patch).  Default off.
+SELF_ENSEMBLE = os.environ.get('DSEN2_SELF_ENSEMBLE', '0') not in ('', '0')
 
 _MODEL_CACHE = {}
 
@@ -79,7 +83,7 @@ def clear_model_cache():
 def _predict(test, input_shape, deep=False, run_60=False):
     """testing/supres.py:53-66 — list of NCHW float32 arrays in, [N, Cout, H, W] float32 array out."""
     model = _get_model(input_shape, deep, run_60)
-    return model.predict(test, verbose=1)
+    return model.predict(test, verbose=1, ensemble=True) if SELF_ENSEMBLE else model.predict(test, verbose=1)
 
 
 def _row_slab(org_lr, scale, patch, border, height):
@@ -249,17 +253,18 @@ def _run(dsets, scales, patch, border, deep, run_60):
         shard = Shard(dsets, scales, patch_sizes, borders, org[first:first + count], world)
         if banded:
             sink = RowSink(shape, dev)
-        bs = model.preferred_batch(patch, patch)
+        bs = model.preferred_batch(patch, patch, ensemble=True) if SELF_ENSEMBLE else model.preferred_batch(patch, patch)
+        forward = model.forward_device_ensemble if SELF_ENSEMBLE else model.forward_device
         for i0 in range(0, count, bs):                                 # this loop only enqueues
             n = min(bs, count - i0)
             xs = shard.batch(i0, n)
             if send is None:
-                model.forward_device(xs, out=pred[i0:i0 + n])
+                forward(xs, out=pred[i0:i0 + n])
                 if banded:
                     for r0, r1 in _final_bands(i0 + n, used, done_rows, size, inner):
                         sink.rows(pred, border, r0, r1)
             else:
-                y = model.forward_device(xs)
+                y = forward(xs)
                 send[i0:i0 + n].copy_(y[:, :, border:patch - border, border:patch - border])
                 # a piece whose slots this rank has all written (a short shard: all it will ever write) goes out now
                 while cg is not None and issued < cg.n_chunks and i0 + n >= min(cg.bounds[issued][1], count):

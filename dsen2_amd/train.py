@@ -29,8 +29,14 @@ the backward pass.  --backend gloo rehearses the control flow with ranks sharing
 WORLD_SIZE > 1 is refused; with it, a single process trains exactly as without.  --data_parallel --emulate_world N in a single
 process is fit(data_parallel=True, emulate_world=N): the N-rank run restated on one GPU (its files, without its speed).
 
-    python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] --path P
-is that script's predict branch: for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
+--augment (not in the reference; default off) turns every training sample of every step by one of the 8 flips and rotations of the
+square, inputs and target alike, on the GPU after the upload (S2Model.fit(augment=True); training.AugmentOps draws the ops from
+--seed on a stream of its own, so the epoch permutations do not change; square patches; validation is never augmented).  Under
+--data_parallel every rank draws the ops of the global batch, so an N-rank run still equals its one-process restatement.
+
+    python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] --path P
+is that script's predict branch (--self_ensemble, not in the reference: predict(ensemble=True), the mean over the 8 flips and
+rotations of every patch; --augment is refused here): for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
 loads the tiled test set (patches.OpenDataFilesTest), runs predict(batch_size=8), recomposes the image (border 4; 12 for test60/
 and true/), multiplies by SCALE = 2000 and writes <P>/<folder>/<dset>/<model_nr>-predict.npy, model_nr being the seven
 characters in front of 'lr_1e-04' in FILE's name (model_number).  `python -m dsen2_amd.evaluate` scores those files.
@@ -72,7 +78,16 @@ def parse_args(argv=None):
                    help='Collectives of --data_parallel: nccl (RCCL, default) or gloo (a rehearsal with ranks sharing GPUs).')
     p.add_argument('--emulate_world', type=int, default=None, metavar='N',
                    help='With --data_parallel in ONE process: compute what an N-rank run computes, bit for bit, shard after shard.')
+    p.add_argument('--augment', action='store_true',
+                   help='Training: flip and rotate every sample of every step at random (the 8 symmetries of the square, inputs and '
+                        'target alike, on the GPU; square patches).  Validation is never augmented.')
+    p.add_argument('--self_ensemble', action='store_true',
+                   help='With --predict: average the predictions for the 8 flips and rotations of every patch (~8x the network time).')
     args = p.parse_args(argv)
+    if args.augment and args.predict_file:
+        p.error('--augment is an option of training: it cannot be combined with --predict')
+    if args.self_ensemble and not args.predict_file:
+        p.error('--self_ensemble is an option of --predict')
     if args.emulate_world is not None and (not args.data_parallel or args.emulate_world < 1):
         p.error('--emulate_world N (N >= 1) restates a --data_parallel run in one process: pass --data_parallel too')
     if args.mixed_precision is not None and args.precision != 'fp32':
@@ -105,7 +120,10 @@ def predict(model, args, path):
         print('Timer started.')
         print('Predicting: {}.'.format(dset))
         train, image_size = patches.OpenDataFilesTest(path + folder + dset, args.run_60, SCALE, args.true)
-        prediction = model.predict(train, batch_size=8, verbose=1)
+        if args.self_ensemble:
+            prediction = model.predict(train, batch_size=8, verbose=1, ensemble=True)
+        else:
+            prediction = model.predict(train, batch_size=8, verbose=1)
         images = patches.recompose_images(prediction, border=border, size=(image_size[1], image_size[0]))     # (rows, columns): see above
         print('Writing to file...')
         np.save(path + folder + dset + '/' + model_nr + '-predict', images * SCALE)
@@ -193,7 +211,7 @@ def run(args, rank, world):
     say('Training starts...')
     model.fit(x=train, y=label, batch_size=batch_size, epochs=args.epochs, verbose=int(rank == 0), callbacks=callbacks,
               validation_data=(val_tr, val_lb), shuffle=True, seed=args.seed, data_parallel=args.data_parallel,
-              emulate_world=args.emulate_world)
+              emulate_world=args.emulate_world, augment=args.augment)
     say('best weights: {}\nlog: {}'.format(ckpt, log_path))
     return 0
 

@@ -5,6 +5,7 @@
   ReduceLROnPlateau  keras-2 logic (supres_train.py: factor 0.5, patience 5, min_delta 1e-6, cooldown 20, min_lr 1e-5)
   ModelCheckpoint    save_best_only on val_loss, written as a flat .npy that weights.load_flat reads
   History            what S2Model.fit returns
+  AugmentOps         the per-sample flips and rotations of fit(augment=True) (not in the reference)
   load_training_data the reference's data layout (utils/patches.py: OpenDataFiles / splitTrainVal)
 """
 import glob
@@ -44,6 +45,23 @@ class Nadam(object):
         """Fresh optimizer state (what keras has after compile(): --resume loads weights only)."""
         self.iterations = 0
         self.m_schedule = 1.0
+
+
+class AugmentOps(object):
+    """The flips and rotations of fit(augment=True): draw(n) returns the ops of the next step, one per sample of the (global)
+    batch — int32 values uniform in 0..7, op = k + 4 f: f = 1 flips left-right first, then k quarter turns counter-clockwise
+    (include/dsen2_hip.h, "dihedral").  The generator is numpy's default_rng on the seed sequence [seed, STREAM]: a function of
+    the fit's seed alone, and a stream of its own — the epoch permutations (default_rng(seed)) are those of a fit without
+    augmentation.  seed None: fresh entropy.  Every draw advances the stream, so equal seeds and equal batch sizes give equal
+    ops, step for step, in any process."""
+    STREAM = 0x64696865          # 'dihe'
+
+    def __init__(self, seed=None):
+        entropy = None if seed is None else [int(seed), self.STREAM]
+        self.rng = np.random.default_rng(np.random.SeedSequence(entropy))
+
+    def draw(self, n):
+        return self.rng.integers(0, 8, size=int(n), dtype=np.int32)
 
 
 class Callback(object):

@@ -117,6 +117,40 @@ int dsen2_model_forward_profile(dsen2_model *m, const float *x10, const float *x
                                 int n, int h, int w, void *workspace, size_t workspace_bytes, void *stream, int warm,
                                 int iters, float *ms5);
 
+/* ---- dihedral: the 8 flips and rotations of a patch; the geometric self-ensemble ("EDSR+") -----------------------------
+ * No reference counterpart (the reference neither augments nor ensembles); opt-in everywhere.
+ * Convention: op = k + 4 f with k in 0..3, f in 0..1, and for a [..., H, W] array a
+ *     D_op(a)    = np.rot90(a[..., ::-1] if f else a, k, axes=(-2, -1))          (counter-clockwise; odd k swaps H and W)
+ *     D_op^-1(b) = t[..., ::-1] if f else t,  t = np.rot90(b, -k, axes=(-2, -1))
+ * One kernel family (csrc/dihedral.hip): 32 x 32 tiles through LDS, reads and writes coalesced for all 8 ops, ragged edges by
+ * bounds, no atomics, any pointer alignment (16-byte reads where the width and the pointer allow; same bits).
+ *
+ * dsen2_dihedral_nchw: dev_out = D_op(dev_in), or D_op^-1(dev_in) when `inverse`; dev_in [n,c,h,w] float32, dev_out [n,c,h,w]
+ *   or [n,c,w,h] (odd k).  Pure data movement: every bit pattern survives.  dev_ops (or NULL): int32 device array [n], sample s
+ *   takes op dev_ops[s] & 7 instead of `op` (which must still be 0..7); needs h == w.
+ * dsen2_dihedral_accumulate: dev_acc = dev_acc + D_op^-1(dev_in) in fp32; h, w are those of dev_acc, dev_in is [n,c,w,h] for
+ *   odd k.  count_or_0 > 0: dev_acc = (dev_acc + D_op^-1(dev_in)) / (float)count_or_0, a correctly rounded fp32 divide.
+ * Both: DSEN2_ERR_INVALID (nothing launched) for a NULL pointer, op outside 0..7, a negative count, 2^31 elements or more,
+ *   dev_ops with h != w, an output that overlaps the input.  n == 0 returns DSEN2_OK.
+ *
+ * dsen2_model_forward_ensemble: the mean over the members selected by `mask` (bit op = member op, 1..255) of
+ *   y_op = D_op^-1(forward(D_op x)).  Members run in ascending op order; the running sum is s = y_first, then s = s + y_next in
+ *   fp32, and after the last member s = s / (float)count (not computed for one member).  Member 0 is the plain forward written
+ *   straight into dev_out: mask = 1 is dsen2_model_forward bit for bit, at its cost and with its workspace.
+ *   Workspace (dsen2_model_ensemble_workspace_bytes, same mask): the forward's, plus — for any member but 0 — the turned inputs
+ *   and one member's output.  The library allocates nothing.  DSEN2_ERR_INVALID for mask 0 or above 255, a NULL pointer,
+ *   dev_out overlapping an input, an image beyond the forward's limit in either orientation, 2^31 elements or more in a tensor;
+ *   DSEN2_ERR_WORKSPACE for a short workspace; n == 0 returns DSEN2_OK.
+ *   The accuracy gain of the ensemble has not been measured in this project (it needs the trained checkpoints). */
+int dsen2_dihedral_nchw(const float *dev_in, float *dev_out, int n, int c, int h, int w, int op, const int *dev_ops_or_null,
+                        int inverse, void *stream);
+int dsen2_dihedral_accumulate(const float *dev_in, float *dev_acc, int n, int c, int h, int w, int op, int count_or_0,
+                              void *stream);
+int dsen2_model_ensemble_workspace_bytes(const dsen2_model *m, int n, int h, int w, int mask, size_t *bytes);
+int dsen2_model_forward_ensemble(dsen2_model *m, const float *dev_x10, const float *dev_x20, const float *dev_x60,
+                                 float *dev_out, int n, int h, int w, int mask, void *dev_workspace, size_t workspace_bytes,
+                                 void *stream);
+
 /* ---- single-layer entry points (kernel-level parity tests and benchmarks) -------------------
  * One 3x3 'same' convolution (keras Conv2D as used at utils/DSen2Net.py:10,12,29,35) on NHWC
  * float32 device tensors.  host_kernel is HWIO (3,3,cin,cout), host_bias is [cout].
