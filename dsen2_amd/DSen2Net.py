@@ -566,8 +566,9 @@ class S2Model(object):
         return [dihedral(t, ops=ops_dev) for t in tensors]
 
     def _step_on_shards(self, fetch, counts, mine=None, augment_ops=None):
-        """One step on a global batch cut into contiguous shards of counts[r] samples.  fetch(first, n) returns the host arrays
-        (x, y) of samples [first, first + n) of the batch.  mine = None: every shard is computed here, one after the other (gradient
+        """One step on a global batch cut into contiguous shards of counts[r] samples.  fetch(first, n) returns (x, y) of samples
+        [first, first + n) of the batch: host arrays, which are uploaded here, or float32 device tensors, which are used as they
+        are (fit_corpus: cut on the device, the ops already applied).  mine = None: every shard is computed here, one after the other (gradient
         accumulation; the one-process restatement of a data-parallel step).  mine = r: this process is rank r of a group of
         len(counts) and computes shard r alone; the rows are all-gathered.  Either way the same rows reach the same kernel in the
         same order.  augment_ops (or None): the checked ops of the GLOBAL batch, sliced like the samples.  Returns the
@@ -580,8 +581,11 @@ class S2Model(object):
             if n > 0 and mine in (None, r):
                 x, y = fetch(first, n)
                 _, _, h, w = np.shape(x[0])
-                xs = self._to_device(x, [(n, c, h, w) for c in self.bands])
-                yd = self._to_device([y], [(n, self.cout, h, w)])[0]
+                if isinstance(y, torch.Tensor):
+                    xs, yd = list(x), y
+                else:
+                    xs = self._to_device(x, [(n, c, h, w) for c in self.bands])
+                    yd = self._to_device([y], [(n, self.cout, h, w)])[0]
                 if augment_ops is not None:
                     *xs, yd = self._augment_device(xs + [yd], self._check_augment_ops(augment_ops[first:first + n], n, h, w))
                 row = rows[r if mine is None else 0]
@@ -636,6 +640,19 @@ class S2Model(object):
         self.nadam_update(st['grad'])
         loss = st['loss2'].cpu().numpy().astype(np.float64)
         return [float(loss[0]), float(loss[1])]
+
+    def train_on_device_batch(self, xs, y, loss_out=None):
+        """train_on_batch for a batch that is already on the device (float32 NCHW tensors, as gradients_device takes them):
+        gradients_device, then nadam_update.  [loss, mean_squared_error] of the batch before the step stay on the device: in
+        loss_out (a float32 device tensor of two values) when given, else in the training state's own pair, which the next step
+        overwrites; the tensor is returned.  Nothing is copied to the host and nothing synchronises."""
+        st = self._train_state()
+        loss2 = st['loss2'] if loss_out is None else loss_out
+        if loss2.dtype != torch.float32 or loss2.numel() != 2 or not loss2.is_contiguous() or loss2.device != self.device:
+            raise ValueError('loss_out must be a contiguous float32 %s tensor of two values' % (self.device,))
+        self.gradients_device(list(xs), y, st['grad'], loss2)
+        self.nadam_update(st['grad'])
+        return loss2
 
     def evaluate(self, x, y, batch_size=None, verbose=0):
         """keras Model.evaluate: [loss, mean_squared_error] over all samples (predict(), then float64 means)."""
@@ -697,6 +714,28 @@ class S2Model(object):
         self.set_weights_flat(payload[:-2])
         return int(payload[-2:].view(np.uint64)[0])
 
+    def _end_epoch(self, epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose):
+        """The end of an epoch of fit and of fit_corpus alike: the epoch's losses from `sums` (the float64 sums of samples x batch
+        loss) over `count` samples, the validation pass (sharded like the steps under a data-parallel plan), the log line, the
+        callbacks, the History entry, and under a process group the check that every rank holds the same weights."""
+        logs = {'loss': sums[0] / count, 'mean_squared_error': sums[1] / count}
+        if validation_data is not None:
+            if plan is None:
+                vl = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size)
+            else:
+                vl = self._evaluate_shards(validation_data[0], validation_data[1], batch_size, plan[0], plan[1])
+            logs['val_loss'], logs['val_mean_squared_error'] = vl
+        logs['lr'] = self.optimizer.lr
+        if verbose:
+            sys.stdout.write('\rEpoch %d/%d ' % (epoch + 1, epochs) +
+                             ' '.join('%s %.4e' % kv for kv in logs.items()) + '\n')
+        for cb in callbacks:
+            cb.on_epoch_end(epoch, logs)
+        history.append(epoch, logs)
+        if plan is not None and plan[1] is not None:
+            from . import dist
+            dist.assert_replicas_identical(self._train['flat'])
+
     def fit(self, x=None, y=None, batch_size=32, epochs=1, verbose=1, callbacks=None, validation_data=None, shuffle=True,
             initial_epoch=0, seed=None, data_parallel=False, emulate_world=None, augment=False):
         """keras Model.fit: a fresh permutation each epoch when `shuffle`, the last partial batch kept, the epoch loss the
@@ -717,8 +756,6 @@ class S2Model(object):
         the broadcast seed and takes its shard's slice.  Validation is never augmented."""
         from . import training
         plan = self._data_parallel_plan(data_parallel, emulate_world)
-        if plan is not None:
-            from . import dist
         x = [np.ascontiguousarray(a, dtype=np.float32) for a in x]
         y = np.ascontiguousarray(y, dtype=np.float32)
         count = y.shape[0]
@@ -751,22 +788,74 @@ class S2Model(object):
                     sys.stdout.write('\rEpoch %d/%d %d/%d loss %.4e' % (epoch + 1, epochs, min(i0 + batch_size, count), count,
                                                                      sums[0] / min(i0 + batch_size, count)))
                     sys.stdout.flush()
-            logs = {'loss': sums[0] / count, 'mean_squared_error': sums[1] / count}
-            if validation_data is not None:
-                if plan is None:
-                    vl = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size)
+            self._end_epoch(epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose)
+            if self.stop_training:
+                break
+        return history
+
+    def fit_corpus(self, corpus, batch_size, steps_per_epoch, epochs=1, validation_data=None, seed=None, augment=False,
+                   callbacks=None, initial_epoch=0, verbose=1, shards=None, data_parallel=False, emulate_world=None):
+        """fit from a corpus.TileCorpus: an epoch is steps_per_epoch batches of batch_size fresh crops, drawn by ONE
+        corpus.CorpusSampler(corpus, seed, augment) and cut on the device (corpus.batch: one launch per step, the dihedral ops of
+        `augment` included).  Per step the host draws the table, uploads it through page-locked memory and enqueues
+        train_on_device_batch; the step's two losses go into a device [steps_per_epoch, 2] buffer that is read ONCE per epoch —
+        no other copy and no synchronisation happen inside an epoch.  The epoch loss is fit's formula: the float64 sum of
+        batch_size * loss over the steps, in step order, divided by the number of samples (all batches are equal: the mean).
+        Validation (validation_data: host arrays, e.g. corpus.validation_arrays), logs, callbacks, the History returned and
+        stop_training are exactly fit's.
+        Sharded steps: shards=K cuts every batch as train_on_batch(shards=K) does (gradient accumulation);
+        data_parallel / emulate_world are fit's: every rank draws the table of the GLOBAL batch from the broadcast seed and cuts
+        its dist.shard_range slice from its own copy of the corpus; the rest is _step_on_shards, which reads each step's losses
+        (these modes synchronise once per step, as fit does)."""
+        from . import training
+        from .corpus import CorpusSampler
+        plan = self._data_parallel_plan(data_parallel, emulate_world)
+        if plan is not None and shards is not None:
+            raise ValueError('shards is the one-process cut of a batch: it cannot be combined with data_parallel')
+        batch_size, steps = int(batch_size), int(steps_per_epoch)
+        if batch_size < 1 or steps < 1:
+            raise ValueError('batch_size and steps_per_epoch must be at least 1, got %d and %d' % (batch_size, steps))
+        if corpus.device != self.device or tuple(c for c in self.bands) != tuple(s[1] for s in corpus.output_shapes(1)[0]) or \
+                self.cout != corpus.cout:
+            raise ValueError('the corpus (%s, run_60=%r) does not feed this model (%s, bands %r)'
+                             % (corpus.device, corpus.run_60, self.device, tuple(self.bands)))
+        self._train_state()
+        callbacks = list(callbacks or [])
+        history = training.History()
+        for cb in callbacks:
+            cb.set_model(self)
+            cb.on_train_begin()
+        if plan is not None:
+            seed = self._data_parallel_start(seed)
+        sampler = CorpusSampler(corpus, seed, augment)
+        sharded = plan is not None or shards is not None
+        if not sharded:
+            losses = torch.empty((steps, 2), dtype=torch.float32, device=self.device)
+            tables = torch.empty((steps, batch_size, 4), dtype=torch.int32).pin_memory()      # one slot per step of an epoch: a
+            tables_dev = torch.empty((steps, batch_size, 4), dtype=torch.int32, device=self.device)   # slot is free again after the
+        count = steps * batch_size                                                           # epoch's read of the losses
+        self.stop_training = False
+        for epoch in range(initial_epoch, epochs):
+            sums = np.zeros(2)
+            for i in range(steps):
+                table = sampler.draw(batch_size)
+                if not sharded:
+                    tables[i].numpy()[...] = table
+                    tables_dev[i].copy_(tables[i], non_blocking=True)
+                    xs, y = corpus.batch(table, table_dev=tables_dev[i])
+                    self.train_on_device_batch(xs, y, loss_out=losses[i])
                 else:
-                    vl = self._evaluate_shards(validation_data[0], validation_data[1], batch_size, plan[0], plan[1])
-                logs['val_loss'], logs['val_mean_squared_error'] = vl
-            logs['lr'] = self.optimizer.lr
-            if verbose:
-                sys.stdout.write('\rEpoch %d/%d ' % (epoch + 1, epochs) +
-                                 ' '.join('%s %.4e' % kv for kv in logs.items()) + '\n')
-            for cb in callbacks:
-                cb.on_epoch_end(epoch, logs)
-            history.append(epoch, logs)
-            if plan is not None and plan[1] is not None:
-                dist.assert_replicas_identical(self._train['flat'])
+                    counts = self._shard_counts(batch_size, shards if plan is None else plan[0])
+                    r = self._step_on_shards(lambda first, m: corpus.batch(table[first:first + m]), counts,
+                                             None if plan is None else plan[1])
+                    sums += np.asarray(r) * batch_size
+                if verbose:
+                    sys.stdout.write('\rEpoch %d/%d %d/%d' % (epoch + 1, epochs, (i + 1) * batch_size, count))
+                    sys.stdout.flush()
+            if not sharded:
+                for r in losses.cpu().numpy().astype(np.float64):                 # the epoch's one read
+                    sums += r * batch_size
+            self._end_epoch(epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose)
             if self.stop_training:
                 break
         return history

@@ -22,6 +22,13 @@ c_int = ctypes.c_int
 c_size_t = ctypes.c_size_t
 c_double = ctypes.c_double
 
+
+class CorpusTile(ctypes.Structure):
+    """dsen2_corpus_tile (include/dsen2_hip.h, "corpus")."""
+    _fields_ = [('dev_lr10', c_void_p), ('dev_lr20', c_void_p), ('dev_lr60', c_void_p), ('dev_gt', c_void_p),
+                ('grid_h', c_int), ('grid_w', c_int), ('gt_dtype', c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/dsen2_hip.h declares
 SIGNATURES = {
     'dsen2_version': (ctypes.c_char_p, []),
@@ -87,6 +94,10 @@ SIGNATURES = {
                                 c_void_p]),
     'dsen2_recompose_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_float,
                                      c_int, c_int, c_void_p]),
+    'dsen2_corpus_create': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    'dsen2_corpus_destroy': (None, [c_void_p]),
+    'dsen2_corpus_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     'dsen2_down_pixel_aggr': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int,
                                       c_void_p, c_int, c_void_p]),
     'dsen2_imresize_axis': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

@@ -113,6 +113,32 @@ def _open_product(args, roi):
     return product.read('10m'), product.read('20m'), product.read('60m'), box
 
 
+def open_tile(data_file, run_60=False, quiet=False):
+    """(d10, d20) — (d10, d20, d60) with run_60 — of one whole tile, through the opener DATA_FILE goes through above (an array
+    file, or a SAFE product where GDAL is importable); None, with the opener's message printed, when it cannot be opened.  For
+    `python -m dsen2_amd.train --tiles`."""
+    import contextlib
+    import io
+    from . import cli
+    args = argparse.Namespace(data_file=data_file, run_60=bool(run_60), true_data=False, roi_x_y='')
+    is_array = os.path.splitext(data_file)[1].lower() in cli.ARRAY_EXTENSIONS
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf if quiet else sys.stdout):
+        opened = _open_arrays(args, None) if is_array else _open_product(args, None)
+    if opened is None:
+        if quiet:
+            sys.stdout.write(buf.getvalue())
+        return None
+    data10, data20, data60, box = opened
+    if box is None:
+        print('%s: empty image' % data_file)
+        return None
+    if run_60 and data60 is None:
+        print('%s holds no 60 m image: --run_60 needs one' % data_file)
+        return None
+    return (data10, data20, data60) if run_60 else (data10, data20)
+
+
 def _print_region(box):
     xmin, ymin, xmax, ymax = box
     print('Selected UTM Zone:')                                     # (the reference's format string has no placeholder)

@@ -25,13 +25,7 @@ constexpr int kDRows = 8;                // rows of the tile a pass of the 256 t
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// (transposing, ry, rx) of op 0..7 as bits 2, 1, 0
-__host__ __device__ __forceinline__ int dihedral_bits(int op) {
-  // op:      0  1  2  3  4  5  6  7
-  // bits:    0  5  3  6  1  4  2  7      (one hex digit each, op 0 lowest)
-  return (int)(0x72416350u >> (4 * (op & 7))) & 7;
-}
-
+// (dihedral_bits: the (transposing, ry, rx) bits of an op, dsen2_internal.h)
 __host__ __device__ __forceinline__ int dihedral_inverse(int op) {
   op &= 7;
   return (op & 4) ? op : ((4 - op) & 3);

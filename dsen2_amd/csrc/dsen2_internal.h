@@ -199,6 +199,26 @@ hipError_t launch_dihedral(const float* in, float* out, int n, int c, int ih, in
                            hipStream_t stream);
 // acc (n * c planes of h x w) = acc + D_op^-1(in); count > 0: = (acc + D_op^-1(in)) / (float)count, a correctly rounded divide
 hipError_t launch_dihedral_accumulate(const float* in, float* acc, int n, int c, int h, int w, int op, int count, hipStream_t stream);
+// (transposing, ry, rx) of op 0..7 as bits 2, 1, 0 — the index map of dihedral.hip's header comment, shared with corpus_batch.hip
+__host__ __device__ __forceinline__ int dihedral_bits(int op) {
+  // op:      0  1  2  3  4  5  6  7
+  // bits:    0  5  3  6  1  4  2  7      (one hex digit each, op 0 lowest)
+  return (int)(0x72416350u >> (4 * (op & 7))) & 7;
+}
+
+// ---- a training batch cut from a device-resident corpus (corpus_batch.hip) -------------------------------
+// One tile's device images (HWC): lr10 [s*eh, s*ew, 4] with s = 2 (6 with run_60), lr20 [eh, ew, 6] ([3 eh, 3 ew, 6]), lr60 [eh, ew,
+// 2] (run_60 only), gt [s*eh, s*ew, 6 (2)] of uint16 (gt_u16) or float32; (eh, ew) is the extent of the origin grid.
+struct CorpusTileDev {
+  const float *lr10, *lr20, *lr60;
+  const void* gt;
+  int eh, ew, gt_u16, pad_;
+};
+// ONE launch: every sample of dev_samples ([n, 4] int32: tile, oy, ox, op), every output tensor.  No argument checks
+// (dsen2_corpus_batch); a sample whose tile or origin does not belong to the table is skipped by the kernel (nothing is read or
+// written for it).
+hipError_t launch_corpus_batch(const CorpusTileDev* dev_tiles, int n_tiles, bool run_60, const int* dev_samples, int n, float divisor,
+                               float* x10, float* x20, float* x60, float* y, hipStream_t stream);
 
 // ---- training (conv3x3_wgrad.hip, train_ops.hip) --------------------------------------------------
 // Weight / bias gradient of a 3x3 'same' convolution: dw (HWIO (3,3,ci_real,co_real)) = scale * sum_p a[p + tap][ci] g[p][co],

@@ -3,6 +3,7 @@
 // All of them are pure gathers: one thread per OUTPUT element, so there are no write races and every
 // store is coalesced; reads are served by L2 (each source line is touched by a handful of neighbours).
 #include "dsen2_internal.h"
+#include "upsample_math.h"
 
 namespace dsen2 {
 
@@ -58,26 +59,7 @@ hipError_t launch_pack_inputs(const float* x10, const float* x20, const float* x
 //   — the captured outputs of the reference's interp_patches are reproduced BIT FOR BIT (tests/test_gpu_patches.py).  warp()'s
 //   clip to the input's [min, max] is a no-op for this arithmetic (a plateau of equal taps returns its value exactly, every
 //   operation is monotone in the taps; the tests' CPU restatement keeps the clip and agrees) and is not computed.
-__device__ __forceinline__ int mirror_index(int i, int dim) {
-  if (dim == 1) return 0;
-  const int cmax = dim - 1;
-  if (i < 0) {
-    const int k = -i;
-    return ((k / cmax) & 1) ? cmax - (k % cmax) : (k % cmax);
-  }
-  if (i > cmax) return ((i / cmax) & 1) ? cmax - (i % cmax) : (i % cmax);
-  return i;
-}
-
-// mirror_index for an index at most one image away (-cmax <= i <= 2 * cmax: one reflection, no division, no branch) —
-// every tap of an up-sampler's window; images of one or two pixels (several reflections) take the general form.
-__device__ __forceinline__ int mirror_index_near(int i, int dim) {
-  const int cmax = dim - 1;
-  int j = i < 0 ? -i : i;
-  j = j > cmax ? 2 * cmax - j : j;
-  if (__builtin_expect((unsigned)j > (unsigned)cmax, 0)) j = mirror_index(i, dim);
-  return j;
-}
+// (mirror_index, mirror_index_near and the arithmetic of one output: upsample_math.h, shared with corpus_batch.hip)
 
 // One thread = 4 consecutive output columns x kUpRows consecutive output rows of one plane.  The reference blends
 // horizontally first (top = row r0, bot = row r1, same formula) and then vertically, so the horizontal blend H[r][oj] of
@@ -100,35 +82,32 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     const float* const plane = in + p * (size_t)h * w;
     // column taps of the four outputs (identical for every row)
     int c0[4], c1[4];
-    double dc[4];
     float dcf[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int oj = oj0 + e < ow ? oj0 + e : ow - 1;
-      const float c = __fadd_rn(__fmul_rn(sx, (float)oj), ox);
-      const float cf = floorf(c);
-      c0[e] = mirror_index((int)cf, w);
-      c1[e] = mirror_index((int)ceilf(c), w);
-      dcf[e] = __fsub_rn(c, cf);
-      dc[e] = (double)dcf[e];
+      int lo, hi;
+      dcf[e] = up_coord(sx, ox, oj, &lo, &hi);
+      c0[e] = mirror_index(lo, w);
+      c1[e] = mirror_index(hi, w);
     }
     // horizontal blend of input row r at the four output columns
     auto hrow = [&](int r, double (&H)[4]) {
       const float* const src = plane + (size_t)r * w;
       int pc0 = -1, pc1 = -1;
-      double pq0 = 0.0, pq1 = 0.0;
+      float pq0 = 0.f, pq1 = 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        double q0, q1;
+        float q0, q1;
         if (c0[e] == pc0) q0 = pq0;
         else if (c0[e] == pc1) q0 = pq1;
-        else q0 = (double)__fdiv_rn(src[c0[e]], 30000.0f);
+        else q0 = up_quotient(src[c0[e]]);
         if (c1[e] == c0[e]) q1 = q0;
         else if (c1[e] == pc1) q1 = pq1;
         else if (c1[e] == pc0) q1 = pq0;
-        else q1 = (double)__fdiv_rn(src[c1[e]], 30000.0f);
+        else q1 = up_quotient(src[c1[e]]);
         pc0 = c0[e]; pc1 = c1[e]; pq0 = q0; pq1 = q1;
-        H[e] = (1.0 - dc[e]) * q0 + (double)__fmul_rn(dcf[e], (float)q1);      // (q1 is a float32 quotient: the cast is exact)
+        H[e] = up_hblend(dcf[e], q0, q1);
       }
     };
     int ia = -1, ib = -1;                       // input rows held in Ha / Hb
@@ -137,10 +116,9 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     for (int k = 0; k < kUpRows; ++k) {
       const int oi = rb * kUpRows + k;
       if (oi >= oh) break;
-      const float r = __fadd_rn(__fmul_rn(sy, (float)oi), oy);
-      const float rf = floorf(r);
-      const int r0 = mirror_index((int)rf, h), r1 = mirror_index((int)ceilf(r), h);
-      const double dr = (double)__fsub_rn(r, rf);
+      int rlo, rhi;
+      const float drf = up_coord(sy, oy, oi, &rlo, &rhi);
+      const int r0 = mirror_index(rlo, h), r1 = mirror_index(rhi, h);
       // make both rows resident (never evicting the one the other tap needs)
       if (r0 != ia && r0 != ib) {
         if (a_older && ia != r1) { hrow(r0, Ha); ia = r0; a_older = false; }
@@ -156,8 +134,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
       for (int e = 0; e < 4; ++e) {
         const double top = r0 == ia ? Ha[e] : Hb[e];
         const double bot = r1 == ia ? Ha[e] : Hb[e];
-        const float v = __fmul_rn((float)((1.0 - dr) * top + dr * bot), 30000.0f);
-        res[e] = post_div == 1.0f ? v : __fdiv_rn(v, post_div);   // folds `p20 /= SCALE` (testing/supres.py:24)
+        res[e] = up_vblend(drf, top, bot, post_div);   // folds `p20 /= SCALE` (testing/supres.py:24)
       }
       float* dst = out + (p * oh + oi) * (size_t)ow + oj0;
       if ((ow & 3) == 0) {
@@ -195,26 +172,24 @@ __global__ __launch_bounds__(256) void upsample_window_kernel(const float* __res
     const float* const plane = in + p * (size_t)h * w;
     // columns: the window starts at the first output's left tap
     int i0[4], i1[4];
-    double dc[4];
     float dcf[4];
     int cb = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int oj = oj0 + e < ow ? oj0 + e : ow - 1;
-      const float c = __fadd_rn(__fmul_rn(sx, (float)oj), ox);
-      const float cf = floorf(c);
-      if (e == 0) cb = (int)cf;
-      i0[e] = (int)cf - cb;
-      i1[e] = (int)ceilf(c) - cb;
-      dcf[e] = __fsub_rn(c, cf);
-      dc[e] = (double)dcf[e];
+      int lo, hi;
+      dcf[e] = up_coord(sx, ox, oj, &lo, &hi);
+      if (e == 0) cb = lo;
+      i0[e] = lo - cb;
+      i1[e] = hi - cb;
     }
     int wcol[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) wcol[j] = mirror_index_near(cb + j, w);
     // rows: the window starts at the first output row's upper tap
     const int oi0 = rb * kUpRows;
-    const int ru0 = (int)floorf(__fadd_rn(__fmul_rn(sy, (float)oi0), oy));
+    int ru0, ru0_hi;
+    (void)up_coord(sy, oy, oi0, &ru0, &ru0_hi);
     float q[NR][4];
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
@@ -225,7 +200,7 @@ __global__ __launch_bounds__(256) void upsample_window_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < NR; ++j)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) q[j][c] = __fdiv_rn(q[j][c], 30000.0f);
+      for (int c = 0; c < 4; ++c) q[j][c] = up_quotient(q[j][c]);
     auto pick = [](const float (&v)[4], int k) -> float {
       const float lo = k == 1 ? v[1] : v[0], hi = k == 3 ? v[3] : v[2];
       return k >= 2 ? hi : lo;
@@ -233,24 +208,19 @@ __global__ __launch_bounds__(256) void upsample_window_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < NR; ++j)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double q0 = (double)pick(q[j], i0[e]);
-        h_s[(j * 4 + e) * 256 + tid] = (1.0 - dc[e]) * q0 + (double)__fmul_rn(dcf[e], pick(q[j], i1[e]));
-      }
+      for (int e = 0; e < 4; ++e) h_s[(j * 4 + e) * 256 + tid] = up_hblend(dcf[e], pick(q[j], i0[e]), pick(q[j], i1[e]));
 #pragma unroll
     for (int k = 0; k < kUpRows; ++k) {
       const int oi = oi0 + k;
       if (oi >= oh) break;
-      const float r = __fadd_rn(__fmul_rn(sy, (float)oi), oy);
-      const float rf = floorf(r);
-      const int j0 = (int)rf - ru0, j1 = (int)ceilf(r) - ru0;
-      const double dr = (double)__fsub_rn(r, rf);
+      int rlo, rhi;
+      const float drf = up_coord(sy, oy, oi, &rlo, &rhi);
+      const int j0 = rlo - ru0, j1 = rhi - ru0;
       float res[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const double top = h_s[(j0 * 4 + e) * 256 + tid], bot = h_s[(j1 * 4 + e) * 256 + tid];
-        const float v = __fmul_rn((float)((1.0 - dr) * top + dr * bot), 30000.0f);
-        res[e] = post_div == 1.0f ? v : __fdiv_rn(v, post_div);   // folds `p20 /= SCALE` (testing/supres.py:24)
+        res[e] = up_vblend(drf, top, bot, post_div);   // folds `p20 /= SCALE` (testing/supres.py:24)
       }
       float* dst = out + (p * oh + oi) * (size_t)ow + oj0;
       if ((ow & 3) == 0) {

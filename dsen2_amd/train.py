@@ -34,6 +34,18 @@ square, inputs and target alike, on the GPU after the upload (S2Model.fit(augmen
 --seed on a stream of its own, so the epoch permutations do not change; square patches; validation is never augmented).  Under
 --data_parallel every rank draws the ops of the global batch, so an N-rank run still equals its one-process restatement.
 
+    python -m dsen2_amd.train --tiles F [F ...] [--steps_per_epoch N] [--val_crops M] ...
+trains from tiles instead of from files of crops (not in the reference): every F is a tile as `python -m dsen2_amd.create_patches
+DATA_FILE` opens it (.npz / .mat, or a SAFE product where GDAL is importable; the same opener).  The tiles are downsampled on the GPU
+and stay there with their ground truth (corpus.TileCorpus; about 1 GB per 10980^2 tile), and every step's batch is cut from them on
+the GPU — fresh random crops each step, uniform over the tiles (S2Model.fit_corpus).  An epoch is --steps_per_epoch batches
+(default: as many crops as the reference's files hold, 8000 per tile, 500 with --run_60); validation is --val_crops fixed crops per
+tile (default a tenth of that), drawn once from --seed.  All other flags keep their meaning, --augment (the ops are drawn with the
+crops) and --data_parallel / --emulate_world included: every rank holds the whole corpus in ITS GPU's memory, draws the crops of the
+global batch and cuts its own share, so no rank needs the training set in host memory; with more than one rank --seed is required
+(the validation crops must be the same everywhere).  The log and the checkpoint are the same files.  --tiles and a training set
+under --path exclude each other.
+
     python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] --path P
 is that script's predict branch (--self_ensemble, not in the reference: predict(ensemble=True), the mean over the 8 flips and
 rotations of every patch; --augment is refused here): for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
@@ -81,6 +93,12 @@ def parse_args(argv=None):
     p.add_argument('--augment', action='store_true',
                    help='Training: flip and rotate every sample of every step at random (the 8 symmetries of the square, inputs and '
                         'target alike, on the GPU; square patches).  Validation is never augmented.')
+    p.add_argument('--tiles', nargs='+', default=None, metavar='F',
+                   help='Train from these tiles (as create_patches DATA_FILE opens them), kept on the GPU; batches are cut there.')
+    p.add_argument('--steps_per_epoch', type=int, default=None, metavar='N',
+                   help='With --tiles: batches per epoch (default: 8000 crops per tile, 500 with --run_60, over the batch size).')
+    p.add_argument('--val_crops', type=int, default=None, metavar='M',
+                   help='With --tiles: fixed validation crops per tile (default 800, 50 with --run_60).')
     p.add_argument('--self_ensemble', action='store_true',
                    help='With --predict: average the predictions for the 8 flips and rotations of every patch (~8x the network time).')
     args = p.parse_args(argv)
@@ -88,6 +106,13 @@ def parse_args(argv=None):
         p.error('--augment is an option of training: it cannot be combined with --predict')
     if args.self_ensemble and not args.predict_file:
         p.error('--self_ensemble is an option of --predict')
+    if args.tiles is None and (args.steps_per_epoch is not None or args.val_crops is not None):
+        p.error('--steps_per_epoch and --val_crops are options of --tiles')
+    if args.tiles is not None and args.predict_file:
+        p.error('--tiles is an option of training: it cannot be combined with --predict')
+    if args.tiles is not None and ((args.steps_per_epoch is not None and args.steps_per_epoch < 1) or
+                                   (args.val_crops is not None and args.val_crops < 1)):
+        p.error('--steps_per_epoch and --val_crops must be at least 1')
     if args.emulate_world is not None and (not args.data_parallel or args.emulate_world < 1):
         p.error('--emulate_world N (N >= 1) restates a --data_parallel run in one process: pass --data_parallel too')
     if args.mixed_precision is not None and args.precision != 'fp32':
@@ -131,6 +156,18 @@ def predict(model, args, path):
     return 0
 
 
+TILES_AND_PATH = '--tiles and a training set under --path exclude each other: {} holds {} *SAFE director{} of crops'
+
+
+def tiles_conflict(args, path):
+    """The message when --tiles meets a populated training set under --path, else None."""
+    train_dir = path + ('train60' if args.run_60 else 'train')
+    found = glob.glob(os.path.join(train_dir, '*SAFE'))
+    if args.tiles is not None and found:
+        return TILES_AND_PATH.format(train_dir, len(found), 'y' if len(found) == 1 else 'ies')
+    return None
+
+
 def main(argv=None):
     args = parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -158,6 +195,14 @@ def run(args, rank, world):
         bands = ((4, None, None), (6, None, None), (2, None, None)) if args.run_60 else ((4, None, None), (6, None, None))
         return predict(s2model(bands, num_layers=32 if args.deep else 6, feature_size=256 if args.deep else 128,
                                precision=args.precision), args, path)
+    if args.tiles is not None:
+        conflict = tiles_conflict(args, path)
+        if conflict:
+            sys.stderr.write(conflict + '\n')
+            return 2
+        if world > 1 and args.seed is None:
+            sys.stderr.write('--tiles under --data_parallel needs --seed: every rank draws the validation crops itself\n')
+            return 2
     out = args.out if args.out is not None else path + 'network_data/'
     if rank == 0:
         os.makedirs(out, exist_ok=True)
@@ -189,9 +234,27 @@ def run(args, rank, world):
     model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
                   loss='mean_absolute_error', mixed_precision=args.mixed_precision)
 
-    say('Loading the training data...')
-    train, label, val_tr, val_lb = training.load_training_data(path, args.run_60, training.SCALE)
-    say('Loaded {} patches for training, {} for validation.'.format(label.shape[0], val_lb.shape[0]))
+    corpus = None
+    if args.tiles is not None:
+        from . import corpus as corpus_mod, create_patches
+        say('Loading {} tile{} onto the GPU...'.format(len(args.tiles), '' if len(args.tiles) == 1 else 's'))
+        rasters = []
+        for f in args.tiles:
+            opened = create_patches.open_tile(f, args.run_60, quiet=rank != 0)
+            if opened is None:
+                return 2
+            rasters.append(opened)
+        corpus = corpus_mod.TileCorpus(rasters, run_60=args.run_60, device=model.device)
+        del rasters
+        nr_crop = 500 if args.run_60 else 8000
+        steps = args.steps_per_epoch or max(1, len(corpus) * nr_crop // batch_size)
+        val_tr, val_lb = corpus.validation_arrays(args.val_crops or nr_crop // 10, args.seed)
+        say('Holding {} tile{} ({:.1f} MB on the GPU): {} steps of {} crops per epoch, {} crops for validation.'
+            .format(len(corpus), '' if len(corpus) == 1 else 's', corpus.nbytes / 1e6, steps, batch_size, val_lb.shape[0]))
+    else:
+        say('Loading the training data...')
+        train, label, val_tr, val_lb = training.load_training_data(path, args.run_60, training.SCALE)
+        say('Loaded {} patches for training, {} for validation.'.format(label.shape[0], val_lb.shape[0]))
 
     ckpt = os.path.join(out, model_nr + 'lr_{:.0e}.npy'.format(args.lr))
     log_path = os.path.join(out, model_nr + '_lr_{:.1e}.txt'.format(args.lr))
@@ -209,6 +272,12 @@ def run(args, rank, world):
     callbacks = files + [training.ReduceLROnPlateau(monitor='val_loss', factor=0.5, patience=5, verbose=int(rank == 0), min_delta=1e-6,
                                                     cooldown=20, min_lr=1e-5)]
     say('Training starts...')
+    if corpus is not None:
+        model.fit_corpus(corpus, batch_size, steps, epochs=args.epochs, validation_data=(val_tr, val_lb), seed=args.seed,
+                         augment=args.augment, callbacks=callbacks, verbose=int(rank == 0), data_parallel=args.data_parallel,
+                         emulate_world=args.emulate_world)
+        say('best weights: {}\nlog: {}'.format(ckpt, log_path))
+        return 0
     model.fit(x=train, y=label, batch_size=batch_size, epochs=args.epochs, verbose=int(rank == 0), callbacks=callbacks,
               validation_data=(val_tr, val_lb), shuffle=True, seed=args.seed, data_parallel=args.data_parallel,
               emulate_world=args.emulate_world, augment=args.augment)

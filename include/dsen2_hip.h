@@ -393,6 +393,53 @@ int dsen2_recompose_rows(const float *dev_patches, int count, int C, int P, int 
 int dsen2_down_pixel_aggr(const void *dev_img, int dtype, int H, int W, int C, int scale, const double *host_weights,
                           int radius, void *dev_out, int out_f64, void *stream);
 
+/* ---- corpus: training batches cut from tiles that live on the device (csrc/corpus_batch.hip) ---------------------------------
+ * No reference counterpart as a function: the reference writes a fixed set of random crops per tile to disk (save_random_patches /
+ * save_random_patches60, utils/patches.py:181-271) and trains from those files.  Here the downsampled images of every tile and the
+ * ground truth stay in device memory and EVERY batch is cut from them, in one launch, with the geometry of those two functions.
+ *
+ * A tile (dsen2_corpus_tile) is the device pointers of its HWC images and the extent (grid_h, grid_w) of its ORIGIN GRID, the
+ * lowest-resolution low-res image; with S = 2 (run_60: 6):
+ *                  run_60 = 0                                   run_60 = 1
+ *   dev_lr10       float32 [2 grid_h, 2 grid_w, 4]               float32 [6 grid_h, 6 grid_w, 4]
+ *   dev_lr20       float32 [grid_h, grid_w, 6]                   float32 [3 grid_h, 3 grid_w, 6]
+ *   dev_lr60       NULL                                         float32 [grid_h, grid_w, 2]
+ *   dev_gt         [2 grid_h, 2 grid_w, 6]                       [6 grid_h, 6 grid_w, 2]      uint16 or float32 (gt_dtype)
+ * A sample is four ints (tile, oy, ox, op): the 16 x 16 crop of the origin grid at (oy, ox), turned by the dihedral op.  Outputs,
+ * NCHW float32 with P = 32 (run_60: 96), sample k at index k:
+ *   dev_x10 [n,4,P,P]   dev_lr10 at (S oy, S ox), P x P, each value / divisor
+ *   dev_x20 [n,6,P,P]   dev_lr20 at (oy, ox), 16 x 16 (run_60: at (3 oy, 3 ox), 48 x 48), up-sampled to P x P as
+ *                       dsen2_upsample_mirror_bilinear up-samples a patch of that size on its own, post_divisor = divisor
+ *   dev_x60 [n,2,P,P]   run_60 only: dev_lr60 at (oy, ox), 16 x 16, up-sampled likewise
+ *   dev_y   [n,6|2,P,P] dev_gt at (S oy, S ox), P x P, widened to float32 (exact), each value / divisor
+ *   and then D_op of every one of them (the convention of "dihedral" above).  divisor == 1 skips the divide exactly.
+ * Bit for bit what dsen2_tile_gather (border 0), dsen2_upsample_mirror_bilinear and dsen2_dihedral_nchw give for the same origins,
+ * in ONE launch: a workgroup per (sample, tensor, 32 x 32 output tile) with all the tensor's bands, low-resolution crops
+ * interpolated from LDS, the op applied through a padded LDS tile so that the stores are coalesced for all 8 ops.  No atomics.
+ *
+ * dsen2_corpus_create checks the table (DSEN2_ERR_INVALID: a NULL image, dev_lr60 given or missing against run_60, a grid below
+ *   16 x 16, another gt_dtype, no tile) and copies it; it touches no device, and nothing of the images is read.  The device copy of
+ *   the table is made by the first dsen2_corpus_batch that launches (one synchronous copy), on the calling thread's current
+ *   device, to which the handle belongs from then on.  The images stay the caller's and must outlive the handle.
+ * dsen2_corpus_batch: host_samples and dev_samples are the same [n, 4] int32 table in host and in device memory: the host copy is
+ *   what is checked, the device copy is what the kernel reads (the caller uploads what it had checked; a device sample that does
+ *   not fit its tile is skipped by the kernel, so no byte outside a tile's images is ever read).  DSEN2_ERR_INVALID with nothing
+ *   launched: a NULL pointer, dev_x60 given or missing against run_60, either sample table missing, a tile index outside the
+ *   table, an origin with oy + 16 > grid_h or ox + 16 > grid_w (grid - 16 itself is the last valid origin) or negative, an op
+ *   outside 0..7, a divisor that is 0 or not finite, n negative or above 2^20.  n == 0 returns DSEN2_OK.  Nothing synchronises
+ *   after the first call. */
+typedef struct dsen2_corpus dsen2_corpus;
+typedef struct dsen2_corpus_tile {
+  const float *dev_lr10, *dev_lr20, *dev_lr60;
+  const void *dev_gt;
+  int grid_h, grid_w;
+  int gt_dtype; /* DSEN2_DTYPE_U16 or DSEN2_DTYPE_F32 */
+} dsen2_corpus_tile;
+int dsen2_corpus_create(const dsen2_corpus_tile *host_tiles, int n_tiles, int run_60, dsen2_corpus **out);
+void dsen2_corpus_destroy(dsen2_corpus *corpus);
+int dsen2_corpus_batch(const dsen2_corpus *corpus, const int *host_samples, const int *dev_samples, int n, float divisor,
+                       float *dev_x10, float *dev_x20, float *dev_x60_or_null, float *dev_y, void *stream);
+
 /* ---- evaluation: MATLAB-compatible bicubic resize and per-band errors (utils/imresize.py, testing/demoDSen2.py:31-35) ----
  * dsen2_imresize_axis  <->  imresizemex(inimg, weights, indices, dim)          utils/imresize.py:50-74
  *   One resampling pass along `axis` (0 = rows, 1 = columns) of the HWC image dev_in [H,W,C] of uint16, float32 or float64
