@@ -117,6 +117,7 @@ class S2Model(object):
         self.max_workspace_bytes = 6 << 30   # predict() and the tile path size their batches to stay below this
         self.optimizer = None                # compile() (training)
         self._train = None                   # device weights, gradient and optimizer state of a compiled model
+        self._error_work = None              # scratch of abs_sq_error_sums_device (used on the training stream alone)
 
     # -- keras.Model surface -------------------------------------------------------------------
     def count_params(self):
@@ -714,12 +715,84 @@ class S2Model(object):
         self.set_weights_flat(payload[:-2])
         return int(payload[-2:].view(np.uint64)[0])
 
-    def _end_epoch(self, epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose):
+    def abs_sq_error_sums_device(self, pred, target, out):
+        """out[0 .. 1] = (sum |pred - target|, sum (pred - target)^2) in float64, formed on the device in an order that the number
+        of elements alone fixes (dsen2_abs_sq_error_sums).  pred, target: contiguous float32 device tensors of one shape; out: a
+        contiguous float64 device tensor of two values.  Nothing is copied to the host and nothing synchronises."""
+        for t in (pred, target):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != tuple(pred.shape):
+                raise ValueError('pred and target must be contiguous float32 %s tensors of one shape' % (self.device,))
+        if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError('out must be a contiguous float64 %s tensor of two values' % (self.device,))
+        need = ctypes.c_size_t(0)
+        _lib.call('dsen2_abs_sq_error_sums_workspace_bytes', ctypes.byref(need))
+        work = self._error_work
+        if work is None or work.numel() < need.value:
+            work = self._error_work = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_abs_sq_error_sums', _ptr(pred), _ptr(target), pred.numel(), _ptr(work), work.numel(), _ptr(out),
+                      _stream_ptr(self.device))
+        return out
+
+    def _validation_rows(self, corpus, table, rows):
+        """The device validation pass over the sample rows `table` of `corpus`: chunks of preferred_batch crops are cut
+        (corpus.batch: op 0, _check_validation_crops refuses any other; divisor SCALE), go through forward_device — what predict runs — and chunk j's pair of error
+        sums lands in rows[j].  Everything is enqueued; nothing is read."""
+        from . import training
+        chunk = self._validation_chunk(corpus)
+        for j, i0 in enumerate(range(0, table.shape[0], chunk)):
+            xs, y = corpus.batch(table[i0:i0 + chunk], divisor=training.SCALE)
+            self.abs_sq_error_sums_device(self.forward_device(xs), y, rows[j])
+
+    def _validation_chunk(self, corpus):
+        return max(1, int(self.preferred_batch(corpus.patch, corpus.patch)))
+
+    @staticmethod
+    def _check_validation_crops(corpus, validation_crops):
+        table = corpus.check_table(validation_crops)
+        if table.shape[0] == 0:
+            raise ValueError('validation_crops holds no sample')
+        if (table[:, 3] != 0).any():
+            raise ValueError('validation is never augmented: every row of validation_crops must have op 0 (corpus.validation_table '
+                             'draws such rows), got ops %r' % (sorted(set(table[:, 3].tolist())),))
+        return table
+
+    def _validate_crops(self, corpus, table, plan):
+        """[val_loss, val_mean_squared_error] of the crops `table` under a data-parallel plan (world, mine), as _evaluate_shards
+        forms them: shard r = dist.shard_range(n, r, world) of the rows gives the float64 triple (sum |e|, sum e^2, elements) —
+        its chunks' pairs added in chunk order on the host — and the triples are added in rank order.  mine None: every shard
+        here; mine = r: shard r alone, the triples all-gathered."""
+        from . import dist
+        world, mine = plan
+        elements = self.cout * corpus.patch * corpus.patch
+        chunk = self._validation_chunk(corpus)
+        triples = np.zeros((world, 3), np.float64)
+        for r in range(world):
+            if mine in (None, r):
+                first, cnt = dist.shard_range(table.shape[0], r, world)
+                if cnt > 0:
+                    rows = torch.empty((-(-cnt // chunk), 2), dtype=torch.float64, device=self.device)
+                    self._validation_rows(corpus, table[first:first + cnt], rows)
+                    sa = sq = 0.0
+                    for row in rows.cpu().numpy():
+                        sa, sq = sa + row[0], sq + row[1]
+                    triples[r] = (sa, sq, float(cnt * elements))
+        if mine is not None:
+            triples = dist.all_gather_rows(torch.from_numpy(triples[mine]).to(self.device)).cpu().numpy()
+        sa = sq = cnt = 0.0
+        for t in triples:
+            sa, sq, cnt = sa + t[0], sq + t[1], cnt + t[2]
+        return [float(sa / cnt), float(sq / cnt)]
+
+    def _end_epoch(self, epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose, val=None):
         """The end of an epoch of fit and of fit_corpus alike: the epoch's losses from `sums` (the float64 sums of samples x batch
-        loss) over `count` samples, the validation pass (sharded like the steps under a data-parallel plan), the log line, the
-        callbacks, the History entry, and under a process group the check that every rank holds the same weights."""
+        loss) over `count` samples, the validation pass (sharded like the steps under a data-parallel plan; val: its two numbers
+        where fit_corpus has formed them on the device), the log line, the callbacks, the History entry, and under a process
+        group the check that every rank holds the same weights."""
         logs = {'loss': sums[0] / count, 'mean_squared_error': sums[1] / count}
-        if validation_data is not None:
+        if val is not None:
+            logs['val_loss'], logs['val_mean_squared_error'] = val
+        elif validation_data is not None:
             if plan is None:
                 vl = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size)
             else:
@@ -794,7 +867,8 @@ class S2Model(object):
         return history
 
     def fit_corpus(self, corpus, batch_size, steps_per_epoch, epochs=1, validation_data=None, seed=None, augment=False,
-                   callbacks=None, initial_epoch=0, verbose=1, shards=None, data_parallel=False, emulate_world=None):
+                   callbacks=None, initial_epoch=0, verbose=1, shards=None, data_parallel=False, emulate_world=None,
+                   validation_crops=None, masks=None):
         """fit from a corpus.TileCorpus: an epoch is steps_per_epoch batches of batch_size fresh crops, drawn by ONE
         corpus.CorpusSampler(corpus, seed, augment) and cut on the device (corpus.batch: one launch per step, the dihedral ops of
         `augment` included).  Per step the host draws the table, uploads it through page-locked memory and enqueues
@@ -806,7 +880,17 @@ class S2Model(object):
         Sharded steps: shards=K cuts every batch as train_on_batch(shards=K) does (gradient accumulation);
         data_parallel / emulate_world are fit's: every rank draws the table of the GLOBAL batch from the broadcast seed and cuts
         its dist.shard_range slice from its own copy of the corpus; the rest is _step_on_shards, which reads each step's losses
-        (these modes synchronise once per step, as fit does)."""
+        (these modes synchronise once per step, as fit does).
+        masks (default None): CorpusSampler's — one packed origin bitmap per tile (corpus.origin_masks()[0]); training crops are
+        drawn from valid origins only (free of blank cells, outside the hold-out), tiles still uniform.
+        validation_crops (default None; not together with validation_data: ValueError): an int32 [k, 4] sample table, e.g.
+        corpus.validation_table(...).  Validation then stays on the device: after the last step of an epoch the table is cut in
+        chunks of preferred_batch crops (corpus.batch, divisor SCALE), every chunk goes through forward_device on the model's own
+        plan — what predict runs: fp32 for an fp32 model, also under mixed_precision — and dsen2_abs_sq_error_sums writes chunk
+        j's (sum |e|, sum e^2) into row j of a device float64 [chunks, 2] buffer, which is read in the SAME synchronising read as
+        the epoch's training losses; nothing else reaches the host.  The host adds the rows in chunk order and divides by the
+        element count.  Under data_parallel / emulate_world the table is sharded by dist.shard_range as _evaluate_shards shards
+        its samples, and the ranks' (sum |e|, sum e^2, elements) triples are all-gathered and added in rank order."""
         from . import training
         from .corpus import CorpusSampler
         plan = self._data_parallel_plan(data_parallel, emulate_world)
@@ -819,6 +903,10 @@ class S2Model(object):
                 self.cout != corpus.cout:
             raise ValueError('the corpus (%s, run_60=%r) does not feed this model (%s, bands %r)'
                              % (corpus.device, corpus.run_60, self.device, tuple(self.bands)))
+        if validation_crops is not None and validation_data is not None:
+            raise ValueError('validation_data (host arrays) and validation_crops (a sample table, validated on the device) exclude '
+                             'each other')
+        val_table = None if validation_crops is None else self._check_validation_crops(corpus, validation_crops)
         self._train_state()
         callbacks = list(callbacks or [])
         history = training.History()
@@ -827,10 +915,19 @@ class S2Model(object):
             cb.on_train_begin()
         if plan is not None:
             seed = self._data_parallel_start(seed)
-        sampler = CorpusSampler(corpus, seed, augment)
+        sampler = CorpusSampler(corpus, seed, augment, masks=masks)
         sharded = plan is not None or shards is not None
+        chunks = 0
+        if val_table is not None and plan is None:
+            chunks = -(-val_table.shape[0] // self._validation_chunk(corpus))
+            val_elements = float(val_table.shape[0] * self.cout * corpus.patch * corpus.patch)
+        # one device buffer for everything an epoch reports: the steps' float32 loss pairs, then the validation chunks' float64
+        # pairs (8 bytes per loss pair: the float64 rows start on a multiple of 8)
+        report = torch.empty((0 if sharded else steps) * 8 + chunks * 16, dtype=torch.uint8, device=self.device)
+        if chunks:
+            val_rows = report[report.numel() - chunks * 16:].view(torch.float64).view(chunks, 2)
         if not sharded:
-            losses = torch.empty((steps, 2), dtype=torch.float32, device=self.device)
+            losses = report[:steps * 8].view(torch.float32).view(steps, 2)
             tables = torch.empty((steps, batch_size, 4), dtype=torch.int32).pin_memory()      # one slot per step of an epoch: a
             tables_dev = torch.empty((steps, batch_size, 4), dtype=torch.int32, device=self.device)   # slot is free again after the
         count = steps * batch_size                                                           # epoch's read of the losses
@@ -852,10 +949,22 @@ class S2Model(object):
                 if verbose:
                     sys.stdout.write('\rEpoch %d/%d %d/%d' % (epoch + 1, epochs, (i + 1) * batch_size, count))
                     sys.stdout.flush()
-            if not sharded:
-                for r in losses.cpu().numpy().astype(np.float64):                 # the epoch's one read
-                    sums += r * batch_size
-            self._end_epoch(epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose)
+            val = None
+            if chunks:
+                self._validation_rows(corpus, val_table, val_rows)                # enqueued behind the last step
+            if not sharded or chunks:
+                host = report.cpu().numpy()                                       # the epoch's one read
+                if not sharded:
+                    for r in host[:steps * 8].view(np.float32).reshape(steps, 2).astype(np.float64):
+                        sums += r * batch_size
+                if chunks:
+                    sa = sq = 0.0
+                    for row in host[host.size - chunks * 16:].view(np.float64).reshape(chunks, 2):
+                        sa, sq = sa + row[0], sq + row[1]
+                    val = [float(sa / val_elements), float(sq / val_elements)]
+            elif val_table is not None:
+                val = self._validate_crops(corpus, val_table, plan)
+            self._end_epoch(epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose, val=val)
             if self.stop_training:
                 break
         return history

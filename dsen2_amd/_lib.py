@@ -14,6 +14,7 @@ OK = 0
 ERR_INVALID, ERR_HIP, ERR_NO_WEIGHTS, ERR_WORKSPACE, ERR_NO_DEVICE, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6, -7
 DTYPE_U16, DTYPE_F32 = 0, 1          # dsen2_down_pixel_aggr
 DTYPE_F64 = 2                        # dsen2_imresize_axis, dsen2_band_errors
+MASK_BLANK_MAP = 3                   # dsen2_corpus_origin_mask: a blank map in place of the raster
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -98,6 +99,10 @@ SIGNATURES = {
     'dsen2_corpus_destroy': (None, [c_void_p]),
     'dsen2_corpus_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    'dsen2_corpus_origin_mask': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    'dsen2_abs_sq_error_sums_workspace_bytes': (c_int, [ctypes.POINTER(c_size_t)]),
+    'dsen2_abs_sq_error_sums': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_size_t, c_void_p, c_void_p]),
     'dsen2_down_pixel_aggr': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int,
                                       c_void_p, c_int, c_void_p]),
     'dsen2_imresize_axis': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

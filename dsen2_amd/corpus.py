@@ -21,8 +21,14 @@ low-res grid, the ORIGIN GRID:
   target           d20 at origin x 2, 32 x 32                 d60 at origin x 6, 96 x 96
 
 S2Model.fit_corpus trains from it; `python -m dsen2_amd.train --tiles` is the command line.
+
+Opt-in: which origins may be drawn.  TileCorpus(skip_blank=True) / origin_masks(holdout=, margin=) compute, on the GPU
+(dsen2_corpus_origin_mask, csrc/corpus_mask.hip), one bitmap of VALID origins per tile: an origin is valid when none of the 16 x 16
+cells of its crop is blank (a band-0 sample of the raw 10 m raster in the cell's footprint fails v >= 1) or lies within `margin`
+cells of a hold-out (validation) crop.  CorpusSampler(masks=) and validation_table(masks=) redraw what is not valid.
 """
 import ctypes
+import sys
 
 import numpy as np
 import torch
@@ -67,15 +73,145 @@ def _check_tile(index, rasters, run_60):
     return grid
 
 
+MIN_VALID_SHARE = 64          # a tile needs at least 1 valid origin in 64: the expected number of redraw rounds stays bounded
+MAX_REDRAW_ROUNDS = 10000
+
+
+def mask_shapes(grid):
+    """(cell map, packed origin bitmap) shapes of a tile whose origin grid is `grid`: one byte per cell; one bit per origin
+    (oy, ox), 0 <= oy <= grid_h - 16, 0 <= ox <= grid_w - 16, in rows padded to whole bytes."""
+    gh, gw = int(grid[0]), int(grid[1])
+    return (gh, gw), (gh - PATCH_LR + 1, (gw - PATCH_LR + 1 + 7) // 8)
+
+
+def origin_mask_device(src, grid, footprint, holdout=None, margin=0, holdout_dev=None, out=None):
+    """dsen2_corpus_origin_mask (include/dsen2_hip.h, "corpus origin mask") on device tensors.  src: the raw 10 m raster [H, W, C]
+    (float32, or int16 holding uint16 bits: patches.upload_raster), H = grid_h * footprint — or a uint8 [grid_h, grid_w] blank
+    map.  holdout: host int32 [m, 2] origins (vy, vx) whose crops, grown by `margin` cells, no valid origin's crop may touch.
+    Returns (cells, bitmap, count): uint8 [grid_h, grid_w], uint8 [grid_h - 15, ceil((grid_w - 15) / 8)] — np.packbits(valid,
+    axis=1, bitorder='little') — and int32 [1], on the device; out: the three tensors to write into.  Nothing synchronises."""
+    gh, gw = int(grid[0]), int(grid[1])
+    f = int(footprint)
+    cells_shape, bitmap_shape = mask_shapes((gh, gw))
+    if src.dtype == torch.uint8:
+        if tuple(src.shape) != cells_shape:
+            raise ValueError('a blank map of shape %r where %r is expected' % (tuple(src.shape), cells_shape))
+        dtype, h, w, c = _lib.MASK_BLANK_MAP, gh * f, gw * f, 1
+    else:
+        if src.dim() != 3 or src.dtype not in (torch.int16, torch.float32):
+            raise ValueError('the raster must be an HWC tensor of float32 or of uint16 bits (int16), got %r %s' % (tuple(src.shape), src.dtype))
+        dtype = _lib.DTYPE_U16 if src.dtype == torch.int16 else _lib.DTYPE_F32
+        h, w, c = (int(s) for s in src.shape)
+    if not src.is_contiguous():
+        raise ValueError('the raster must be contiguous')
+    if holdout is None:
+        holdout = np.zeros((0, 2), np.int32)
+    holdout = np.ascontiguousarray(holdout, dtype=np.int32)
+    if holdout.ndim != 2 or holdout.shape[1] != 2:
+        raise ValueError('hold-out origins are int32 [m, 2] (vy, vx), got shape %r' % (holdout.shape,))
+    m = holdout.shape[0]
+    if m and holdout_dev is None:
+        holdout_dev = torch.from_numpy(holdout).to(src.device)
+    if m and (tuple(holdout_dev.shape) != holdout.shape or holdout_dev.dtype != torch.int32 or not holdout_dev.is_contiguous() or
+              holdout_dev.device != src.device):
+        raise ValueError('holdout_dev must be the int32 %s copy of the hold-out origins, shape %r' % (src.device, holdout.shape))
+    if out is None:
+        out = (torch.empty(cells_shape, dtype=torch.uint8, device=src.device),
+               torch.empty(bitmap_shape, dtype=torch.uint8, device=src.device),
+               torch.empty(1, dtype=torch.int32, device=src.device))
+    cells, bitmap, count = out
+    for t, shape, dt in ((cells, cells_shape, torch.uint8), (bitmap, bitmap_shape, torch.uint8), (count, (1,), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != src.device:
+            raise ValueError('out must hold contiguous %s tensors: uint8 %r, uint8 %r and int32 (1,)' % (src.device, cells_shape, bitmap_shape))
+    if cells.data_ptr() == src.data_ptr():
+        raise ValueError('the blank map that is read and the cell map that is written must be two buffers')
+    with torch.cuda.device(src.device):
+        _lib.call('dsen2_corpus_origin_mask', patches._ptr(src), dtype, h, w, c, gh, gw,
+                  holdout.ctypes.data_as(ctypes.c_void_p) if m else None, patches._ptr(holdout_dev) if m else None, m, int(margin),
+                  patches._ptr(cells), patches._ptr(bitmap), patches._ptr(count), patches._stream(src.device))
+    return cells, bitmap, count
+
+
+def _download_masks(done):
+    """done: the (cells, bitmap, count) device tensors of origin_mask_device, one triple per tile.  ([packed bitmap on the host],
+    [count]) in ONE synchronising read: every tile's count (as its 4 bytes) and bitmap travel in one uint8 tensor."""
+    parts = [t.view(torch.uint8).reshape(-1) for _, bitmap, count in done for t in (count, bitmap)]
+    host = torch.cat(parts).cpu().numpy()
+    bitmaps, counts, at = [], [], 0
+    for _, bitmap, _ in done:
+        counts.append(int.from_bytes(host[at:at + 4].tobytes(), sys.byteorder, signed=True))
+        at += 4
+        bitmaps.append(host[at:at + bitmap.numel()].reshape(tuple(bitmap.shape)).copy())
+        at += bitmap.numel()
+    return bitmaps, counts
+
+
+def check_origin_counts(extents, counts):
+    """The stated condition of drawing with masks: a tile whose valid origins number fewer than 1 in MIN_VALID_SHARE of its
+    origins (none at all included) is refused — a redraw round then succeeds with a probability that is bounded from below."""
+    for i, ((gh, gw), n) in enumerate(zip(extents, counts)):
+        total = (int(gh) - PATCH_LR + 1) * (int(gw) - PATCH_LR + 1)
+        if int(n) * MIN_VALID_SHARE < total:
+            raise ValueError('tile %d: %d of %d origins are valid, fewer than 1 in %d: too little of the tile is left to draw crops from'
+                             % (i, int(n), total, MIN_VALID_SHARE))
+
+
+def _check_masks(extents, masks):
+    """masks: one packed origin bitmap per tile (mask_shapes; the first of the two lists TileCorpus.origin_masks returns).
+    Returns them as uint8 arrays, after check_origin_counts on their popcounts."""
+    masks = [np.ascontiguousarray(b, dtype=np.uint8) for b in masks]
+    if len(masks) != len(extents):
+        raise ValueError('%d masks for %d tiles' % (len(masks), len(extents)))
+    for i, (b, grid) in enumerate(zip(masks, extents)):
+        if b.shape != mask_shapes(grid)[1]:
+            raise ValueError('tile %d: a packed origin bitmap of shape %r where %r is expected' % (i, b.shape, mask_shapes(grid)[1]))
+    check_origin_counts(extents, [int(np.unpackbits(b).sum()) for b in masks])
+    return masks
+
+
+def _valid_rows(masks, rows):
+    """Per row (tile, oy, ox, ...) of `rows`: is the origin's bit set in its tile's bitmap."""
+    ok = np.zeros(rows.shape[0], bool)
+    for i in np.unique(rows[:, 0]):
+        sel = rows[:, 0] == i
+        oy, ox = rows[sel, 1], rows[sel, 2]
+        ok[sel] = (masks[i][oy, ox >> 3] >> (ox & 7).astype(np.uint8)) & 1
+    return ok
+
+
+def _redraw_invalid(rng, table, extents, masks):
+    """The redraw rule of drawing with masks, in place: while any sample's origin is not valid, the still-invalid sample indices
+    in ascending order get new origins — ONE integers call for their rows with the per-sample bounds, then one for their columns.
+    The tile is kept and the op is not touched."""
+    bad = np.flatnonzero(~_valid_rows(masks, table))
+    rounds = 0
+    while bad.size:
+        if rounds == MAX_REDRAW_ROUNDS:
+            raise RuntimeError('%d samples still have no valid origin after %d redraw rounds' % (bad.size, MAX_REDRAW_ROUNDS))
+        rounds += 1
+        tiles = table[bad, 0]
+        table[bad, 1] = rng.integers(0, extents[tiles, 0] - PATCH_LR)
+        table[bad, 2] = rng.integers(0, extents[tiles, 1] - PATCH_LR)
+        bad = bad[~_valid_rows(masks, table[bad])]
+    return table
+
+
 class TileCorpus(object):
     """tiles: a list of (d10, d20) HWC rasters — (d10, d20, d60) with run_60 — each uint16 or float32.
 
     Holds, per tile and on the device, the float32 low-resolution images lr10, lr20 (and lr60) and the target (d20, or d60 with
     run_60) in its own dtype: uint16 stays uint16 (as its bits in an int16 tensor) and is widened in the kernel, which is exact.
-    A 10980^2 tile is 663 MB of low-resolution images and 362 MB of uint16 target."""
+    A 10980^2 tile is 663 MB of low-resolution images and 362 MB of uint16 target.
 
-    def __init__(self, tiles, run_60=False, device=None):
+    skip_blank=True (default off): while a tile's raw 10 m raster is still on the device, its BLANK MAP is computed there
+    (origin_mask_device: a cell of the origin grid is blank when a BAND-0 sample of d10 in its footprint fails v >= 1, the
+    reference's `chan3 < 1`; no other band and no other raster is looked at) and kept, one byte per cell, with a host copy of the
+    packed bitmap of origins whose crops are free of blank cells (under 1 MB for a 10980^2 tile).  One line per tile is printed.
+    origin_masks() returns the bitmaps; CorpusSampler(masks=) and validation_table(masks=) draw from them."""
+
+    def __init__(self, tiles, run_60=False, device=None, skip_blank=False):
         self.run_60 = bool(run_60)
+        self.skip_blank = bool(skip_blank)
         self.scale = 6 if self.run_60 else 2
         self.patch = PATCH_LR * self.scale
         tiles = [tuple(t) for t in tiles]
@@ -86,11 +222,17 @@ class TileCorpus(object):
         if self.device.type == 'cuda' and self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
         self.lr, self.gt, self.gt_dtypes = [], [], []
+        self.footprint = self.scale * self.scale           # samples of d10 per cell of the origin grid, per axis
+        self.blank_cells = None                            # skip_blank: per tile, uint8 [grid_h, grid_w] on the device
+        self._blank_masks = None                           # skip_blank: ([packed bitmap on the host], [count])
+        pending = []
         want = 3 if self.run_60 else 2
-        for rasters in tiles:
+        for i, rasters in enumerate(tiles):
             lr = []
             for k in range(want):
                 t, dt = patches.upload_raster(rasters[k], self.device)
+                if k == 0 and self.skip_blank:             # d10 is still here: its blank map, before it is dropped
+                    pending.append(origin_mask_device(t, self.extents[i], self.footprint))
                 lr.append(patches.down_pixel_aggr_device(t, self.scale, dt))
                 if k == want - 1:
                     self.gt.append(t)
@@ -99,11 +241,40 @@ class TileCorpus(object):
             self.lr.append(lr)
         self.cout = BANDS[want - 1]
         self._handle = ctypes.c_void_p(0)
+        if self.skip_blank:                                # (a nearly blank tile is refused before the handle is made)
+            self.blank_cells = [cells for cells, _, _ in pending]
+            self._blank_masks = _download_masks(pending)
+            for i, (n, (gh, gw)) in enumerate(zip(self._blank_masks[1], self.extents)):
+                print('tile %d: %d of %d origins free of blank pixels' % (i, n, (gh - PATCH_LR + 1) * (gw - PATCH_LR + 1)))
+            check_origin_counts(self.extents, self._blank_masks[1])
         table = (_lib.CorpusTile * len(tiles))()
         for i, (lr, gt, dt, grid) in enumerate(zip(self.lr, self.gt, self.gt_dtypes, self.extents)):
             table[i] = _lib.CorpusTile(lr[0].data_ptr(), lr[1].data_ptr(), lr[2].data_ptr() if self.run_60 else None, gt.data_ptr(),
                                        grid[0], grid[1], _lib.DTYPE_U16 if dt == np.uint16 else _lib.DTYPE_F32)
         _lib.call('dsen2_corpus_create', table, len(tiles), int(self.run_60), ctypes.byref(self._handle))
+
+    def origin_masks(self, holdout=None, margin=0):
+        """([packed bitmap per tile], [valid origins per tile]) on the host: bit (oy, ox) of a tile's bitmap (mask_shapes;
+        np.unpackbits(b, axis=1, bitorder='little')) is set when the crop at that origin touches no blank cell (skip_blank; without
+        it nothing is blank) and no cell within `margin` cells of a hold-out crop.  holdout: int32 [k, 4] sample rows (tile, oy,
+        ox, op), as validation_table returns them; every tile's cell map is then rebuilt on the device from its blank map and the
+        rectangles of its rows.  A tile left with fewer than 1 valid origin in 64 is a ValueError (check_origin_counts)."""
+        if holdout is None and self._blank_masks is not None:
+            return list(self._blank_masks[0]), list(self._blank_masks[1])
+        holdout = np.zeros((0, 4), np.int32) if holdout is None else self.check_table(holdout)
+        if int(margin) < 0:
+            raise ValueError('margin is in cells and cannot be negative, got %d' % margin)
+        if holdout.shape[0] and (holdout[:, 0].min() < 0 or holdout[:, 0].max() >= len(self)):
+            raise ValueError('a hold-out row names a tile outside the corpus of %d' % len(self))
+        done = []
+        for i, grid in enumerate(self.extents):
+            blank = self.blank_cells[i] if self.blank_cells is not None else \
+                torch.zeros(mask_shapes(grid)[0], dtype=torch.uint8, device=self.device)
+            rows = np.ascontiguousarray(holdout[holdout[:, 0] == i, 1:3])
+            done.append(origin_mask_device(blank, grid, self.footprint, rows, int(margin)))
+        bitmaps, counts = _download_masks(done)
+        check_origin_counts(self.extents, counts)
+        return bitmaps, counts
 
     def __len__(self):
         return len(self.extents)
@@ -159,12 +330,18 @@ class TileCorpus(object):
                       patches._ptr(y), patches._stream(self.device))
         return xs, y
 
-    def validation_arrays(self, crops_per_tile, seed, chunk=256):
-        """Host arrays (xs, y) of crops_per_tile fixed crops of every tile, op 0, divided by SCALE: drawn once, from a stream of
-        their own (CorpusSampler.VAL_STREAM: the training draws of the same seed do not move), tile after tile — for each tile
-        crops_per_tile row origins, then crops_per_tile column origins — and cut by the same kernel.  For fit_corpus's
-        validation_data.  Training crops may overlap them, as the reference's random crops overlap its validation patches."""
+    def validation_table(self, crops_per_tile, seed, masks=None):
+        """The int32 [tiles * crops_per_tile, 4] sample table (tile, oy, ox, 0) of the validation crops: crops_per_tile fixed crops
+        of every tile, drawn once, from a stream of their own (CorpusSampler.VAL_STREAM: the training draws of the same seed do
+        not move), tile after tile — for each tile crops_per_tile row origins, then crops_per_tile column origins.
+        masks (the blank-only bitmaps, origin_masks()[0]): after those draws, rows whose origin is not valid are redrawn by
+        CorpusSampler's rule (ascending row order, rows then columns, until none is left).  The masks are fixed before any hold-out
+        is formed: validation crops may overlap each other, never a blank cell.
+        For fit_corpus's validation_crops, for origin_masks(holdout=), and what validation_arrays cuts."""
         CorpusSampler(self)                        # (refuses a tile without a range to draw from)
+        extents = np.asarray(self.extents, np.int64).reshape(-1, 2)
+        if masks is not None:
+            masks = _check_masks(extents, masks)
         entropy = None if seed is None else [int(seed), CorpusSampler.VAL_STREAM]
         rng = np.random.default_rng(np.random.SeedSequence(entropy))
         m = int(crops_per_tile)
@@ -173,6 +350,21 @@ class TileCorpus(object):
             table[i * m:(i + 1) * m, 0] = i
             table[i * m:(i + 1) * m, 1] = rng.integers(0, eh - PATCH_LR, size=m)
             table[i * m:(i + 1) * m, 2] = rng.integers(0, ew - PATCH_LR, size=m)
+        if masks is not None:
+            _redraw_invalid(rng, table, extents, masks)
+        return table
+
+    def validation_arrays(self, crops_per_tile, seed, chunk=256, masks=None):
+        """Host arrays (xs, y) of the crops of validation_table(crops_per_tile, seed, masks), op 0, divided by SCALE, cut by the
+        same kernel as the training batches.  For fit_corpus's validation_data.  Training crops may overlap them, as the reference's
+        random crops overlap its validation patches, unless the sampler is given origin_masks(holdout=validation_table(...))."""
+        return self.table_arrays(self.validation_table(crops_per_tile, seed, masks), chunk)
+
+    def table_arrays(self, table, chunk=256):
+        """Host arrays (xs, y) of the crops of the sample table `table` (op as given, divided by SCALE), cut on the device `chunk`
+        rows at a time.  What validation_arrays returns for validation_table's rows: a caller that also needs the table — for
+        origin_masks(holdout=) — draws it ONCE and cuts it here, so that the crops held out are the crops validated on."""
+        table = self.check_table(table)
         x_shapes, y_shape = self.output_shapes(table.shape[0])
         xs = [np.empty(s, np.float32) for s in x_shapes]
         y = np.empty(y_shape, np.float32)
@@ -202,17 +394,27 @@ class CorpusSampler(object):
     Order of the draws inside one draw(n): n tile indices (integers(0, tiles)); then n row origins, each below its tile's
     extent - 16 (one integers call with the per-sample bounds); then n column origins likewise; then, with augment only, n ops
     (integers(0, 8)).  The table is a function of the seed, the tiles' origin-grid extents and the sequence of n alone: identical
-    in every process, whatever the images hold."""
+    in every process, whatever the images hold.
+
+    masks (default None: the draws above, call for call): one packed origin bitmap per tile (TileCorpus.origin_masks()[0]).
+    draw(n) first makes the draws above; then, while any sample's origin is not valid, the still-invalid sample indices in
+    ascending order are redrawn: one integers call for their rows with the per-sample bounds, then one for their columns.  The
+    tile of a sample is kept and the ops are not touched, so tiles stay UNIFORM over the corpus: a tile is not weighted by its
+    valid area, and a half-blank tile gives as many crops as a full one, from half the ground.  The table is then a function of
+    the seed, the extents, the masks and the sequence of n.  A tile with fewer than 1 valid origin in 64 is refused here
+    (check_origin_counts), which bounds the expected number of rounds; after MAX_REDRAW_ROUNDS rounds draw raises RuntimeError
+    (it takes valid origins that all lie on the last row or column, which is never drawn)."""
     STREAM = 0x636f7270          # 'corp'
     VAL_STREAM = 0x6376616c      # 'cval'
 
-    def __init__(self, corpus, seed=None, augment=False):
+    def __init__(self, corpus, seed=None, augment=False, masks=None):
         extents = corpus.extents if hasattr(corpus, 'extents') else corpus
         self.extents = np.asarray([(int(h), int(w)) for h, w in extents], np.int64).reshape(-1, 2)
         if self.extents.shape[0] == 0 or (self.extents - PATCH_LR).min() <= 0:
             raise ValueError('origins are drawn below extent - %d: every tile needs an origin grid larger than %d x %d, got %r'
                              % (PATCH_LR, PATCH_LR, PATCH_LR, self.extents.tolist()))
         self.augment = bool(augment)
+        self.masks = None if masks is None else _check_masks(self.extents, masks)
         entropy = None if seed is None else [int(seed), self.STREAM]
         self.rng = np.random.default_rng(np.random.SeedSequence(entropy))
 
@@ -225,4 +427,6 @@ class CorpusSampler(object):
         table[:, 2] = self.rng.integers(0, self.extents[tiles, 1] - PATCH_LR)
         if self.augment:
             table[:, 3] = self.rng.integers(0, 8, size=n)
+        if self.masks is not None:
+            _redraw_invalid(self.rng, table, self.extents, self.masks)
         return table

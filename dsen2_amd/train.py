@@ -45,6 +45,13 @@ crops) and --data_parallel / --emulate_world included: every rank holds the whol
 global batch and cuts its own share, so no rank needs the training set in host memory; with more than one rank --seed is required
 (the validation crops must be the same everywhere).  The log and the checkpoint are the same files.  --tiles and a training set
 under --path exclude each other.
+With --tiles only (each without it is an error; with none of them the log and the checkpoint are the bytes they always were):
+--skip_blank draws no crop, training or validation, that touches a blank cell — a cell of the origin grid with a band-0 sample of
+the 10 m raster < 1, the reference's `chan3 < 1`; no other band is looked at — and prints how many origins each tile keeps;
+--holdout [--holdout_margin K] keeps the training crops out of the validation crops (and K cells around them); --val_on_device
+validates from the table of validation crops on the GPU and builds no host arrays.  Tiles stay uniform: a tile is not weighted by
+its valid area; a tile left with fewer than 1 valid origin in 64 is refused.  Under --data_parallel every rank builds the same
+masks from its own copy of the corpus and the same --seed.
 
     python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] --path P
 is that script's predict branch (--self_ensemble, not in the reference: predict(ensemble=True), the mean over the 8 flips and
@@ -99,6 +106,14 @@ def parse_args(argv=None):
                    help='With --tiles: batches per epoch (default: 8000 crops per tile, 500 with --run_60, over the batch size).')
     p.add_argument('--val_crops', type=int, default=None, metavar='M',
                    help='With --tiles: fixed validation crops per tile (default 800, 50 with --run_60).')
+    p.add_argument('--skip_blank', action='store_true',
+                   help='With --tiles: draw no crop (training or validation) that touches a blank cell: band 0 of the 10 m raster < 1.')
+    p.add_argument('--holdout', action='store_true',
+                   help='With --tiles: keep the training crops out of the validation crops (no training crop overlaps one).')
+    p.add_argument('--holdout_margin', type=int, default=None, metavar='K',
+                   help='With --holdout: also keep K cells of the origin grid around every validation crop free (default 0).')
+    p.add_argument('--val_on_device', action='store_true',
+                   help='With --tiles: validate from the table of validation crops on the GPU; no host arrays are built.')
     p.add_argument('--self_ensemble', action='store_true',
                    help='With --predict: average the predictions for the 8 flips and rotations of every patch (~8x the network time).')
     args = p.parse_args(argv)
@@ -108,6 +123,10 @@ def parse_args(argv=None):
         p.error('--self_ensemble is an option of --predict')
     if args.tiles is None and (args.steps_per_epoch is not None or args.val_crops is not None):
         p.error('--steps_per_epoch and --val_crops are options of --tiles')
+    if args.tiles is None and (args.skip_blank or args.holdout or args.val_on_device or args.holdout_margin is not None):
+        p.error('--skip_blank, --holdout, --holdout_margin and --val_on_device are options of --tiles')
+    if args.holdout_margin is not None and (not args.holdout or args.holdout_margin < 0):
+        p.error('--holdout_margin K (K >= 0) is an option of --holdout')
     if args.tiles is not None and args.predict_file:
         p.error('--tiles is an option of training: it cannot be combined with --predict')
     if args.tiles is not None and ((args.steps_per_epoch is not None and args.steps_per_epoch < 1) or
@@ -166,6 +185,21 @@ def tiles_conflict(args, path):
     if args.tiles is not None and found:
         return TILES_AND_PATH.format(train_dir, len(found), 'y' if len(found) == 1 else 'ies')
     return None
+
+
+def tiles_validation(corpus, args, crops_per_tile, say=print):
+    """(validation table, training masks or None, validation host arrays or None) of a --tiles run.  The table is drawn ONCE
+    (without --seed it comes from fresh entropy: a second draw would be other crops) and everything is derived from that one table:
+    the hold-out masks of --holdout, the host arrays (cut from it, unless --val_on_device) and fit_corpus's validation_crops.  Every
+    rank builds the same masks from its own copy of the corpus and the same --seed."""
+    blank = corpus.origin_masks()[0] if args.skip_blank else None
+    masks = blank
+    val_table = corpus.validation_table(crops_per_tile, args.seed, blank)
+    if args.holdout:
+        masks, left = corpus.origin_masks(holdout=val_table, margin=args.holdout_margin or 0)
+        say('Hold-out: training crops are drawn from {} origins outside the validation crops.'.format(sum(left)))
+    arrays = None if args.val_on_device else corpus.table_arrays(val_table)
+    return val_table, masks, arrays
 
 
 def main(argv=None):
@@ -244,13 +278,22 @@ def run(args, rank, world):
             if opened is None:
                 return 2
             rasters.append(opened)
-        corpus = corpus_mod.TileCorpus(rasters, run_60=args.run_60, device=model.device)
+        if args.skip_blank and rank != 0:                        # (one rank talks: the others build the same masks quietly)
+            import contextlib
+            with open(os.devnull, 'w') as quiet, contextlib.redirect_stdout(quiet):
+                corpus = corpus_mod.TileCorpus(rasters, run_60=args.run_60, device=model.device, skip_blank=True)
+        elif args.skip_blank:
+            corpus = corpus_mod.TileCorpus(rasters, run_60=args.run_60, device=model.device, skip_blank=True)
+        else:
+            corpus = corpus_mod.TileCorpus(rasters, run_60=args.run_60, device=model.device)
         del rasters
         nr_crop = 500 if args.run_60 else 8000
         steps = args.steps_per_epoch or max(1, len(corpus) * nr_crop // batch_size)
-        val_tr, val_lb = corpus.validation_arrays(args.val_crops or nr_crop // 10, args.seed)
+        val_table, masks, val_arrays = tiles_validation(corpus, args, args.val_crops or nr_crop // 10, say)
+        if val_arrays is not None:
+            val_tr, val_lb = val_arrays
         say('Holding {} tile{} ({:.1f} MB on the GPU): {} steps of {} crops per epoch, {} crops for validation.'
-            .format(len(corpus), '' if len(corpus) == 1 else 's', corpus.nbytes / 1e6, steps, batch_size, val_lb.shape[0]))
+            .format(len(corpus), '' if len(corpus) == 1 else 's', corpus.nbytes / 1e6, steps, batch_size, val_table.shape[0]))
     else:
         say('Loading the training data...')
         train, label, val_tr, val_lb = training.load_training_data(path, args.run_60, training.SCALE)
@@ -273,9 +316,14 @@ def run(args, rank, world):
                                                     cooldown=20, min_lr=1e-5)]
     say('Training starts...')
     if corpus is not None:
-        model.fit_corpus(corpus, batch_size, steps, epochs=args.epochs, validation_data=(val_tr, val_lb), seed=args.seed,
-                         augment=args.augment, callbacks=callbacks, verbose=int(rank == 0), data_parallel=args.data_parallel,
-                         emulate_world=args.emulate_world)
+        extra = {}                              # (without the new flags: the call as it always was)
+        if masks is not None:
+            extra['masks'] = masks
+        if args.val_on_device:
+            extra['validation_crops'] = val_table
+        model.fit_corpus(corpus, batch_size, steps, epochs=args.epochs, validation_data=None if args.val_on_device else (val_tr, val_lb),
+                         seed=args.seed, augment=args.augment, callbacks=callbacks, verbose=int(rank == 0),
+                         data_parallel=args.data_parallel, emulate_world=args.emulate_world, **extra)
         say('best weights: {}\nlog: {}'.format(ckpt, log_path))
         return 0
     model.fit(x=train, y=label, batch_size=batch_size, epochs=args.epochs, verbose=int(rank == 0), callbacks=callbacks,

@@ -440,6 +440,52 @@ void dsen2_corpus_destroy(dsen2_corpus *corpus);
 int dsen2_corpus_batch(const dsen2_corpus *corpus, const int *host_samples, const int *dev_samples, int n, float divisor,
                        float *dev_x10, float *dev_x20, float *dev_x60_or_null, float *dev_y, void *stream);
 
+/* ---- corpus origin mask: which crop origins of a tile may be drawn (csrc/corpus_mask.hip) -------------------------------------------
+ * Definitions, for ONE tile whose origin grid is grid_h x grid_w (as dsen2_corpus_tile has it):
+ *   CELL FOOTPRINT  with S = 2 (run_60: 6), one cell of the origin grid covers F x F samples of the raw 10 m raster d10 [H, W, C],
+ *                   F = S * S (4, or 36 for run_60): H = grid_h * F, W = grid_w * F.
+ *   BLANK CELL      any BAND-0 sample v of d10 in the cell's footprint fails v >= 1 — the reference's `chan3 < 1` test on the same
+ *                   band (training/create_patches.py:208-211); a NaN of a float32 raster counts as blank.  No other band is read.
+ *   COVERED CELL    the cell lies inside [vy - margin, vy + 16 + margin) x [vx - margin, vx + 16 + margin) for some hold-out origin
+ *                   (vy, vx); margin >= 0 is in cells.  With margin 0, "the window of origin (oy, ox) contains a covered cell" is
+ *                   exactly "the crop at (oy, ox) overlaps the crop at a hold-out origin".
+ *   VALID ORIGIN    (oy, ox), 0 <= oy <= grid_h - 16, 0 <= ox <= grid_w - 16, is valid when no cell of [oy, oy + 16) x [ox, ox + 16)
+ *                   is blank or covered.
+ * dsen2_corpus_origin_mask writes
+ *   dev_bitmap  one bit per origin: grid_h - 15 rows of ceil((grid_w - 15) / 8) bytes, bit k of byte b = origin column 8 b + k
+ *               (least significant bit first), set when the origin is valid, the padding bits of a row's last byte 0: exactly
+ *               np.packbits(valid, axis=1, bitorder='little');
+ *   dev_count   the number of valid origins (one int32);
+ *   dev_cells   scratch of grid_h * grid_w bytes, which holds the cell map afterwards (1 = blank or covered, else 0): with m == 0
+ *               it is the BLANK MAP, which a later call may be given in place of the raster.
+ * dev_src: the raster d10 in device memory, uint16 (DSEN2_DTYPE_U16) or float32 (DSEN2_DTYPE_F32), any C >= 1 — or, with dtype ==
+ *   DSEN2_MASK_BLANK_MAP, a blank map [grid_h, grid_w] of bytes (non-zero = blank; all zero: nothing is blank), H, W and C as they
+ *   were for the raster; dev_src and dev_cells must then not be the same buffer.
+ * host_holdout / dev_holdout: the same [m, 2] int32 table of hold-out origins (vy, vx) in host and in device memory, as
+ *   dsen2_corpus_batch takes its samples: the host copy is checked, the device copy is read (a rectangle is clipped to the grid on
+ *   the device, so no table can make the kernel write outside dev_cells).  Both may be NULL when m == 0.
+ * Two launches on `stream`, three with m > 0 (the count is formed inside the last), integer work only (flags, ORs, wave ballots, an integer count; no float arithmetic, no float
+ *   atomics): the result depends on the inputs alone.  Nothing synchronises.
+ * DSEN2_ERR_INVALID with nothing launched: a NULL pointer, an unknown dtype, C < 1, grid_h or grid_w below 16 (or above 2^15 = 32768: the number of origins, (grid_h - 15) * (grid_w - 15), then fits the int32 count), H or
+ *   W not grid * F, F other than 4 or 36, m or margin negative (or above 2^24 / 2^20), a table missing with m > 0, a hold-out origin
+ *   outside [0, grid - 16]. */
+#define DSEN2_MASK_BLANK_MAP 3
+int dsen2_corpus_origin_mask(const void *dev_src, int dtype, int H, int W, int C, int grid_h, int grid_w, const int *host_holdout,
+                             const int *dev_holdout, int m, int margin, unsigned char *dev_cells, unsigned char *dev_bitmap,
+                             int *dev_count, void *stream);
+
+/* dsen2_abs_sq_error_sums (csrc/error_sums.hip): dev_out[0 .. 1] = { sum |p - t|, sum (p - t)^2 } over `count` float32 pairs, as
+ *   float64: what a validation pass needs of a prediction that is already on the device.  Every difference, product and sum is
+ *   float64 and rounded on its own (no FMA).  The order of every addition is fixed by `count` alone: blocks = clamp(ceil(count /
+ *   2048), 1, 4096) workgroups of 256 threads; thread t of workgroup b adds elements b * 256 + t, + blocks * 256, ... in index
+ *   order (|d| and d * d onto 0.0); the workgroup adds its threads in a halving tree (128, 64, ... 1); one workgroup adds the
+ *   partial pairs likewise (thread t: partials t, t + 256, ...; then the tree).  The grid never depends on the device: the same
+ *   bits on every run and every GPU.  dev_work: dsen2_abs_sq_error_sums_workspace_bytes() bytes of device scratch.
+ *   DSEN2_ERR_INVALID: a NULL pointer, count <= 0 or >= 2^31; DSEN2_ERR_WORKSPACE: a workspace that is too small. */
+int dsen2_abs_sq_error_sums_workspace_bytes(size_t *bytes);
+int dsen2_abs_sq_error_sums(const float *dev_pred, const float *dev_target, long long count, void *dev_work, size_t work_bytes,
+                            double *dev_out, void *stream);
+
 /* ---- evaluation: MATLAB-compatible bicubic resize and per-band errors (utils/imresize.py, testing/demoDSen2.py:31-35) ----
  * dsen2_imresize_axis  <->  imresizemex(inimg, weights, indices, dim)          utils/imresize.py:50-74
  *   One resampling pass along `axis` (0 = rows, 1 = columns) of the HWC image dev_in [H,W,C] of uint16, float32 or float64

@@ -17,6 +17,17 @@
         one epoch of `steps` steps of one path and nothing else, for `rocprofv3 --memory-copy-trace` (a run without counters): the
         copies per step are the difference of two runs with different `steps` over the difference of the steps (the set-up —
         weights, the corpus — is the same in both).
+    python tools/bench_fit_corpus.py --mode mask [--iters N]
+        dsen2_corpus_origin_mask on a full tile's raw 10 m raster (10980 x 10980 x 4 uint16, origin grid 2745 x 2745): HIP events
+        around `iters` calls (two launches each; three with a hold-out table), beside the HBM bound of the bytes it must touch — the whole raster, since band 0
+        shares its sectors with the other bands — and the same entry rebuilding the mask from the kept blank map with the 800
+        hold-out crops of train.py's default.
+    python tools/bench_fit_corpus.py --mode validation [--crops M]
+        the end of an epoch with validation on the device (fit_corpus(validation_crops=T)) against the host-array path
+        (validation_data=corpus.validation_arrays(...): evaluate -> predict, an upload and a download of every crop) for the SAME
+        M crops per tile of 4 tiles: wall time of fits of one step per epoch, alternated, minus the same fit without validation,
+        per epoch; beside the time of the forward passes alone — in the device pass's chunks, and at the training batch, which is
+        what the host path's predict runs them at — and the bytes the host path moves over the bus.
 """
 import argparse
 import json
@@ -181,9 +192,66 @@ def mode_copies(path, steps, batch=128):
     print(json.dumps(dict(mode='copies', path=path, steps=steps, batch=batch)), flush=True)
 
 
+def mode_mask(iters):
+    grid, f, c = (2745, 2745), 4, 4
+    raster = torch.randint(200, 12000, (grid[0] * f, grid[1] * f, c), dtype=torch.int16, device=DEV)       # uint16 bits
+    raster[:, :3000, 0] = 0                                          # a blank strip, as a partial swath has
+    out = corpus.origin_mask_device(raster, grid, f)
+    blank = out[0].clone()
+    valid = int(out[2].cpu())
+    rng = np.random.default_rng(0)
+    holdout = np.ascontiguousarray(rng.integers(0, grid[0] - 16, (800, 2)), dtype=np.int32)
+    holdout_dev = torch.from_numpy(holdout).to(DEV)
+    rounds = []
+    for _ in range(3):                                               # alternated: from the raster, from the blank map
+        rounds.append((timed(lambda: corpus.origin_mask_device(raster, grid, f, out=out), iters),
+                       timed(lambda: corpus.origin_mask_device(blank, grid, f, holdout, 0, holdout_dev=holdout_dev, out=out), iters)))
+    cells, bitmap = out[0].numel(), out[1].numel()
+    raster_bytes = raster.numel() * 2
+    moved = raster_bytes + cells + cells * 2 + bitmap                # the raster once; the cell map written, then read by the window
+    ms = min(a for a, _ in rounds)
+    print(json.dumps(dict(mode='mask', raster=list(raster.shape), dtype='uint16', origin_grid=list(grid), valid_origins=valid,
+                          raster_bytes=raster_bytes, band0_bytes=raster_bytes // c, bitmap_bytes=bitmap, bytes_moved=moved,
+                          hbm_bound_us=round(moved / HBM_PEAK * 1e6, 1), from_raster_call_us=[round(a * 1e3, 1) for a, _ in rounds],
+                          achieved_tb_s=round(moved / (ms * 1e-3) / 1e12, 3), fraction_of_hbm_peak=round(moved / (ms * 1e-3) / HBM_PEAK, 3),
+                          from_blank_map_800_holdout_call_us=[round(b * 1e3, 1) for _, b in rounds])), flush=True)
+
+
+def mode_validation(crops, batch=128):
+    c = make_corpus(False)
+    table = c.validation_table(crops, 1)
+    arrays = c.validation_arrays(crops, 1)
+    m = _model('fp32', None)
+    epochs = 3
+    chunk = m._validation_chunk(c)
+    xs, y = c.batch(table[:chunk])
+    forward_ms = timed(lambda: m.forward_device(xs), 5) * (table.shape[0] / float(xs[0].shape[0]))
+    xs_b = [t[:batch].contiguous() for t in xs]                      # the host path's predict runs its forwards at the training batch
+    forward_b_ms = timed(lambda: m.forward_device(xs_b), 10) * (table.shape[0] / float(batch))
+    runs = {'none': {}, 'host_arrays': dict(validation_data=arrays), 'device': dict(validation_crops=table)}
+    walls = {k: [] for k in runs}
+    for name in ('none', 'host_arrays', 'device') * 3:                 # alternated, three rounds; the first is the warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m.fit_corpus(c, batch, 1, epochs=epochs, seed=1, verbose=0, **runs[name])
+        torch.cuda.synchronize()
+        walls[name].append((time.perf_counter() - t0) * 1e3 / epochs)
+    per_epoch = {k: [round(v, 2) for v in w[1:]] for k, w in walls.items()}
+    base = min(walls['none'][1:])
+    crop_bytes = sum(a[0].nbytes for a in arrays[0]) + arrays[1][0].nbytes     # inputs up, ...
+    pred_bytes = arrays[1][0].nbytes                                          # ... predictions down
+    print(json.dumps(dict(mode='validation', tiles=len(c), crops=int(table.shape[0]), train_batch=batch, device_chunk=int(chunk),
+                          epoch_ms=per_epoch, epoch_end_ms={k: round(min(walls[k][1:]) - base, 2) for k in ('host_arrays', 'device')},
+                          forwards_alone_ms=round(forward_ms, 2), forwards_at_train_batch_ms=round(forward_b_ms, 2),
+                          host_path_bus_bytes=int(table.shape[0] * (crop_bytes - arrays[1][0].nbytes + pred_bytes)),
+                          host_arrays_bytes=int(table.shape[0] * crop_bytes), device_path_bus_bytes=int(table.nbytes + 16 * -(-table.shape[0] // chunk)))),
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--mode', required=True, choices=['kernel', 'epoch', 'copies'])
+    ap.add_argument('--mode', required=True, choices=['kernel', 'epoch', 'copies', 'mask', 'validation'])
+    ap.add_argument('--crops', type=int, default=800)
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--path', default='corpus', choices=['corpus', 'host'])
@@ -192,6 +260,10 @@ def main():
         mode_kernel(args.iters)
     elif args.mode == 'epoch':
         mode_epoch(args.steps or 200)
+    elif args.mode == 'mask':
+        mode_mask(min(args.iters, 20))
+    elif args.mode == 'validation':
+        mode_validation(args.crops)
     else:
         mode_copies(args.path, args.steps or 5)
 
