@@ -543,8 +543,8 @@ int dsen2_model_create(dsen2_model** out, int c10, int c20, int c60, int num_lay
       return fail(DSEN2_ERR_INVALID, "precision %d unknown (0 = fp32, 1 = bf16 operands, 2 = bf16x3)", precision);
     const int cin = c10 + c20 + c60;
     const int cout = c60 > 0 ? c60 : c20;   // utils/DSen2Net.py:35 — input_shape[-1][0]
+    // (cout <= cin - 1 <= 15: inside what the output layer's plan takes, 32)
     if (cin > 16) return fail(DSEN2_ERR_INVALID, "%d input channels > 16", cin);
-    if (cout > 32) return fail(DSEN2_ERR_INVALID, "%d output channels > 32", cout);
     dsen2_model* m = new (std::nothrow) dsen2_model();
     if (!m) return fail(DSEN2_ERR_INVALID, "out of host memory");
     m->c10 = c10; m->c20 = c20; m->c60 = c60; m->cin = cin; m->cout = cout;

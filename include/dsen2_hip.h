@@ -51,8 +51,12 @@ int dsen2_device_count(void);
 /* ---- network object -------------------------------------------------------------------------
  * dsen2_model_create  <->  s2model(input_shape, num_layers, feature_size)   utils/DSen2Net.py:18-43
  *   c10/c20/c60: channel counts of the 10 m / 20 m / 60 m inputs (c60 = 0 for the 2-input net).
- *   The output has the channel count of the last input and that input is added back (:35-41).
- *   feature_size must be a multiple of 128 (reference uses 128 and 256, testing/supres.py:56,59).
+ *   Accepted: c10 >= 1, c20 >= 1, c60 >= 0, c10 + c20 + c60 <= 16 (the first convolution reads the concatenated inputs as 16
+ *   channel lanes, the unused ones zero), num_layers >= 0; anything else is DSEN2_ERR_INVALID and *out stays NULL.
+ *   The output has the channel count of the last input and that input is added back (:35-41): so at most 15 output channels
+ *   through a model (the single-layer entry dsen2_conv3x3_nhwc takes up to 32).  The Sentinel-2 groupings 4 + 6 (+ 2) have
+ *   first-layer kernels of their own; every other grouping runs a generic one (tests/test_gpu_band_groups.py).
+ *   feature_size must be 128 or 256 (what the reference uses, testing/supres.py:56,59).
  *   precision: 0 = fp32 everywhere (exact-f32 MFMA); 1 = bf16 operands for the residual-block convolutions
  *   (v_mfma_f32_16x16x32_bf16), fp32 accumulation, an exact fp32 residual stream (kept as two 16-bit planes, see
  *   dsen2_split_f32), the FIRST convolution in the same arithmetic (bf16 operands, fp32 accumulate: dsen2_conv3x3_first_planes;
@@ -258,7 +262,8 @@ int dsen2_model_time_body_conv(dsen2_model *m, int layer, const float *dev_in, c
  *     holds: weights rounded to bf16, round to nearest even) are rebuilt from the master vector after every
  *     dsen2_model_set_weights_device / dsen2_model_load_weights, next to the model's own fp32 buffers;
  *   - dev_out_or_NULL receives the forward of a precision-1 model with the same weights run layer by layer: the first
- *     convolution on bf16(x), bf16(w) (round to nearest even); each block t = bf16(relu(convA(hi(x)) + b)) (nearest even),
+ *     convolution on bf16(x), bf16(w) (round to nearest even; band groups other than 4 + 6 (+ 2): in fp32, as in every
+ *     precision-1 model, dsen2_model_create); each block t = bf16(relu(convA(hi(x)) + b)) (nearest even),
  *     x += 0.1 * (convB(t) + b) in fp32, hi(x) = the stream's operand plane (u + 0x8000) >> 16 of the fp32 bit pattern u
  *     (nearest, ties away from zero); the output convolution in fp32;
  *   - backward through the blocks, g = dL/dx in fp32: dWB = 0.1 * wgrad(t, hi(g)), dbB = 0.1 * sum hi(g),
@@ -299,8 +304,9 @@ int dsen2_model_time_body_conv(dsen2_model *m, int layer, const float *dev_in, c
  *   count, a count >= 2^24, a zero total, shard_stride < count, a NULL pointer.
  * dsen2_conv3x3_wgrad: the weight-gradient kernel alone (kernel-level tests): dev_dw (3,3,ci,co) = scale * sum over all pixels
  *   of a[p + tap][c] g[p][o], dev_db [co] = scale * sum g[p][o]; dev_a NHWC [n,h,w,ca], dev_g NHWC [n,h,w,cg]; ci <= ca, co <= cg.
- *   Shapes: cg a multiple of 128 (ca a multiple of 4), or cg <= 32 with ca a multiple of 128.  Allocates its scratch and
- *   synchronises (test path). */
+ *   Shapes: cg a multiple of 128 (ca a multiple of 4), or cg <= 32 with ca a multiple of 128.  Lanes ci .. ca-1 of dev_a and
+ *   co .. cg-1 of dev_g are read but reach neither dev_dw nor dev_db (each element of dW sums the products of ONE lane of a with
+ *   ONE lane of g): they may hold anything.  Allocates its scratch and synchronises (test path). */
 int dsen2_model_train_workspace_bytes(const dsen2_model *m, int n, int h, int w, size_t *bytes);
 int dsen2_model_gradients(dsen2_model *m, const float *x10, const float *x20, const float *x60, const float *target,
                           float *dev_out_or_NULL, float *dev_grad_flat, float *dev_loss2, int n, int h, int w, void *ws,

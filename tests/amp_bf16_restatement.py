@@ -5,7 +5,8 @@ kernels: every convolution accumulates in float64; what is restated is WHERE ope
   weights, the first convolution's inputs, t_l and du    round to nearest even            (bf16_rne_bits)
   the hi plane of a residual stream (x_l, g)             (u + 0x8000) >> 16, ties away    (bf16_hi_bits)
 
-  forward   x_0 = relu(conv(r(x), r(W0)) + b0);  t_l = r(relu(conv(hi(x_{l-1}), r(WA)) + bA));
+  forward   x_0 = relu(conv(r(x), r(W0)) + b0) (band groups other than 4 + 6 (+ 2): x and W0 unrounded);
+            t_l = r(relu(conv(hi(x_{l-1}), r(WA)) + bA));
             x_l = x_{l-1} + 0.1 * (conv(t_l, r(WB)) + bB);  out = conv(x_d, W_out) + b_out + skip   (unrounded)
   backward  g = dL/dx_l:  dWB = 0.1 * wgrad(t_l, hi(g)), dbB = 0.1 * sum hi(g), du = r([t_l > 0] * 0.1 * conv_T(hi(g), r(WB))),
             dWA = wgrad(hi(x_{l-1}), du), dbA = sum du, g += conv_T(du, r(WA));
@@ -138,7 +139,10 @@ def forward(xs, ps, d, emulate, pre=None):
     """xs: float64 NCHW tensors; pre (a list) receives every ReLU input."""
     r, h = (rne, hi) if emulate else (_identity, _identity)
     keep = pre.append if pre is not None else (lambda v: None)
-    v = _FirstConv.apply(torch.cat(xs, 1), ps[0], ps[1], r, r)
+    # the first convolution of a precision-1 model runs on bf16 operands for the band groups 4 + 6 (+ 2) only; any other
+    # grouping's is fp32 (include/dsen2_hip.h: dsen2_model_create), and the training step runs that model's forward
+    r0 = r if tuple(int(x.shape[1]) for x in xs) in ((4, 6), (4, 6, 2)) else _identity
+    v = _FirstConv.apply(torch.cat(xs, 1), ps[0], ps[1], r0, r0)
     keep(v)
     x = torch.relu(v)
     for l in range(d):

@@ -107,9 +107,15 @@ def test_conv_out_skip_nchw_matches_oracle(feat, cout, n, h, w):
 # and shapes it hands to the vector-unit kernel (Cout 7, a row of Q too wide for LDS)
 OUT_SHAPES = [(128, 6, 1, 128, 128), (128, 2, 1, 50, 192), (128, 6, 3, 40, 70), (256, 6, 1, 33, 64), (128, 5, 2, 7, 31),
               (128, 3, 1, 1, 1), (256, 2, 2, 67, 33), (128, 6, 1, 70, 97), (128, 7, 1, 20, 40), (128, 6, 1, 9, 230)]
+# the channel counts a model of another band grouping brings (tests/test_gpu_band_groups.py), at small ragged shapes: Cout 1
+# (out_mfma<F, 1> with one output), 4 (out_mfma<F, 3>, not a multiple of 3), 8 (the vector-unit kernel's last slot); and 9, 15, 16, 32:
+# beyond the output kernels, the tile kernel's kEpiSkipNCHW instance (conv3x3_mfma.hip, cout_pad 32) with its Cout tail
+OUT_SHAPES += [(128, cout, n, h, w) for cout in (1, 4, 8) for n, h, w in ((2, 7, 31), (1, 20, 40))] + [(128, 1, 1, 1, 1), (256, 4, 2, 7, 31)]
+OUT_TILE_SHAPES = [(128, cout, n, h, w) for cout in (9, 15, 16, 32) for n, h, w in ((2, 7, 31), (1, 20, 40))] + \
+    [(128, 32, 1, 1, 1), (256, 15, 2, 7, 31), (256, 9, 1, 20, 40)]
 
 
-@pytest.mark.parametrize('feat,cout,n,h,w', OUT_SHAPES)
+@pytest.mark.parametrize('feat,cout,n,h,w', OUT_SHAPES + OUT_TILE_SHAPES)
 def test_conv_out_shapes_match_oracle(feat, cout, n, h, w):
     rng = np.random.default_rng(feat + cout + h)
     x = _rand(rng, (n, feat, h, w))
@@ -122,19 +128,29 @@ def test_conv_out_shapes_match_oracle(feat, cout, n, h, w):
     assert y.shape == (n, cout, h, w)
     # (Cout 7-8 and rows of Q too wide for LDS go to the vector-unit kernel: conv3x3_out.hip)
     kind = 'out_valu' if cout > 6 or w > 224 else 'out'
+    # Cout 9-32: the tile kernel, gated as its body convolution at the same Cin (the same contraction over 9 * Cin products in
+    # the same order; only the epilogue differs, and it adds one rounding of the sum with the skip input)
+    kind = 'relu' if cout > 8 else kind
     _check(y, ref, kind, feat, '%dx%dx%d->%d' % (n, h, w, cout))      # incl. max: no single pixel off (a block edge, a strip's first row)
 
 
-@pytest.mark.parametrize('feat,cout,h,w', [(128, 6, 32, 32), (128, 6, 45, 100), (128, 2, 40, 192), (256, 6, 20, 64)])
+@pytest.mark.parametrize('feat,cout,h,w', [(128, 6, 32, 32), (128, 6, 45, 100), (128, 2, 40, 192), (256, 6, 20, 64),
+                                           (128, 1, 20, 40), (128, 4, 20, 40), (128, 8, 20, 40), (128, 15, 20, 40), (128, 32, 20, 40),
+                                           (256, 15, 7, 31)])
 def test_conv_out_delta_kernels_shift_exactly(feat, cout, h, w):
     """Known-answer for the output convolution: a one-hot kernel copies a shifted input channel bit-exactly into ONE
-    output channel (zero outside the image, across every block edge and strip boundary), bias and skip added after."""
+    output channel (zero outside the image, across every block edge and strip boundary), bias and skip added after.
+    Cout 1, 4, 8 (the output kernels' other channel counts) and 15, 32 (the tile kernel's kEpiSkipNCHW instance): every output
+    channel in turn, the nine taps and the input channels going round."""
     rng = np.random.default_rng(h + w)
     x = _rand(rng, (1, feat, h, w))
     from dsen2_amd.DSen2Net import conv3x3_nhwc
     zero = torch.zeros(1, cout, h, w, device='cuda')
-    for dy, dx, ci, co in [(0, 0, 3, cout - 1), (2, 1, feat - 1, 0), (1, 1, feat // 2, 1), (0, 2, 31, 0), (2, 2, 64, cout - 1),
-                           (1, 0, 95, 1), (2, 0, 7, 0)]:
+    cases = [(0, 0, 3, cout - 1), (2, 1, feat - 1, 0), (1, 1, feat // 2, 1), (0, 2, 31, 0), (2, 2, 64, cout - 1), (1, 0, 95, 1), (2, 0, 7, 0)]
+    if cout not in (2, 6):
+        cases = [((co + co // 3) % 3, co % 3, (37 * co + 5) % feat, co) for co in range(cout)]
+        assert [c[3] for c in cases] == list(range(cout))
+    for dy, dx, ci, co in cases:
         k = np.zeros((3, 3, feat, cout), np.float32); k[dy, dx, ci, co] = 1
         y = conv3x3_nhwc(_nhwc(x), k, np.zeros(cout, np.float32), epilogue=2, aux=zero).cpu().numpy()
         exp = np.zeros((h, w), np.float32)
