@@ -55,7 +55,7 @@ static bool may_chain(const dsen2_model* m) {
 }
 
 // DSen2Net.py:24-29: Concatenate + Conv2D + ReLU.  Leaves the residual stream where the body reads it: fp32 B.a (precision 0,
-// or no residual blocks), the planes (B.hi, B.lo) (precision 1) or (B.hx, B.lo16) (precision 2).
+// or no residual blocks) or the 16-bit tensors (B.s0, B.s1) (precision 1 / 2).
 static int first_layer(const dsen2_model* m, const float* x10, const float* x20, const float* x60, int n, int h, int w,
                        const ForwardWs& B, bool x0_packed, hipStream_t stream) {
   const Layer& L = m->layers[0];
@@ -65,8 +65,8 @@ static int first_layer(const dsen2_model* m, const float* x10, const float* x20,
   ConvParams pf = make_params(B.x0, L.weights(P), L.bias(P), nullptr, B.a, n, h, w, 0, 0.f);
   if (pl.epilogue == kEpiReluSplit) {
     // a precision-1 model's first convolution writes the residual stream directly as its two blocked 16-bit planes
-    pf.out = reinterpret_cast<float*>(B.hi);
-    pf.out2 = B.lo;
+    pf.out = reinterpret_cast<float*>(B.s0);
+    pf.out2 = B.s1;
   }
   // the direct kernels read the NCHW inputs themselves; other channel counts, and the reference structure, pack them to
   // NHWC16 first
@@ -79,8 +79,8 @@ static int first_layer(const dsen2_model* m, const float* x10, const float* x20,
     // precision 1 / 2: on the bf16 matrix cores, writing the residual stream's planes itself (conv3x3_first16.hip) —
     // precision 1: (hi, lo); precision 2: hx (hi | xl planes) and lo16
     pd.wpk = L.first16(P);
-    pd.out = reinterpret_cast<float*>(x3 ? B.hx : B.hi);
-    pd.out2 = x3 ? B.lo16 : B.lo;
+    pd.out = reinterpret_cast<float*>(B.s0);
+    pd.out2 = B.s1;
     HIP_TRY(try_launch(launch_conv3x3_first16(pd, fi, m->feat, x3, stream), &done));
   } else if (pl.first_direct) {
     HIP_TRY(try_launch(launch_conv3x3_first(pd, fi, m->feat, pl.epilogue, stream, m->tune.first_ablate), &done));
@@ -88,7 +88,7 @@ static int first_layer(const dsen2_model* m, const float* x10, const float* x20,
   if (!done) {
     if (!x0_packed) HIP_TRY(launch_pack_inputs(x10, x20, x60, m->c10, m->c20, m->c60, B.x0, n, h, w, stream));
     HIP_TRY(launch(pl, pf, pl.epilogue, m->tune, stream));
-    if (x3) HIP_TRY(launch_split3_f32(B.a, B.hx, B.lo16, n, h, w, m->feat, stream));   // (generic first layer: fp32 `a`)
+    if (x3) HIP_TRY(launch_split3_f32(B.a, B.s0, B.s1, n, h, w, m->feat, stream));   // (generic first layer: fp32 `a`)
   }
   return DSEN2_OK;
 }
@@ -145,9 +145,8 @@ static int body16(const dsen2_model* m, void* s0, void* s1, void* t16, float* ou
 
 namespace dsen2 {
 
-// fp32: x0 | a | t.   bf16: x0 | a (fp32: the last block's output) | hi | lo | tbf
-// (hi, lo: the residual stream as two 16-bit planes; tbf: bf16; each half an fp32 tensor)
-// bf16x3: x0 | a (fp32: the first convolution's and the last block's output) | hx (hi | xl planes) | lo16 | t2 (hi | lo planes)
+// fp32: x0 | a | t.   bf16, bf16x3: x0 | a (fp32: the last block's output, and a generic first convolution's) | s0 | s1 | t16:
+// s0 and t16 operand tensors (bf16: one plane, half an fp32 tensor; bf16x3: two planes), s1 the stream's low halves (one plane)
 ForwardWs forward_ws(const dsen2_model* m, int n, int h, int w, char* base) {
   const size_t pix = (size_t)n * h * w;
   const size_t full = align_up(pix * m->feat), half = align_up(pix * m->feat / 2);
@@ -160,12 +159,11 @@ ForwardWs forward_ws(const dsen2_model* m, int n, int h, int w, char* base) {
   };
   r.x0 = take(align_up(pix * 16));
   r.a = take(full);
-  if (m->precision == 1) {
-    r.hi = take(half); r.lo = take(half); r.tbf = take(half);
-  } else if (m->precision == 2) {
-    r.hx = take(full); r.lo16 = take(half); r.t2 = take(full);
-  } else {
+  if (m->precision == 0) {
     r.t = take(full);
+  } else {
+    const size_t operand = m->precision == 2 ? full : half;
+    r.s0 = take(operand); r.s1 = take(half); r.t16 = take(operand);
   }
   r.bytes = off * sizeof(float);
   return r;
@@ -178,18 +176,12 @@ int forward_launches(const dsen2_model* m, const float* x10, const float* x20, c
   if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
   if (int rc = first_layer(m, x10, x20, x60, n, h, w, B, x0_packed, stream)) return rc;
   if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
-  if (m->precision == 2 && d > 0) {
+  if (m->precision != 0 && d > 0) {
     if (keep_step > 0) {
-      HIP_TRY(launch_join3_f32(B.hx, B.lo16, B.x0f, n, h, w, m->feat, stream));
-      HIP_TRY(hipMemcpyAsync(B.xkeep, B.hx, operand16_bytes(m, n, h, w), hipMemcpyDeviceToDevice, stream));
+      HIP_TRY((m->precision == 2 ? launch_join3_f32 : launch_join_f32)(B.s0, B.s1, B.x0f, n, h, w, m->feat, stream));
+      HIP_TRY(hipMemcpyAsync(B.xkeep, B.s0, operand16_bytes(m, n, h, w), hipMemcpyDeviceToDevice, stream));
     }
-    if (int rc = body16(m, B.hx, B.lo16, B.t2, B.a, n, h, w, stream, keep_step, B.xkeep)) return rc;
-  } else if (m->precision == 1 && d > 0) {
-    if (keep_step > 0) {
-      HIP_TRY(launch_join_f32(B.hi, B.lo, B.x0f, n, h, w, m->feat, stream));
-      HIP_TRY(hipMemcpyAsync(B.xkeep, B.hi, operand16_bytes(m, n, h, w), hipMemcpyDeviceToDevice, stream));
-    }
-    if (int rc = body16(m, B.hi, B.lo, B.tbf, B.a, n, h, w, stream, keep_step, B.xkeep)) return rc;
+    if (int rc = body16(m, B.s0, B.s1, B.t16, B.a, n, h, w, stream, keep_step, B.xkeep)) return rc;
   } else {
     // (the ablation mask is 0 in the product library; a diagnostic build that sets it times the ablated kernels in the
     // inference and in the training forward)
@@ -587,7 +579,7 @@ int dsen2_model_load_weights(dsen2_model* m, const float* host_flat, size_t coun
     if (!m->dev_params) HIP_TRY(hipMalloc((void**)&m->dev_params, m->dev_param_floats * sizeof(float)));
     HIP_TRY(hipMemcpy(m->dev_params, staged.data(), m->dev_param_floats * sizeof(float), hipMemcpyHostToDevice));
     m->loaded = true;
-    if (m->trains_x3()) m->host_flat.assign(host_flat, host_flat + count);
+    if (m->train_planes() == 2) m->host_flat.assign(host_flat, host_flat + count);
     if (m->train) return train_state_after_load(m);     // a model being trained: its master weights follow
     return DSEN2_OK;
   });

@@ -57,9 +57,10 @@ struct dsen2_model : dsen2::NetworkPlan {   // every layer's plan and place insi
   // precision 2 with residual blocks: the packed planes (hi + lo, 16 significant bits) do not hold the fp32 weights, so the
   // keras-flat vector dsen2_model_load_weights was given is kept until a training state takes it over as its master copy
   std::vector<float> host_flat;
-  bool trains_x3() const { return precision == 2 && num_layers > 0; }
-  // an fp32 model whose training step runs on a precision-1 companion plan (without residual blocks that plan is all fp32)
-  bool trains_amp() const { return precision == 0 && train_precision == 1 && num_layers > 0; }
+  // How the model trains (capi_train.hip, StepFormat): the bf16 planes of a 16-bit tensor of its step.  0: fp32 tensors (an
+  // fp32 model; any model without residual blocks, whose plan is all fp32), 2: bf16x3, 1: an fp32 model whose step runs on
+  // a precision-1 companion plan (and that companion itself)
+  int train_planes() const { return num_layers == 0 ? 0 : precision == 0 ? train_precision : precision; }
 };
 
 namespace dsen2 {
@@ -136,22 +137,22 @@ struct ForwardWs {
   float* a = nullptr;                                 // residual stream x, fp32 (16-bit precisions: the first convolution's
                                                       // output where it is the generic kernel's, and the last block's)
   float* t = nullptr;                                 // precision 0: relu(convA(x))
-  void *hi = nullptr, *lo = nullptr, *tbf = nullptr;  // precision 1: the stream as two 16-bit planes; relu(convA(x)) as bf16
-  void *hx = nullptr, *lo16 = nullptr, *t2 = nullptr; // precision 2: the stream as hx (hi | xl planes) and lo16; t as (hi | lo) planes
-  void* xkeep = nullptr;                              // precision 1 / 2, keep_step > 0: copies of hi / hx, x_l at xkeep + l * keep_step floats (l < d)
+  // precision 1 / 2: the stream as s0, the operand tensor of the next convolution (precision 1: the hi plane; precision 2:
+  // hx, the hi | xl planes), and s1, the low halves; t16 = relu(convA(x)) as an operand tensor (bf16; hi | lo planes)
+  void *s0 = nullptr, *s1 = nullptr, *t16 = nullptr;
+  void* xkeep = nullptr;                              // precision 1 / 2, keep_step > 0: copies of s0, x_l at xkeep + l * keep_step floats (l < d)
   float* x0f = nullptr;                               // precision 1 / 2, keep_step > 0: x_0 as fp32 NHWC
   size_t bytes = 0;
 };
 // the inference workspace for n images of h x w: its size and, with base != NULL, its sub-buffers
 ForwardWs forward_ws(const dsen2_model* m, int n, int h, int w, char* base);
 // Every launch of one forward pass, in stream order; no argument checks.  keep_step = 0: the blocks run in place.  keep_step
-// > 0, precision 0: block l reads x_{l-1} at B.a + (l - 1) * keep_step and writes t_l at B.t + (l - 1) * keep_step and
-// x_l at B.a + l * keep_step (floats).  keep_step > 0, precision 2 (with residual blocks): always layer by layer, never the
-// chain kernel; conv-A writes t_l at B.t2 + (l - 1) * keep_step; conv-B runs in place on (B.hx, B.lo16), so hx (hi | xl, what
-// the backward reads) is copied to B.xkeep + l * keep_step after the first convolution (l = 0) and after every block but the
-// last, whose output is the fp32 tensor B.a; B.x0f receives x_0 as fp32.  keep_step > 0, precision 1 (with residual blocks; the
-// companion plan of a mixed-precision training step): the same with one-plane tensors: t_l (bf16) at B.tbf + (l - 1) *
-// keep_step, the stream's hi plane — conv-A's operand — copied to B.xkeep + l * keep_step, x_0 joined from (hi, lo) into B.x0f.
+// > 0 (training; floats): every block's activations are kept.  Precision 0: block l reads x_{l-1} at B.a + (l - 1) * keep_step
+// and writes t_l at B.t + (l - 1) * keep_step and x_l at B.a + l * keep_step.  Precision 1 / 2 with residual blocks (a bf16x3
+// model; the companion plan of a mixed-precision step): always layer by layer, never the chain kernel; conv-A writes t_l at
+// B.t16 + (l - 1) * keep_step; conv-B runs in place on (B.s0, B.s1), so s0 — what the backward reads — is copied to B.xkeep +
+// l * keep_step after the first convolution (l = 0) and after every block but the last, whose output is the fp32 tensor B.a;
+// B.x0f receives x_0 joined to fp32.
 // x0_packed: the caller has already run launch_pack_inputs into B.x0.
 // ev (optional, 4 events): recorded on the stream before the first convolution, before the first and after the last
 // residual-block convolution, and after the output convolution.

@@ -8,34 +8,41 @@
 // bias: dgradA + g is the body kernel's residual epilogue with res_scale 1; dgradB is the same epilogue on a zeroed buffer
 // with res_scale 0.1, then the ReLU mask.  wgrad is conv3x3_wgrad.hip; loss, masks and Nadam are train_ops.hip.
 //
-// The weights of a model being trained live as a device keras-flat vector (the master copy).  Every packed buffer — the
-// forward's and the dgrad weights — is rebuilt from it by one gather kernel whose index maps are made once, by running the
-// host packers on per-layer iota + 1 kernels (0 = padding): the repacked weights are the host packers' bits by construction.
+// One walk (gradients) serves every model.  A StepFormat says which plan it runs on and how many bf16 planes a 16-bit tensor
+// of the step has.  In every format the forward is forward_launches with every t_l and x_l kept, and the loss, the output and
+// the first convolution's gradients run on the fp32 kernels on fp32 tensors; the formats differ in the residual blocks:
+//   planes 0  (an fp32 model; any model without residual blocks): fp32 tensors and the kernels above; g is updated in place,
+//             du is zeroed for every block.
+//   planes 2  (a bf16x3 model): the forward's bf16x3 per-layer kernels.  g lives as a precision-2 residual stream (s0 = hx: hi | xl
+//             planes, the dgrads' operand; s1 = lo16), reached through launch_split3_f32 / launch_join3_f32, so g + dgradA(du) is
+//             the body kernel's in-place residual epilogue and 0.1 * dgradB(g) its fp32 epilogue over a zero stream it never
+//             writes, followed by launch_mask_split3 (ReLU mask of t_l, du as a two-plane operand tensor); the block weight
+//             gradients are conv3x3_wgrad16.hip.  A 16-bit operand tensor (s0, t_l, the kept copies of s0, du) has the size of
+//             an fp32 tensor.
+//   planes 1  (mixed precision: dsen2_model_set_train_precision(m, 1) on an fp32 model with residual blocks): the same on
+//             one-plane tensors of half that size, on the model's COMPANION plan.  g is a precision-1 residual stream (hi, lo) =
+//             exact fp32 (launch_split_f32 / launch_join_f32), hi = (u + 0x8000) >> 16 the dgrads' and conv-B wgrad's operand;
+//             t_l is bf16 (RNE), du = bf16_rne of the masked value (launch_mask_round16); the block weight gradients are the
+//             one-plane instance of conv3x3_wgrad16.hip (db = the sum of the bf16 operand g).
 //
-// A precision-2 (bf16x3) model with residual blocks trains in its own formats (gradients_x3): the forward on the bf16x3 per-layer
-// kernels with t_l and copies of the stream's operand tensor hx kept; g lives as a precision-2 residual stream (hx, lo16), so
-// g + dgradA(du) is the X3 body kernel's in-place residual epilogue and 0.1 * dgradB(g) its fp32 epilogue over a zero stream,
-// followed by launch_mask_split3 (ReLU mask of t_l, du as a two-plane operand tensor); the block weight gradients are
-// conv3x3_wgrad16.hip.  The first and the output convolution's gradients stay on the fp32 kernels, reached through
-// launch_split3_f32 / launch_join3_f32.  The master copy is still the fp32 keras-flat vector; the packed buffers hold bf16
-// (hi, lo) planes next to fp32 words, so their maps have one entry per 16-bit half (launch_gather16) and are read off the host
-// packers digit by digit: an iota does not survive a bf16 split, but a base-128 digit d packed as the value d + 1 does (exact
-// in bf16: it lands in the hi plane, the lo plane gets 0), and packed as 1 + (d + 1) * 2^-16 it lands in the lo plane (hi = 1).
-// Three passes of each kind give every half its flat index and its kind.  The body layers share one plan and so one map.
+// The weights of a model being trained live as a device keras-flat fp32 vector (the master copy).  Every packed buffer — the
+// forward's and the dgrad weights — is rebuilt from it (repack_from_master) by gather kernels whose index maps are made once,
+// by running the host packers on index-valued kernels: the repacked weights are the host packers' bits by construction.
+// fp32 buffers have one map entry per float (launch_gather; the packers run on 1 + index, 0 = padding).  The buffers of a
+// 16-bit plan hold bf16 (hi, lo) planes next to fp32 words, so their maps have one entry per 16-bit half (launch_gather16) and
+// are read off the host packers digit by digit: an index does not survive a bf16 split, but a base-128 digit d packed as the
+// value d + 1 does (exact in bf16: it lands in the hi plane, the lo plane gets 0), and packed as 1 + (d + 1) * 2^-16 it lands
+// in the lo plane (hi = 1).  Three passes of each kind give every half its flat index and its kind.  The body layers share
+// one plan and so one map.
 //
-// Mixed precision (dsen2_model_set_train_precision(m, 1) on an fp32 model with residual blocks; gradients_amp): the model, its
-// master weights and its packed fp32 buffers stay as they are, and the training state owns a COMPANION: a precision-1 plan of
-// the same network with the packed buffers a precision-1 model of these weights would hold (first16 image, bf16 body planes,
-// fp32 output layer) and its own 16-bit training state (the bf16 flipped / transposed dgrad weights), both rebuilt from the
-// one master vector by launch_gather16 after every weight change — the same maps, read off the precision-1 host packers.  The
-// step is gradients_x3 with one-plane tensors: the companion's forward layer by layer, t_l (bf16, RNE) and the stream's hi
-// plane kept; g as a precision-1 residual stream (hi, lo) = exact fp32, hi = (u + 0x8000) >> 16 the dgrads' and conv-B wgrad's
-// operand; 0.1 * dgradB(hi(g)) through the fp32 epilogue over a zero stream, du = bf16_rne of its masked value
-// (launch_mask_round16); g + dgradA(du) in place; the block weight gradients on the one-plane instance of conv3x3_wgrad16.hip
-// (db = the sum of the bf16 operand g).  Loss, output layer and first layer as in gradients_x3: fp32 kernels on fp32 tensors.
+// The companion of a mixed-precision model is owned by its training state: a precision-1 plan of the same network with the
+// packed buffers a precision-1 model of these weights would hold (first16 image, bf16 body planes, fp32 output layer) and its
+// own 16-bit training state (the bf16 flipped / transposed dgrad weights) on the owner's master vector.  The model, its master
+// weights and its packed fp32 buffers stay as they are; it builds no fp32 dgrad weights.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 
 #include "capi_internal.h"
@@ -46,32 +53,26 @@ namespace dsen2 {
 
 struct TrainState {
   float* master = nullptr;     // [n_params] keras-flat
-  int* fwd_map = nullptr;      // [dev_param_floats]: 1 + flat index of every packed forward value, 0 = padding
+  bool owns_master = true;     // (a companion borrows its owner's)
   float* dg = nullptr;         // flipped / transposed packed weights of every layer with an input gradient, + zero bias
-  int* dg_map = nullptr;       // [dg_floats]
   size_t dg_floats = 0;
   std::vector<size_t> dg_off;  // per layer: float offset of its dgrad weights in dg (layer 0: none)
+  size_t dg_body_stride = 0;   // floats between the dgrad weights of consecutive body layers
   size_t zero_off = 0;         // feat zeros (the dgrad convolutions' bias)
   ConvPlan body_plan{}, out_plan{};   // the dgrad convolutions of a body layer (F -> F) and of the output layer (16 -> F)
-  // a 16-bit plan with residual blocks (a precision-2 model; the precision-1 companion of a mixed-precision step): launch_gather16
-  // maps of the first layer's, a body layer's and the output layer's forward buffer and of a body layer's and the output layer's
-  // dgrad weights (fwd_map / dg_map stay NULL)
-  bool packed16 = false;
+  // fp32 buffers: launch_gather / launch_scatter maps, 1 + flat index of every packed value, 0 = padding
+  int* fwd_map = nullptr;      // [dev_param_floats]
+  int* dg_map = nullptr;       // [dg_floats]
+  // a 16-bit plan (packed16): launch_gather16 maps of the first layer's, a body layer's and the output layer's forward buffer
+  // and of a body layer's and the output layer's dgrad weights
   int* map16[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t dg_body_stride = 0;          // floats between the dgrad weights of consecutive body layers
-  // mixed precision: the precision-1 companion plan (owned; its own state has packed16 set and borrows `master`)
-  dsen2_model* amp = nullptr;
-  bool owns_master = true;
+  dsen2_model* amp = nullptr;  // mixed precision: the companion plan (owned)
 };
 enum { kMapFirst = 0, kMapBody = 1, kMapOut = 2, kMapDgBody = 3, kMapDgOut = 4 };
 
 void train_state_destroy(TrainState* t) {
   if (!t) return;
-  if (t->amp) {
-    train_state_destroy(t->amp->train);
-    if (t->amp->dev_params) (void)hipFree(t->amp->dev_params);
-    delete t->amp;
-  }
+  dsen2_model_destroy(t->amp);
   if (t->master && t->owns_master) (void)hipFree(t->master);
   if (t->fwd_map) (void)hipFree(t->fwd_map);
   if (t->dg) (void)hipFree(t->dg);
@@ -85,17 +86,51 @@ void train_state_destroy(TrainState* t) {
 
 namespace {
 
+// How a model trains: `plan` is the model whose packed buffers and dgrad weights the step runs on (m itself, or its companion
+// once the training state exists); `planes` is dsen2_model::train_planes().  A companion has the network, feature size and
+// tuning of its owner, so a workspace may be sized from either.
+struct StepFormat {
+  const dsen2_model* plan;
+  int planes;
+};
+bool has_companion(const dsen2_model* m) { return m->precision == 0 && m->train_planes() == 1; }
+// m's own packed buffers are a 16-bit plan's (a bf16x3 model, a companion): 16-bit-granular maps, the master copy not
+// recoverable from them
+bool packed16(const dsen2_model* m) { return m->precision != 0 && m->train_planes() != 0; }
+StepFormat step_format(const dsen2_model* m) { return {has_companion(m) && m->train ? m->train->amp : m, m->train_planes()}; }
+
 int check_train_model(const dsen2_model* m) {
   if (!m) return fail(DSEN2_ERR_INVALID, "NULL model");
   if (m->precision == 1) return fail(DSEN2_ERR_INVALID, "training needs an fp32 model or a bf16x3 one (precision 0 or 2), not bf16 operands");
   return check_device(m);
 }
 
-// map value for a packed float that holds iota value v of the layer starting at flat_off: 1 + flat index, 0 = padding
-inline int map_value(float v, size_t flat_off) { return v > 0.f ? (int)(flat_off + (size_t)v) : 0; }
+// What the packers are run on, as indices into a layer's keras-flat values (-1 = a zero).  A layer's own buffer: the kernel,
+// then the bias, as they lie there.
+std::vector<int> layer_values(const Layer& Ly) {
+  std::vector<int> v((size_t)9 * Ly.plan.cin * Ly.plan.cout + Ly.plan.cout);
+  for (size_t i = 0; i < v.size(); ++i) v[i] = (int)i;
+  return v;
+}
+// The kernel of the dgrad convolution g of a layer ci -> co: W'[tap][c'][o'] = W[8 - tap][o'][c'] (the output layer: 16 -> F,
+// the outputs zero-padded to 16 input channels)
+std::vector<int> flipped_values(const ConvPlan& g, int ci, int co) {
+  std::vector<int> v((size_t)9 * g.cin * g.cout, -1);
+  for (int tap = 0; tap < 9; ++tap)
+    for (int c = 0; c < co; ++c)
+      for (int o = 0; o < ci; ++o) v[((size_t)tap * g.cin + c) * g.cout + o] = (int)(((size_t)(8 - tap) * ci + o) * co + c);
+  return v;
+}
 
-// One 16-bit-granular gather map (launch_gather16) of a layer buffer, read off the host packers: src[e] = the index, inside the
-// layer's keras-flat values, of element e of the kernel (+ bias) handed to pack(), or -1 for a zero.  See the file comment.
+// the float-granular map (launch_gather / launch_scatter) of a layer buffer whose values start at flat_off
+void build_gather_map(const ConvPlan& pl, bool with_bias, const std::vector<int>& src, size_t flat_off, int* map) {
+  std::vector<float> k(src.size()), buf(with_bias ? pl.floats : pl.weight_floats);
+  for (size_t e = 0; e < src.size(); ++e) k[e] = (float)(src[e] + 1);
+  pack(pl, k.data(), with_bias ? k.data() + (size_t)9 * pl.cin * pl.cout : nullptr, buf.data());
+  for (size_t i = 0; i < buf.size(); ++i) map[i] = buf[i] > 0.f ? (int)(flat_off + (size_t)buf[i]) : 0;
+}
+
+// The 16-bit-granular map (launch_gather16) of a layer buffer, relative to the layer's values; see the file comment.
 // Three base-128 digits hold indices below 2^21 (the largest layer, 256 -> 256, has 590,080 values); a larger one is refused
 // (std::length_error: DSEN2_ERR_INTERNAL through guarded()), never aliased.
 std::vector<int> build_gather16_map(const ConvPlan& pl, bool with_bias, const std::vector<int>& src) {
@@ -121,10 +156,10 @@ std::vector<int> build_gather16_map(const ConvPlan& pl, bool with_bias, const st
     memcpy(&f, &u, 4);
     return f;
   };
-  const bool packed16 = pl.kernel == ConvKernel::Body16 || pl.kernel == ConvKernel::Body16x3;
+  const bool body16 = pl.kernel == ConvKernel::Body16 || pl.kernel == ConvKernel::Body16x3;
   std::vector<int> map(2 * words, 0);
   for (size_t i = 0; i < words; ++i) {
-    const bool is16 = (packed16 && i < pl.weight_floats) || (pl.first16_planes && i >= pl.first16_off);
+    const bool is16 = (body16 && i < pl.weight_floats) || (pl.first16_planes && i >= pl.first16_off);
     if (!is16) {
       if (buf[0][i] == 0.f) continue;
       int idx = 0;
@@ -147,247 +182,140 @@ std::vector<int> build_gather16_map(const ConvPlan& pl, bool with_bias, const st
   return map;
 }
 
-struct StateGuard {                 // freed unless handed to the model
-  TrainState* t;
-  ~StateGuard() { train_state_destroy(t); }
-};
-
 int upload_map(const std::vector<int>& map, int** dev) {
   HIP_TRY(hipMalloc((void**)dev, map.size() * sizeof(int)));
   HIP_TRY(hipMemcpy(*dev, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
   return DSEN2_OK;
 }
 
-// the training state of a 16-bit plan with residual blocks: a precision-2 model (master == NULL: its own master vector), or the
-// precision-1 companion of a mixed-precision step, which borrows its owner's
-int ensure_train_state_x3(dsen2_model* m, float* master = nullptr) {
-  TrainState* t = new TrainState();
-  StateGuard guard{t};
-  t->packed16 = true;
-  const int F = m->feat;
-  const size_t L = m->layers.size();
-  if (!plan_conv(ConvRole::DgradBody, F, F, m->precision, m->tune, nullptr, &t->body_plan) ||
-      !plan_conv(ConvRole::DgradOutput, 16, F, 0, m->tune, nullptr, &t->out_plan))
-    return fail(DSEN2_ERR_INVALID, "no dgrad kernel for feature size %d", F);
-  auto iota = [](size_t count) {
-    std::vector<int> v(count);
-    for (size_t i = 0; i < count; ++i) v[i] = (int)i;
-    return v;
-  };
-  // the packers' kernel of a dgrad convolution: W'[tap][c'][o'] = W[8 - tap][o'][c'] (ensure_train_state)
-  auto flipped = [](const ConvPlan& g, int ci, int co) {
-    std::vector<int> v((size_t)9 * g.cin * g.cout, -1);
-    for (int tap = 0; tap < 9; ++tap)
-      for (int c = 0; c < co; ++c)
-        for (int o = 0; o < ci; ++o) v[((size_t)tap * g.cin + c) * g.cout + o] = (int)(((size_t)(8 - tap) * ci + o) * co + c);
-    return v;
-  };
-  const Layer &L0 = m->layers[0], &L1 = m->layers[1], &LO = m->layers[L - 1];
-  auto layer_values = [](const Layer& Ly) { return (size_t)9 * Ly.plan.cin * Ly.plan.cout + Ly.plan.cout; };
-  if (int rc = upload_map(build_gather16_map(L0.plan, true, iota(layer_values(L0))), &t->map16[kMapFirst])) return rc;
-  if (int rc = upload_map(build_gather16_map(L1.plan, true, iota(layer_values(L1))), &t->map16[kMapBody])) return rc;
-  if (int rc = upload_map(build_gather16_map(LO.plan, true, iota(layer_values(LO))), &t->map16[kMapOut])) return rc;
-  if (int rc = upload_map(build_gather16_map(t->body_plan, false, flipped(t->body_plan, F, F)), &t->map16[kMapDgBody])) return rc;
-  if (int rc = upload_map(build_gather16_map(t->out_plan, false, flipped(t->out_plan, LO.plan.cin, LO.plan.cout)), &t->map16[kMapDgOut]))
-    return rc;
-  t->dg_body_stride = align_up(t->body_plan.weight_floats);
-  t->dg_off.assign(L, 0);
-  size_t off = 0;
-  for (size_t li = 1; li < L; ++li) {
-    t->dg_off[li] = off;
-    off += li + 1 == L ? align_up(t->out_plan.weight_floats) : t->dg_body_stride;
-  }
-  t->zero_off = off;
-  off += align_up((size_t)F);
-  t->dg_floats = off;
-  t->owns_master = master == nullptr;
-  t->master = master;
-  if (t->owns_master) HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&t->dg, t->dg_floats * sizeof(float)));
-  HIP_TRY(hipMemset(t->dg, 0, t->dg_floats * sizeof(float)));        // the zero bias; the padding between the layers
-  m->train = t;
-  guard.t = nullptr;
-  if (t->owns_master && m->loaded) return train_state_after_load(m);
-  return DSEN2_OK;
-}
-
-// the packed forward buffers (fwd) and / or the dgrad weights of a 16-bit plan <- master
-int repack_x3(dsen2_model* m, bool fwd, hipStream_t s) {
-  TrainState* t = m->train;
-  const size_t L = m->layers.size();
-  const Layer &L0 = m->layers[0], &L1 = m->layers[1], &LO = m->layers[L - 1];
-  const size_t body_values = (size_t)9 * m->feat * m->feat + m->feat;
-  if (fwd) {
-    HIP_TRY(launch_gather16(m->dev_params + L0.off, t->master + L0.flat_off, t->map16[kMapFirst], L0.plan.floats, 1, 0, 0, s));
-    HIP_TRY(launch_gather16(m->dev_params + L1.off, t->master + L1.flat_off, t->map16[kMapBody], L1.plan.floats, 2 * m->num_layers,
-                            L1.plan.floats, body_values, s));
-    HIP_TRY(launch_gather16(m->dev_params + LO.off, t->master + LO.flat_off, t->map16[kMapOut], LO.plan.floats, 1, 0, 0, s));
-  }
-  HIP_TRY(launch_gather16(t->dg + t->dg_off[1], t->master + L1.flat_off, t->map16[kMapDgBody], t->body_plan.weight_floats,
-                          2 * m->num_layers, t->dg_body_stride, body_values, s));
-  HIP_TRY(launch_gather16(t->dg + t->dg_off[L - 1], t->master + LO.flat_off, t->map16[kMapDgOut], t->out_plan.weight_floats, 1, 0, 0, s));
-  return DSEN2_OK;
-}
+int ensure_train_state(dsen2_model* m, float* borrowed_master = nullptr);
 
 // the precision-1 companion of a mixed-precision step: the same network planned with bf16 operands, its packed buffers allocated
-// (filled by repack_x3) and its 16-bit training state on the owner's master vector
+// (filled by repack_from_master) and its training state on the owner's master vector
 int create_amp_companion(const dsen2_model* m, float* master, dsen2_model** out) {
-  struct Guard {
-    dsen2_model* c;
-    ~Guard() {
-      if (!c) return;
-      train_state_destroy(c->train);
-      if (c->dev_params) (void)hipFree(c->dev_params);
-      delete c;
-    }
-  } g{new dsen2_model()};
-  dsen2_model* c = g.c;
+  std::unique_ptr<dsen2_model, void (*)(dsen2_model*)> guard(new dsen2_model(), dsen2_model_destroy);
+  dsen2_model* c = guard.get();
   c->c10 = m->c10; c->c20 = m->c20; c->c60 = m->c60; c->cin = m->cin; c->cout = m->cout;
   c->num_layers = m->num_layers; c->feat = m->feat; c->precision = 1; c->device = m->device; c->tune = m->tune;
   c->dev_params = nullptr; c->loaded = false; c->train = nullptr;
   if (!plan_network(m->c10, m->c20, m->c60, m->num_layers, m->feat, 1, c->tune, c) || c->n_params != m->n_params)
     return fail(DSEN2_ERR_INVALID, "no bf16 kernel for a layer of this network");
   HIP_TRY(hipMalloc((void**)&c->dev_params, c->dev_param_floats * sizeof(float)));
-  if (int rc = ensure_train_state_x3(c, master)) return rc;
-  *out = c;
-  g.c = nullptr;
+  if (int rc = ensure_train_state(c, master)) return rc;
+  *out = guard.release();
   return DSEN2_OK;
 }
 
-int ensure_train_state(dsen2_model* m) {
+// The training state of m: its master vector (borrowed_master: a companion's, which is its owner's), the dgrad weights of its
+// plan where the step runs on it, the maps that rebuild its packed buffers, and its companion where it has one.
+int ensure_train_state(dsen2_model* m, float* borrowed_master) {
   if (m->train) return DSEN2_OK;
   if (m->n_params >= (size_t)0x7fffffff) return fail(DSEN2_ERR_INVALID, "too many parameters for the gather maps");
-  if (m->trains_x3()) return ensure_train_state_x3(m);
-  TrainState* t = new TrainState();
-  StateGuard guard{t};
+  std::unique_ptr<TrainState, void (*)(TrainState*)> guard(new TrainState(), train_state_destroy);
+  TrainState* t = guard.get();
   const int F = m->feat;
   const size_t L = m->layers.size();
-  if (!plan_conv(ConvRole::DgradBody, F, F, 0, m->tune, nullptr, &t->body_plan) ||
+  // (mixed precision: the step runs on the companion's bf16 dgrad weights; the fp32 ones are neither built nor kept)
+  const bool p16 = packed16(m), own_dgrad = !has_companion(m);
+  if (!plan_conv(ConvRole::DgradBody, F, F, p16 ? m->precision : 0, m->tune, nullptr, &t->body_plan) ||
       !plan_conv(ConvRole::DgradOutput, 16, F, 0, m->tune, nullptr, &t->out_plan))
     return fail(DSEN2_ERR_INVALID, "no dgrad kernel for feature size %d", F);
-  // forward map: dsen2_model_load_weights' pack() on iota kernels (kernel, then bias, as in the keras-flat array)
-  std::vector<int> fmap(m->dev_param_floats, 0);
-  std::vector<float> buf, k;
-  for (const Layer& Ly : m->layers) {
-    const size_t nk = (size_t)9 * Ly.plan.cin * Ly.plan.cout;
-    k.resize(nk + Ly.plan.cout);
-    for (size_t i = 0; i < k.size(); ++i) k[i] = (float)(i + 1);
-    buf.resize(Ly.plan.floats);
-    pack(Ly.plan, k.data(), k.data() + nk, buf.data());
-    for (size_t i = 0; i < buf.size(); ++i) fmap[Ly.off + i] = map_value(buf[i], Ly.flat_off);
-  }
-  // (mixed precision: the step runs on the companion's bf16 dgrad weights; the fp32 ones are neither built nor kept)
-  const bool own_dgrad = !m->trains_amp();
-  std::vector<int> dmap;
-  if (own_dgrad) {
-    // dgrad weights: W'[tap][c'][o'] = W[8 - tap][o'][c'] for the body layers (F -> F) and the output layer (16 -> F, the
-    // outputs zero-padded to 16 input channels); layer 0 needs no input gradient
+  auto dgrad_plan = [&](size_t li) -> const ConvPlan& { return li + 1 == L ? t->out_plan : t->body_plan; };
+  if (own_dgrad) {     // dg: the dgrad weights of layers 1 .. L - 1 (layer 0 needs no input gradient), then the zero bias
+    t->dg_body_stride = align_up(t->body_plan.weight_floats);
     t->dg_off.assign(L, 0);
     size_t off = 0;
     for (size_t li = 1; li < L; ++li) {
       t->dg_off[li] = off;
-      off += align_up((li + 1 == L ? t->out_plan : t->body_plan).weight_floats);
+      off += align_up(dgrad_plan(li).weight_floats);
     }
     t->zero_off = off;
-    off += align_up((size_t)F);
-    t->dg_floats = off;
-    dmap.assign(off, 0);
-    for (size_t li = 1; li < L; ++li) {
-      const int ci = m->layers[li].plan.cin, co = m->layers[li].plan.cout;
-      const ConvPlan& g = li + 1 == L ? t->out_plan : t->body_plan;    // the dgrad convolution: forward outputs -> forward inputs
-      k.assign((size_t)9 * g.cin * g.cout, 0.f);
-      for (int tap = 0; tap < 9; ++tap)
-        for (int c = 0; c < co; ++c)
-          for (int o = 0; o < ci; ++o)
-            k[((size_t)tap * g.cin + c) * g.cout + o] = (float)(((size_t)(8 - tap) * ci + o) * co + c + 1);
-      buf.resize(g.weight_floats);
-      pack(g, k.data(), nullptr, buf.data());
-      for (size_t i = 0; i < buf.size(); ++i) dmap[t->dg_off[li] + i] = map_value(buf[i], m->layers[li].flat_off);
-    }
+    t->dg_floats = off + align_up((size_t)F);
   }
-  HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&t->fwd_map, fmap.size() * sizeof(int)));
-  HIP_TRY(hipMemcpy(t->fwd_map, fmap.data(), fmap.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (p16) {
+    const Layer &L0 = m->layers[0], &L1 = m->layers[1], &LO = m->layers[L - 1];
+    if (int rc = upload_map(build_gather16_map(L0.plan, true, layer_values(L0)), &t->map16[kMapFirst])) return rc;
+    if (int rc = upload_map(build_gather16_map(L1.plan, true, layer_values(L1)), &t->map16[kMapBody])) return rc;
+    if (int rc = upload_map(build_gather16_map(LO.plan, true, layer_values(LO)), &t->map16[kMapOut])) return rc;
+    if (int rc = upload_map(build_gather16_map(t->body_plan, false, flipped_values(t->body_plan, F, F)), &t->map16[kMapDgBody])) return rc;
+    if (int rc = upload_map(build_gather16_map(t->out_plan, false, flipped_values(t->out_plan, LO.plan.cin, LO.plan.cout)), &t->map16[kMapDgOut]))
+      return rc;
+  } else {
+    std::vector<int> fmap(m->dev_param_floats, 0), dmap(t->dg_floats, 0);
+    for (const Layer& Ly : m->layers) build_gather_map(Ly.plan, true, layer_values(Ly), Ly.flat_off, &fmap[Ly.off]);
+    for (size_t li = 1; own_dgrad && li < L; ++li) {
+      const Layer& Ly = m->layers[li];
+      build_gather_map(dgrad_plan(li), false, flipped_values(dgrad_plan(li), Ly.plan.cin, Ly.plan.cout), Ly.flat_off, &dmap[t->dg_off[li]]);
+    }
+    if (int rc = upload_map(fmap, &t->fwd_map)) return rc;
+    if (own_dgrad)
+      if (int rc = upload_map(dmap, &t->dg_map)) return rc;
+  }
+  t->owns_master = borrowed_master == nullptr;
+  t->master = borrowed_master;
+  if (t->owns_master) HIP_TRY(hipMalloc((void**)&t->master, m->n_params * sizeof(float)));
   if (own_dgrad) {
     HIP_TRY(hipMalloc((void**)&t->dg, t->dg_floats * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&t->dg_map, dmap.size() * sizeof(int)));
-    HIP_TRY(hipMemcpy(t->dg_map, dmap.data(), dmap.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(t->dg, 0, t->dg_floats * sizeof(float)));        // the zero bias; the padding between the layers
   }
-  if (m->trains_amp())
+  if (has_companion(m))
     if (int rc = create_amp_companion(m, t->master, &t->amp)) return rc;
-  m->train = t;
-  guard.t = nullptr;
-  if (m->loaded) return train_state_after_load(m);
+  m->train = guard.release();
+  if (t->owns_master && m->loaded) return train_state_after_load(m);
   return DSEN2_OK;
 }
 
-// master <- the packed forward weights (inverse gather), dgrad weights (where the state has its own) <- master
-int refresh_from_packed(dsen2_model* m, hipStream_t s) {
+// Every packed buffer that depends on the master vector <- master: m's forward buffers (forward_too), its dgrad weights
+// where it has them, and all of its companion's
+int repack_from_master(dsen2_model* m, bool forward_too, hipStream_t s) {
   TrainState* t = m->train;
-  HIP_TRY(launch_scatter(t->master, m->dev_params, t->fwd_map, m->dev_param_floats, s));
-  if (t->dg) HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
+  if (packed16(m)) {
+    const size_t L = m->layers.size();
+    const Layer &L0 = m->layers[0], &L1 = m->layers[1], &LO = m->layers[L - 1];
+    const size_t body_values = (size_t)9 * m->feat * m->feat + m->feat;
+    if (forward_too) {
+      HIP_TRY(launch_gather16(m->dev_params + L0.off, t->master + L0.flat_off, t->map16[kMapFirst], L0.plan.floats, 1, 0, 0, s));
+      HIP_TRY(launch_gather16(m->dev_params + L1.off, t->master + L1.flat_off, t->map16[kMapBody], L1.plan.floats, 2 * m->num_layers,
+                              L1.plan.floats, body_values, s));
+      HIP_TRY(launch_gather16(m->dev_params + LO.off, t->master + LO.flat_off, t->map16[kMapOut], LO.plan.floats, 1, 0, 0, s));
+    }
+    HIP_TRY(launch_gather16(t->dg + t->dg_off[1], t->master + L1.flat_off, t->map16[kMapDgBody], t->body_plan.weight_floats,
+                            2 * m->num_layers, t->dg_body_stride, body_values, s));
+    HIP_TRY(launch_gather16(t->dg + t->dg_off[L - 1], t->master + LO.flat_off, t->map16[kMapDgOut], t->out_plan.weight_floats, 1, 0, 0, s));
+  } else {
+    if (forward_too) HIP_TRY(launch_gather(m->dev_params, t->master, t->fwd_map, m->dev_param_floats, s));     // predict / evaluate read these
+    if (t->dg) HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
+  }
+  if (t->amp) {
+    if (int rc = repack_from_master(t->amp, true, s)) return rc;
+    t->amp->loaded = true;
+  }
   return DSEN2_OK;
 }
 
+// The training workspace, by role.  char*: a tensor in the step's format (fp32, or a 16-bit operand tensor of `planes` planes).
 struct TrainWs {
-  float *in16, *out, *gpad, *G, *DU, *wg, *loss2;
+  float *in16, *out, *gpad, *wg, *loss2;   // NHWC16 packed input; the forward's output and the loss where the caller passes none
+  float *x0f, *xd, *g;                     // fp32 x_0, fp32 x_d (the output layer's input), fp32 g
+  char *xkeep, *tkeep;                     // x_l at xkeep + l * keep_step floats, t_l at tkeep + (l - 1) * keep_step, as the
+  size_t keep_step;                        // forward keeps them (planes 0: x_0 .. x_d, so x0f and xd lie inside; else l < d)
+  char* du;
+  void *s0, *s1, *gs0, *gs1, *zs0, *zs1;   // planes 1 / 2: the forward's stream, g as a stream, the zero stream
   double* partial;
-  std::vector<float*> X, T;
-  size_t keep_step;   // X[l] = X[0] + l * keep_step, T[l] = T[1] + (l - 1) * keep_step: what forward_launches writes
   size_t wg_floats;
   size_t bytes;
 };
 
 // carve (or, with base == NULL, only size) the training workspace
-TrainWs carve(const dsen2_model* m, int n, int h, int w, char* base) {
-  const size_t pix = (size_t)n * h * w, F = m->feat;
-  const size_t full = align_up(pix * F);
-  size_t wg = wgrad_workspace_floats(n, h, w, m->feat, m->feat);
-  const size_t wg1 = wgrad_workspace_floats(n, h, w, 16, m->feat), wg2 = wgrad_workspace_floats(n, h, w, m->feat, 16);
-  if (wg1 > wg) wg = wg1;
-  if (wg2 > wg) wg = wg2;
-  TrainWs r;
-  size_t off = 0;
-  auto take = [&](size_t floats) -> float* {
-    float* p = base ? reinterpret_cast<float*>(base) + off : nullptr;
-    off += align_up(floats);
-    return p;
-  };
-  r.in16 = take(pix * 16);
-  r.keep_step = full;
-  for (int l = 0; l <= m->num_layers; ++l) r.X.push_back(take(full));
-  r.T.push_back(nullptr);
-  for (int l = 1; l <= m->num_layers; ++l) r.T.push_back(take(full));
-  r.out = take(pix * m->cout);
-  r.gpad = take(pix * 16);
-  r.G = take(full);
-  r.DU = take(full);
-  r.wg = take(wg);
-  r.wg_floats = wg;
-  r.partial = reinterpret_cast<double*>(take(2 * mae_loss_partial_doubles(pix)));
-  r.loss2 = take(2);
-  r.bytes = off * sizeof(float);
-  return r;
-}
-
-// ---- precision 2 with residual blocks ----
-struct TrainWs3 {
-  float *in16, *a32, *x0f, *out, *gpad, *g32, *wg, *loss2;
-  char *hx, *lo16, *xkeep, *tkeep, *ghx, *glo, *du, *zhx, *zlo;     // 16-bit tensors
-  double* partial;
-  size_t keep_step;   // floats between the kept x_l (hx copies) and between the kept t_l
-  size_t wg_floats;
-  size_t bytes;
-};
-
-TrainWs3 carve_x3(const dsen2_model* m, int n, int h, int w, char* base) {
-  const size_t pix = (size_t)n * h * w, F = m->feat;
-  const size_t full = align_up(pix * F), half = align_up(pix * F / 2);     // a two-plane 16-bit tensor is `full` floats
-  size_t wg = wgrad16_workspace_floats(n, h, w, m->feat);
-  const size_t wg1 = wgrad_workspace_floats(n, h, w, 16, m->feat), wg2 = wgrad_workspace_floats(n, h, w, m->feat, 16);
-  if (wg1 > wg) wg = wg1;
-  if (wg2 > wg) wg = wg2;
-  TrainWs3 r;
+TrainWs carve(const StepFormat& f, int n, int h, int w, char* base) {
+  const dsen2_model* m = f.plan;
+  const size_t pix = (size_t)n * h * w, F = m->feat, d = (size_t)m->num_layers;
+  const size_t full = align_up(pix * F), half = align_up(pix * F / 2);
+  const size_t operand = f.planes == 1 ? half : full;     // a tensor in the step's format: fp32, or one or two bf16 planes
+  size_t wg = f.planes ? wgrad16_workspace_floats(n, h, w, m->feat) : wgrad_workspace_floats(n, h, w, m->feat, m->feat);
+  for (size_t other : {wgrad_workspace_floats(n, h, w, 16, m->feat), wgrad_workspace_floats(n, h, w, m->feat, 16)})
+    if (other > wg) wg = other;
+  TrainWs r{};
   size_t off = 0;
   auto take = [&](size_t floats) -> float* {
     float* p = base ? reinterpret_cast<float*>(base) + off : nullptr;
@@ -395,156 +323,45 @@ TrainWs3 carve_x3(const dsen2_model* m, int n, int h, int w, char* base) {
     return p;
   };
   auto take16 = [&](size_t floats) { return reinterpret_cast<char*>(take(floats)); };
-  const size_t d = (size_t)m->num_layers;
   r.in16 = take(pix * 16);
-  r.a32 = take(full);
-  r.x0f = take(full);
-  r.hx = take16(full);
-  r.lo16 = take16(half);
-  r.keep_step = full;
-  r.xkeep = take16(d * full);      // hx of x_0 .. x_{d-1}
-  r.tkeep = take16(d * full);      // t_1 .. t_d
-  r.out = take(pix * m->cout);
-  r.gpad = take(pix * 16);
-  r.g32 = take(full);
-  r.ghx = take16(full);
-  r.glo = take16(half);
-  r.du = take16(full);
-  r.zhx = take16(full);
-  r.zlo = take16(half);
-  r.wg = take(wg);
-  r.wg_floats = wg;
-  r.partial = reinterpret_cast<double*>(take(2 * mae_loss_partial_doubles(pix)));
-  r.loss2 = take(2);
-  r.bytes = off * sizeof(float);
-  return r;
-}
-
-// ---- mixed precision: an fp32 model's step on its precision-1 companion ----
-struct TrainWsAmp {
-  float *in16, *a32, *x0f, *out, *gpad, *g32, *wg, *loss2;
-  char *hi, *lo, *xkeep, *tkeep, *ghi, *glo, *du, *zhi, *zlo;     // one-plane 16-bit tensors
-  double* partial;
-  size_t keep_step;   // floats between the kept hi planes of x_l and between the kept t_l
-  size_t wg_floats;
-  size_t bytes;
-};
-
-TrainWsAmp carve_amp(const dsen2_model* m, int n, int h, int w, char* base) {
-  const size_t pix = (size_t)n * h * w, F = m->feat;
-  const size_t full = align_up(pix * F), half = align_up(pix * F / 2);     // a one-plane 16-bit tensor is `half` floats
-  size_t wg = wgrad16_workspace_floats(n, h, w, m->feat);
-  const size_t wg1 = wgrad_workspace_floats(n, h, w, 16, m->feat), wg2 = wgrad_workspace_floats(n, h, w, m->feat, 16);
-  if (wg1 > wg) wg = wg1;
-  if (wg2 > wg) wg = wg2;
-  TrainWsAmp r;
-  size_t off = 0;
-  auto take = [&](size_t floats) -> float* {
-    float* p = base ? reinterpret_cast<float*>(base) + off : nullptr;
-    off += align_up(floats);
-    return p;
-  };
-  auto take16 = [&](size_t floats) { return reinterpret_cast<char*>(take(floats)); };
-  const size_t d = (size_t)m->num_layers;
-  r.in16 = take(pix * 16);
-  r.a32 = take(full);
-  r.x0f = take(full);
-  r.hi = take16(half);
-  r.lo = take16(half);
-  r.keep_step = half;
-  r.xkeep = take16(d * half);      // hi of x_0 .. x_{d-1}
-  r.tkeep = take16(d * half);      // t_1 .. t_d
-  r.out = take(pix * m->cout);
-  r.gpad = take(pix * 16);
-  r.g32 = take(full);
-  r.ghi = take16(half);
-  r.glo = take16(half);
-  r.du = take16(half);
-  r.zhi = take16(half);
-  r.zlo = take16(half);
-  r.wg = take(wg);
-  r.wg_floats = wg;
-  r.partial = reinterpret_cast<double*>(take(2 * mae_loss_partial_doubles(pix)));
-  r.loss2 = take(2);
-  r.bytes = off * sizeof(float);
-  return r;
-}
-
-size_t train_ws_bytes(const dsen2_model* m, int n, int h, int w) {
-  return m->trains_x3()    ? carve_x3(m, n, h, w, nullptr).bytes
-         : m->trains_amp() ? carve_amp(m, n, h, w, nullptr).bytes
-                           : carve(m, n, h, w, nullptr).bytes;
-}
-
-// dsen2_model_gradients of an fp32 model with train precision 1 (arguments checked, training state present): on the companion
-// plan c; see the file comment
-int gradients_amp(dsen2_model* m, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out, float* grad,
-                  float* loss2, int n, int h, int w, void* ws, hipStream_t s) {
-  TrainWsAmp W = carve_amp(m, n, h, w, reinterpret_cast<char*>(ws));
-  if (!dev_out) dev_out = W.out;
-  if (!loss2) loss2 = W.loss2;
-  const dsen2_model* c = m->train->amp;
-  const TrainState* t = c->train;
-  const float* zero = t->dg + t->zero_off;
-  const int F = c->feat, d = c->num_layers;
-  const size_t pix = (size_t)n * h * w;
-  const size_t fbytes = pix * F * sizeof(float);
-  const Layer& LO = c->layers.back();
-  auto kept = [&](char* base, int l) { return base + (size_t)l * W.keep_step * sizeof(float); };
-
-  // ---- forward on the precision-1 per-layer launches, t_l and the hi plane of every x_l kept ----
-  HIP_TRY(launch_pack_inputs(x10, x20, x60, c->c10, c->c20, c->c60, W.in16, n, h, w, s));
-  ForwardWs B;
-  B.x0 = W.in16; B.a = W.a32; B.hi = W.hi; B.lo = W.lo; B.tbf = W.tkeep; B.xkeep = W.xkeep; B.x0f = W.x0f;
-  if (int rc = forward_launches(c, x10, x20, x60, dev_out, n, h, w, B, W.keep_step, true, s, nullptr)) return rc;
-
-  // ---- loss, output layer (fp32 kernels) ----
-  HIP_TRY(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, c->cout, h, w, s));
-  auto wgrad32 = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly) -> hipError_t {
-    float* dw = grad + Ly.flat_off;
-    return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.plan.cin, Ly.plan.cout, 1.f, dw, dw + (size_t)9 * Ly.plan.cin * Ly.plan.cout, W.wg,
-                                W.wg_floats, s);
-  };
-  auto wgrad16 = [&](const void* a, const void* g, const Layer& Ly, float scale) -> hipError_t {
-    float* dw = grad + Ly.flat_off;
-    return launch_conv3x3_wgrad16_bf16(a, g, n, h, w, F, scale, dw, dw + (size_t)9 * F * F, W.wg, W.wg_floats, s);
-  };
-  HIP_TRY(wgrad32(W.a32, F, W.gpad, 16, LO));
-  HIP_TRY(hipMemsetAsync(W.g32, 0, fbytes, s));
-  HIP_TRY(launch(t->out_plan, make_params(W.gpad, t->dg + t->dg_off[c->layers.size() - 1], zero, W.g32, W.g32, n, h, w, 0, 1.f), kEpiResidual,
-                 c->tune, s));
-  // g as a precision-1 residual stream; the zero stream 0.1 * dgradB is added to (its fp32 epilogue never writes it)
-  HIP_TRY(launch_split_f32(W.g32, W.ghi, W.glo, n, h, w, F, s));
-  HIP_TRY(hipMemsetAsync(W.zhi, 0, fbytes / 2, s));
-  HIP_TRY(hipMemsetAsync(W.zlo, 0, fbytes / 2, s));
-  // ---- residual blocks, last to first ----
-  for (int l = d; l >= 1; --l) {
-    const Layer& LA = c->layers[2 * l - 1];
-    const Layer& LB = c->layers[2 * l];
-    const char* t_l = kept(W.tkeep, l - 1);
-    HIP_TRY(wgrad16(t_l, W.ghi, LB, 0.1f));
-    ConvParams pb = make_params(reinterpret_cast<const float*>(W.ghi), t->dg + t->dg_off[2 * l], zero, reinterpret_cast<const float*>(W.zhi),
-                                W.g32, n, h, w, 0, 0.1f);
-    pb.out2 = W.zlo;
-    HIP_TRY(launch(t->body_plan, pb, kEpiResidualF32, c->tune, s));
-    HIP_TRY(launch_mask_round16(W.g32, t_l, W.du, n, h, w, F, s));
-    HIP_TRY(wgrad16(kept(W.xkeep, l - 1), W.du, LA, 1.f));
-    ConvParams pa = make_params(reinterpret_cast<const float*>(W.du), t->dg + t->dg_off[2 * l - 1], zero, reinterpret_cast<const float*>(W.ghi),
-                                reinterpret_cast<float*>(W.ghi), n, h, w, 0, 1.f);
-    pa.out2 = W.glo;
-    HIP_TRY(launch(t->body_plan, pa, kEpiResidual, c->tune, s));
+  r.keep_step = operand;
+  if (f.planes == 0) {       // the forward writes x_0 .. x_d into the kept x
+    r.xkeep = take16((d + 1) * full);
+    r.x0f = reinterpret_cast<float*>(r.xkeep);
+    r.xd = base ? r.x0f + d * full : nullptr;
+  } else {                   // the forward keeps copies of s0 for x_0 .. x_{d-1}
+    r.xd = take(full);
+    r.x0f = take(full);
+    r.s0 = take(operand);
+    r.s1 = take(half);
+    r.xkeep = take16(d * operand);
   }
-  // ---- first convolution (fp32 kernels) ----
-  HIP_TRY(launch_join_f32(W.ghi, W.glo, W.g32, n, h, w, F, s));
-  HIP_TRY(launch_relu_mask(W.g32, W.x0f, pix * F, s));
-  HIP_TRY(wgrad32(W.in16, 16, W.g32, F, c->layers[0]));
-  return DSEN2_OK;
+  r.tkeep = take16(d * operand);
+  r.out = take(pix * m->cout);
+  r.gpad = take(pix * 16);
+  r.g = take(full);
+  if (f.planes) {
+    r.gs0 = take(operand);
+    r.gs1 = take(half);
+  }
+  r.du = take16(operand);
+  if (f.planes) {
+    r.zs0 = take(operand);
+    r.zs1 = take(half);
+  }
+  r.wg = take(wg);
+  r.wg_floats = wg;
+  r.partial = reinterpret_cast<double*>(take(2 * mae_loss_partial_doubles(pix)));
+  r.loss2 = take(2);
+  r.bytes = off * sizeof(float);
+  return r;
 }
 
-// dsen2_model_gradients of a precision-2 model (arguments checked, training state present); see the file comment
-int gradients_x3(dsen2_model* m, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out, float* grad,
-                 float* loss2, int n, int h, int w, void* ws, hipStream_t s) {
-  TrainWs3 W = carve_x3(m, n, h, w, reinterpret_cast<char*>(ws));
+// dsen2_model_gradients (arguments checked, training state present) in the step format f; see the file comment
+int gradients(const StepFormat& f, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out, float* grad,
+              float* loss2, int n, int h, int w, void* ws, hipStream_t s) {
+  const dsen2_model* m = f.plan;
+  TrainWs W = carve(f, n, h, w, reinterpret_cast<char*>(ws));
   if (!dev_out) dev_out = W.out;
   if (!loss2) loss2 = W.loss2;
   const TrainState* t = m->train;
@@ -552,55 +369,70 @@ int gradients_x3(dsen2_model* m, const float* x10, const float* x20, const float
   const int F = m->feat, d = m->num_layers;
   const size_t pix = (size_t)n * h * w;
   const size_t fbytes = pix * F * sizeof(float);
-  const Layer& LO = m->layers.back();
   auto kept = [&](char* base, int l) { return base + (size_t)l * W.keep_step * sizeof(float); };
+  auto kept32 = [&](char* base, int l) { return reinterpret_cast<float*>(kept(base, l)); };
+  auto wgrad32 = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly, float scale) -> hipError_t {
+    float* dw = grad + Ly.flat_off;
+    return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.plan.cin, Ly.plan.cout, scale, dw, dw + (size_t)9 * Ly.plan.cin * Ly.plan.cout, W.wg,
+                                W.wg_floats, s);
+  };
+  auto dgrad = [&](const void* in, size_t li, const void* aux, void* out, void* out2, float scale, int epilogue) -> hipError_t {
+    ConvParams p = make_params(reinterpret_cast<const float*>(in), t->dg + t->dg_off[li], zero, reinterpret_cast<const float*>(aux),
+                               reinterpret_cast<float*>(out), n, h, w, 0, scale);
+    p.out2 = out2;
+    return launch(li + 1 == m->layers.size() ? t->out_plan : t->body_plan, p, epilogue, m->tune, s);
+  };
 
-  // ---- forward on the precision-2 per-layer launches, t_l and hx of every x_l kept ----
+  // ---- forward, every activation kept: dsen2_model_forward's own launches (forward_launches), so the same bits.  The
+  // NHWC16 input is packed here whatever the first convolution reads: the first layer's weight gradient needs it ----
   HIP_TRY(launch_pack_inputs(x10, x20, x60, m->c10, m->c20, m->c60, W.in16, n, h, w, s));
   ForwardWs B;
-  B.x0 = W.in16; B.a = W.a32; B.hx = W.hx; B.lo16 = W.lo16; B.t2 = W.tkeep; B.xkeep = W.xkeep; B.x0f = W.x0f;
+  B.x0 = W.in16; B.a = f.planes ? W.xd : W.x0f; B.t = kept32(W.tkeep, 0);
+  B.s0 = W.s0; B.s1 = W.s1; B.t16 = W.tkeep; B.xkeep = W.xkeep; B.x0f = W.x0f;
   if (int rc = forward_launches(m, x10, x20, x60, dev_out, n, h, w, B, W.keep_step, true, s, nullptr)) return rc;
 
   // ---- loss, output layer (fp32 kernels) ----
   HIP_TRY(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, s));
-  auto wgrad32 = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly) -> hipError_t {
-    float* dw = grad + Ly.flat_off;
-    return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.plan.cin, Ly.plan.cout, 1.f, dw, dw + (size_t)9 * Ly.plan.cin * Ly.plan.cout, W.wg,
-                                W.wg_floats, s);
-  };
-  auto wgrad16 = [&](const void* a, const void* g, const Layer& Ly, float scale) -> hipError_t {
-    float* dw = grad + Ly.flat_off;
-    return launch_conv3x3_wgrad16(a, g, n, h, w, F, scale, dw, dw + (size_t)9 * F * F, W.wg, W.wg_floats, s);
-  };
-  HIP_TRY(wgrad32(W.a32, F, W.gpad, 16, LO));
-  HIP_TRY(hipMemsetAsync(W.g32, 0, fbytes, s));
-  HIP_TRY(launch(t->out_plan, make_params(W.gpad, t->dg + t->dg_off[m->layers.size() - 1], zero, W.g32, W.g32, n, h, w, 0, 1.f), kEpiResidual,
-                 m->tune, s));
-  // g as a precision-2 residual stream; the zero stream 0.1 * dgradB is added to (its epilogue never writes it)
-  HIP_TRY(launch_split3_f32(W.g32, W.ghx, W.glo, n, h, w, F, s));
-  HIP_TRY(hipMemsetAsync(W.zhx, 0, fbytes, s));
-  HIP_TRY(hipMemsetAsync(W.zlo, 0, fbytes / 2, s));
+  HIP_TRY(wgrad32(W.xd, F, W.gpad, 16, m->layers.back(), 1.f));
+  HIP_TRY(hipMemsetAsync(W.g, 0, fbytes, s));
+  HIP_TRY(dgrad(W.gpad, m->layers.size() - 1, W.g, W.g, nullptr, 1.f, kEpiResidual));
+
   // ---- residual blocks, last to first ----
-  for (int l = d; l >= 1; --l) {
-    const Layer& LA = m->layers[2 * l - 1];
-    const Layer& LB = m->layers[2 * l];
-    const char* t_l = kept(W.tkeep, l - 1);
-    HIP_TRY(wgrad16(t_l, W.ghx, LB, 0.1f));
-    ConvParams pb = make_params(reinterpret_cast<const float*>(W.ghx), t->dg + t->dg_off[2 * l], zero, reinterpret_cast<const float*>(W.zhx),
-                                W.g32, n, h, w, 0, 0.1f);
-    pb.out2 = W.zlo;
-    HIP_TRY(launch(t->body_plan, pb, kEpiResidualF32, m->tune, s));
-    HIP_TRY(launch_mask_split3(W.g32, t_l, W.du, n, h, w, F, s));
-    HIP_TRY(wgrad16(kept(W.xkeep, l - 1), W.du, LA, 1.f));
-    ConvParams pa = make_params(reinterpret_cast<const float*>(W.du), t->dg + t->dg_off[2 * l - 1], zero, reinterpret_cast<const float*>(W.ghx),
-                                reinterpret_cast<float*>(W.ghx), n, h, w, 0, 1.f);
-    pa.out2 = W.glo;
-    HIP_TRY(launch(t->body_plan, pa, kEpiResidual, m->tune, s));
+  if (f.planes == 0) {
+    for (int l = d; l >= 1; --l) {
+      float* du = reinterpret_cast<float*>(W.du);
+      HIP_TRY(wgrad32(kept32(W.tkeep, l - 1), F, W.g, F, m->layers[2 * l], 0.1f));
+      HIP_TRY(hipMemsetAsync(du, 0, fbytes, s));
+      HIP_TRY(dgrad(W.g, 2 * l, du, du, nullptr, 0.1f, kEpiResidual));
+      HIP_TRY(launch_relu_mask(du, kept32(W.tkeep, l - 1), pix * F, s));
+      HIP_TRY(wgrad32(kept32(W.xkeep, l - 1), F, du, F, m->layers[2 * l - 1], 1.f));
+      HIP_TRY(dgrad(du, 2 * l - 1, W.g, W.g, nullptr, 1.f, kEpiResidual));
+    }
+  } else {
+    const bool x3 = f.planes == 2;
+    const size_t operand_bytes = x3 ? fbytes : fbytes / 2;
+    auto wgrad16 = [&](const void* a, const void* g, const Layer& Ly, float scale) -> hipError_t {
+      float* dw = grad + Ly.flat_off;
+      return (x3 ? launch_conv3x3_wgrad16 : launch_conv3x3_wgrad16_bf16)(a, g, n, h, w, F, scale, dw, dw + (size_t)9 * F * F, W.wg, W.wg_floats, s);
+    };
+    // g as a residual stream of the plan's precision; the zero stream 0.1 * dgradB is added to (its fp32 epilogue never writes it)
+    HIP_TRY((x3 ? launch_split3_f32 : launch_split_f32)(W.g, W.gs0, W.gs1, n, h, w, F, s));
+    HIP_TRY(hipMemsetAsync(W.zs0, 0, operand_bytes, s));
+    HIP_TRY(hipMemsetAsync(W.zs1, 0, fbytes / 2, s));
+    for (int l = d; l >= 1; --l) {
+      const char* t_l = kept(W.tkeep, l - 1);
+      HIP_TRY(wgrad16(t_l, W.gs0, m->layers[2 * l], 0.1f));
+      HIP_TRY(dgrad(W.gs0, 2 * l, W.zs0, W.g, W.zs1, 0.1f, kEpiResidualF32));
+      HIP_TRY((x3 ? launch_mask_split3 : launch_mask_round16)(W.g, t_l, W.du, n, h, w, F, s));
+      HIP_TRY(wgrad16(kept(W.xkeep, l - 1), W.du, m->layers[2 * l - 1], 1.f));
+      HIP_TRY(dgrad(W.du, 2 * l - 1, W.gs0, W.gs0, W.gs1, 1.f, kEpiResidual));
+    }
+    HIP_TRY((x3 ? launch_join3_f32 : launch_join_f32)(W.gs0, W.gs1, W.g, n, h, w, F, s));
   }
+
   // ---- first convolution (fp32 kernels) ----
-  HIP_TRY(launch_join3_f32(W.ghx, W.glo, W.g32, n, h, w, F, s));
-  HIP_TRY(launch_relu_mask(W.g32, W.x0f, pix * F, s));
-  HIP_TRY(wgrad32(W.in16, 16, W.g32, F, m->layers[0]));
+  HIP_TRY(launch_relu_mask(W.g, W.x0f, pix * F, s));
+  HIP_TRY(wgrad32(W.in16, 16, W.g, F, m->layers[0], 1.f));
   return DSEN2_OK;
 }
 
@@ -609,20 +441,16 @@ int gradients_x3(dsen2_model* m, const float* x10, const float* x20, const float
 namespace dsen2 {
 
 int train_state_after_load(dsen2_model* m) {
-  if (m->train->packed16) {
+  TrainState* t = m->train;
+  if (packed16(m)) {
     // the packed planes do not hold the fp32 weights: the master copy is the vector dsen2_model_load_weights was given
     if (m->host_flat.size() != m->n_params) return fail(DSEN2_ERR_INTERNAL, "the loaded weights were not kept");
-    HIP_TRY(hipMemcpy(m->train->master, m->host_flat.data(), m->n_params * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t->master, m->host_flat.data(), m->n_params * sizeof(float), hipMemcpyHostToDevice));
     std::vector<float>().swap(m->host_flat);
-    if (int rc = repack_x3(m, false, nullptr)) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return DSEN2_OK;
+  } else {
+    HIP_TRY(launch_scatter(t->master, m->dev_params, t->fwd_map, m->dev_param_floats, nullptr));     // the inverse gather
   }
-  if (int rc = refresh_from_packed(m, nullptr)) return rc;
-  if (dsen2_model* c = m->train->amp) {       // the companion's packed buffers follow the master copy
-    if (int rc = repack_x3(c, true, nullptr)) return rc;
-    c->loaded = true;
-  }
+  if (int rc = repack_from_master(m, false, nullptr)) return rc;
   HIP_TRY(hipStreamSynchronize(nullptr));
   return DSEN2_OK;
 }
@@ -636,7 +464,7 @@ int dsen2_model_train_workspace_bytes(const dsen2_model* m, int n, int h, int w,
     if (!bytes) return fail(DSEN2_ERR_INVALID, "NULL argument");
     if (int rc = check_train_model(m)) return rc;
     if (int rc = check_shape(m, n, h, w)) return rc;
-    *bytes = train_ws_bytes(m, n, h, w);
+    *bytes = carve(step_format(m), n, h, w, nullptr).bytes;
     return DSEN2_OK;
   });
 }
@@ -649,57 +477,10 @@ int dsen2_model_gradients(dsen2_model* m, const float* x10, const float* x20, co
     if ((m->c60 > 0) != (x60 != nullptr)) return fail(DSEN2_ERR_INVALID, "x60 must be given iff the model has a 60 m input");
     if (!m->loaded) return fail(DSEN2_ERR_NO_WEIGHTS, "no weights: dsen2_model_load_weights or dsen2_model_set_weights_device first");
     if (int rc = check_shape(m, n, h, w)) return rc;
-    const size_t need = train_ws_bytes(m, n, h, w);
+    const size_t need = carve(step_format(m), n, h, w, nullptr).bytes;
     if (ws_bytes < need) return fail(DSEN2_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
     if (int rc = ensure_train_state(m)) return rc;
-    if (m->train->packed16) return gradients_x3(m, x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
-    if (m->train->amp) return gradients_amp(m, x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
-    TrainWs W = carve(m, n, h, w, reinterpret_cast<char*>(ws));
-    if (!dev_out) dev_out = W.out;
-    if (!loss2) loss2 = W.loss2;
-    hipStream_t s = (hipStream_t)stream_;
-    const TrainState* t = m->train;
-    const float* zero = t->dg + t->zero_off;
-    const int F = m->feat, d = m->num_layers;
-    const size_t pix = (size_t)n * h * w;
-    const Layer& LO = m->layers.back();
-
-    // ---- forward, every activation kept: dsen2_model_forward's own launches (forward_launches), so the same bits.  The
-    // NHWC16 input is packed here whatever the first convolution reads: the first layer's weight gradient needs it ----
-    HIP_TRY(launch_pack_inputs(x10, x20, x60, m->c10, m->c20, m->c60, W.in16, n, h, w, s));
-    ForwardWs B;
-    B.x0 = W.in16;
-    B.a = W.X[0];
-    B.t = d > 0 ? W.T[1] : nullptr;
-    if (int rc = forward_launches(m, x10, x20, x60, dev_out, n, h, w, B, W.keep_step, true, s, nullptr)) return rc;
-
-    // ---- loss, output layer ----
-    HIP_TRY(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, s));
-    auto wgrad = [&](const float* a, int ca, const float* g, int cg, const Layer& Ly, float scale) -> hipError_t {
-      float* dw = grad + Ly.flat_off;
-      return launch_conv3x3_wgrad(a, ca, g, cg, n, h, w, Ly.plan.cin, Ly.plan.cout, scale, dw, dw + (size_t)9 * Ly.plan.cin * Ly.plan.cout, W.wg,
-                                  W.wg_floats, s);
-    };
-    HIP_TRY(wgrad(W.X[d], F, W.gpad, 16, LO, 1.f));
-    const size_t fbytes = pix * F * sizeof(float);
-    HIP_TRY(hipMemsetAsync(W.G, 0, fbytes, s));
-    HIP_TRY(launch(t->out_plan, make_params(W.gpad, t->dg + t->dg_off[m->layers.size() - 1], zero, W.G, W.G, n, h, w, 0, 1.f), kEpiResidual,
-                   m->tune, s));
-    // ---- residual blocks, last to first ----
-    for (int l = d; l >= 1; --l) {
-      const Layer& LA = m->layers[2 * l - 1];
-      const Layer& LB = m->layers[2 * l];
-      HIP_TRY(wgrad(W.T[l], F, W.G, F, LB, 0.1f));
-      HIP_TRY(hipMemsetAsync(W.DU, 0, fbytes, s));
-      HIP_TRY(launch(t->body_plan, make_params(W.G, t->dg + t->dg_off[2 * l], zero, W.DU, W.DU, n, h, w, 0, 0.1f), kEpiResidual, m->tune, s));
-      HIP_TRY(launch_relu_mask(W.DU, W.T[l], pix * F, s));
-      HIP_TRY(wgrad(W.X[l - 1], F, W.DU, F, LA, 1.f));
-      HIP_TRY(launch(t->body_plan, make_params(W.DU, t->dg + t->dg_off[2 * l - 1], zero, W.G, W.G, n, h, w, 0, 1.f), kEpiResidual, m->tune, s));
-    }
-    // ---- first convolution ----
-    HIP_TRY(launch_relu_mask(W.G, W.X[0], pix * F, s));
-    HIP_TRY(wgrad(W.in16, 16, W.G, F, m->layers[0], 1.f));
-    return DSEN2_OK;
+    return gradients(step_format(m), x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
   });
 }
 
@@ -722,22 +503,10 @@ int dsen2_model_set_weights_device(dsen2_model* m, const float* dev_flat, void* 
     if (!m->dev_params) HIP_TRY(hipMalloc((void**)&m->dev_params, m->dev_param_floats * sizeof(float)));
     if (int rc = ensure_train_state(m)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    TrainState* t = m->train;
-    if (dev_flat != t->master)
-      HIP_TRY(hipMemcpyAsync(t->master, dev_flat, m->n_params * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (t->packed16) {
-      std::vector<float>().swap(m->host_flat);
-      if (int rc = repack_x3(m, true, s)) return rc;
-      m->loaded = true;
-      return DSEN2_OK;
-    }
-    HIP_TRY(launch_gather(m->dev_params, t->master, t->fwd_map, m->dev_param_floats, s));     // predict / evaluate read these
-    if (t->amp) {       // the step runs on the companion: its packed buffers and bf16 dgrad weights, not the fp32 dgrad weights
-      if (int rc = repack_x3(t->amp, true, s)) return rc;
-      t->amp->loaded = true;
-    } else {
-      HIP_TRY(launch_gather(t->dg, t->master, t->dg_map, t->dg_floats, s));
-    }
+    if (dev_flat != m->train->master)
+      HIP_TRY(hipMemcpyAsync(m->train->master, dev_flat, m->n_params * sizeof(float), hipMemcpyDeviceToDevice, s));
+    std::vector<float>().swap(m->host_flat);      // (a bf16x3 model's kept load: the master copy has taken its place)
+    if (int rc = repack_from_master(m, true, s)) return rc;
     m->loaded = true;
     return DSEN2_OK;
   });
