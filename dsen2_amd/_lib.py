@@ -95,6 +95,10 @@ SIGNATURES = {
                                 c_void_p]),
     'dsen2_recompose_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_float,
                                      c_int, c_int, c_void_p]),
+    'dsen2_tile_nodata_geometry': (c_int, [c_int, c_int, c_int, c_int, c_int_p, c_int_p, ctypes.POINTER(c_size_t)]),
+    'dsen2_tile_nodata': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'dsen2_recompose_rows_nodata': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                            ctypes.c_float, c_int, c_int, c_void_p]),
     'dsen2_corpus_create': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
     'dsen2_corpus_destroy': (None, [c_void_p]),
     'dsen2_corpus_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -5,7 +5,7 @@
                                   [--roi_lon_lat lon1,lat1,lon2,lat2] [--list_bands] [--list_UTM]
                                   [--list_output_file_formats]
                                   [--bands10 B4,B3,B2,B8] [--models DIR] [--precision fp32|bf16|bf16x3] [--deep]
-                                  [--self_ensemble]
+                                  [--self_ensemble] [--skip_nodata]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         -m dsen2_amd.cli INPUT [OUTPUT] ...                       one process per GPU: the patches of the tile are
         sharded over the ranks (dsen2_amd/dist.py: RCCL over xGMI), rank 0 receives the predictions, recomposes
@@ -339,6 +339,9 @@ def main(argv=None):
     ap.add_argument('--precision', default=None, choices=['fp32', 'bf16', 'bf16x3'])
     ap.add_argument('--self_ensemble', action='store_true',
                     help='geometric self-ensemble: average the predictions for the 8 flips and rotations of every patch (~8x the network time)')
+    ap.add_argument('--skip_nodata', action='store_true',
+                    help='no-data in, no-data out: a 10 m pixel that is 0 in every band is written as 0 in every super-resolved band, '
+                         'and patches without any data are not computed')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='under torch.distributed.run: nccl = RCCL, one GPU per rank; gloo = rehearsal with shared GPUs')
     args = ap.parse_args(argv)
@@ -383,6 +386,8 @@ def _run(args):
         supres.PRECISION = args.precision
     if args.self_ensemble:
         supres.SELF_ENSEMBLE = True
+    if args.skip_nodata:
+        supres.SKIP_NODATA = True
 
     roi = [float(v) for v in re.split(',', args.roi_x_y)] if args.roi_x_y else None
     product = None

@@ -268,6 +268,53 @@ def final_row_runs(have, done_rows, size, inner):
     return runs
 
 
+def final_row_runs_slots(slot_of_patch, slots_done, per, done_rows, size, inner):
+    """final_row_runs for a compact patch buffer (`slot_map`): patch k is final when it is empty (slot -1: nothing will ever be
+    computed for it) or when its slot is among the first `slots_done` of its shard of `per` slots (one rank: per = all kept
+    patches)."""
+    slot = np.asarray(slot_of_patch)
+    have = slot < 0
+    if per > 0:
+        have = have | ((slot >= 0) & (slot % per < slots_done))
+    return final_row_runs(have, done_rows, size, inner)
+
+
+# ---- no-data (not in the reference; csrc/nodata.hip) ---------------------------------------------
+def nodata_geometry(size, patch, border):
+    """(x_tiles, y_tiles, bitmap_words) of dsen2_tile_nodata_geometry: host only; DSen2Error for a geometry the recomposition
+    refuses."""
+    xt, yt, words = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
+    _lib.call('dsen2_tile_nodata_geometry', int(size[0]), int(size[1]), int(patch), int(border), ctypes.byref(xt), ctypes.byref(yt),
+              ctypes.byref(words))
+    return xt.value, yt.value, words.value
+
+
+def nodata_device(img10_dev, patch, border):
+    """[H,W,C10] float32 CUDA tensor -> (patch_empty uint8 [y_tiles * x_tiles], valid_bits int32 [H, ceil(W / 32)]), both on the
+    device (dsen2_tile_nodata): a pixel holds data unless all its bands are exactly 0; a patch is empty when the rectangle of the
+    image that recompose_images takes from it holds no data.  Enqueues only."""
+    H, W, C = img10_dev.shape
+    xt, yt, words = nodata_geometry((H, W), patch, border)
+    if not 1 <= C <= 16:
+        raise ValueError('no-data detection takes 1..16 bands, got %d' % C)
+    dev = img10_dev.device
+    empty = torch.empty(xt * yt, dtype=torch.uint8, device=dev)
+    bits = torch.empty((H, words // H), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call('dsen2_tile_nodata', _ptr(img10_dev), H, W, C, int(patch), int(border), _ptr(empty), _ptr(bits), _stream(dev))
+    return empty, bits
+
+
+def slot_map(patch_empty):
+    """Host side, numpy: (kept, slot_of_patch) — the indices of the patches that are not empty, ascending, and the int32 map
+    patch index -> position in that list, -1 for an empty patch."""
+    empty = np.asarray(patch_empty).reshape(-1) != 0
+    kept = np.nonzero(~empty)[0].astype(np.int64)
+    slot_of_patch = np.full(empty.size, -1, np.int32)
+    slot_of_patch[kept] = np.arange(kept.size, dtype=np.int32)
+    return kept, slot_of_patch
+
+
 def recompose_device(a_dev, border, size, scale=1.0):
     """[N,C,P,P] CUDA tensor -> [size0,size1,C] CUDA tensor (N > 1)."""
     n, c, p, _ = a_dev.shape
@@ -279,11 +326,28 @@ def recompose_device(a_dev, border, size, scale=1.0):
     return img
 
 
-def recompose_rows_device(a_dev, border, img, row0, row1, scale=1.0):
+def recompose_rows_device(a_dev, border, img, row0, row1, scale=1.0, slots=None, valid_bits=None):
     """Rows [row0, row1) of `img` ([H,W,C] CUDA tensor) from the patch buffer a_dev [N,C,P,P] (dsen2_recompose_rows): only the
-    patches those rows read need to be final."""
+    patches those rows read need to be final.  slots (int32 device tensor, patch index -> index in a_dev or -1: `slot_map`) and
+    valid_bits (`nodata_device`), given together: a_dev is the compact buffer of the kept patches, and a pixel without data, or
+    whose patch has no slot in a_dev, becomes 0 (dsen2_recompose_rows_nodata)."""
     n, c, p, _ = a_dev.shape
     H, W = int(img.shape[0]), int(img.shape[1])
+    if (slots is None) != (valid_bits is None):
+        raise ValueError('slots and valid_bits go together')
+    if slots is not None:
+        if slots.dtype != torch.int32 or valid_bits.dtype != torch.int32 or not slots.is_contiguous() or not valid_bits.is_contiguous():
+            raise TypeError('slots and valid_bits are contiguous int32 tensors')
+        xt, yt, words = nodata_geometry((H, W), p, border)
+        if slots.numel() != xt * yt or valid_bits.numel() != words:
+            raise ValueError('slot map of %d entries and bitmap of %d words for a %d x %d grid and %d words'
+                             % (slots.numel(), valid_bits.numel(), yt, xt, words))
+        if int(img.shape[2]) != c:
+            raise ValueError('image of %d channels for patches of %d' % (int(img.shape[2]), c))
+        with torch.cuda.device(img.device):
+            _lib.call('dsen2_recompose_rows_nodata', _ptr(a_dev) if n else None, n, c, p, border, _ptr(slots), _ptr(valid_bits),
+                      _ptr(img), H, W, float(scale), int(row0), int(row1), _stream(img.device))
+        return
     with torch.cuda.device(a_dev.device):
         _lib.call('dsen2_recompose_rows', _ptr(a_dev), n, c, p, border, _ptr(img), H, W, float(scale), int(row0), int(row1),
                   _stream(a_dev.device))

@@ -16,6 +16,8 @@ and re-read on every call as the reference does (supres.py:59,63) — observable
 from __future__ import division
 
 import contextlib
+import functools
+import inspect
 import os
 
 import numpy as np
@@ -36,8 +38,19 @@ PRECISION = os.environ.get('DSEN2_PRECISION', 'fp32')
 # each prediction is turned back and the 8 are averaged (S2Model.forward_device_ensemble) — about 8 x the network time of a tile;
 # tiling, up-sampling, recomposition and the sharding over ranks are untouched (the ensemble is per patch).  Default off.
 SELF_ENSEMBLE = os.environ.get('DSEN2_SELF_ENSEMBLE', '0') not in ('', '0')
+# Nor this: no-data in, no-data out.  On: a 10 m pixel whose bands are all exactly 0 (the sensor's fill value) comes back as 0 in
+# every output band, and a patch that decides no pixel with data is never gathered, up-sampled, predicted, sent or read
+# (csrc/nodata.hip); everywhere else the image is the one the option off returns, bit for bit.  Default off.
+SKIP_NODATA = os.environ.get('DSEN2_SKIP_NODATA', '0') not in ('', '0')
 
 _MODEL_CACHE = {}
+_LAST_RUN = {}
+
+
+def last_run_stats():
+    """{'patches': ..., 'kept': ..., 'skipped': ...} of the last DSen2_20 / DSen2_60 call of this process (a copy): the patches of
+    the tile, those that were predicted and those SKIP_NODATA left out (always 0 with the option off)."""
+    return dict(_LAST_RUN)
 
 
 def _weight_file(deep, run_60):
@@ -100,10 +113,14 @@ class Shard(object):
     only the rows those patches read (1/world of the tile; everything when there is one rank) and, once, the origins shifted
     into that slab: batch() only enqueues."""
 
-    def __init__(self, dsets, scales, patch_sizes, borders, my_org, world):
+    def __init__(self, dsets, scales, patch_sizes, borders, my_org, world, img10=None):
         dev = _patches.default_device()
         self.org, self.geom, self.imgs, self.org_dev = my_org, list(zip(scales, patch_sizes, borders)), [], []
-        for d, (s, ps, b) in zip(dsets, self.geom):
+        for k, (d, (s, ps, b)) in enumerate(zip(dsets, self.geom)):
+            if k == 0 and img10 is not None:       # SKIP_NODATA: the whole 10 m raster is on the device already
+                self.imgs.append(img10)
+                self.org_dev.append(_patches.device_origins(my_org, s, dev))
+                continue
             r0, r1 = _row_slab(my_org, s, ps, b, d.shape[0]) if world > 1 else (0, d.shape[0])
             self.imgs.append(_patches._to_device_f32(d[r0:r1], dev))
             self.org_dev.append(_patches.device_origins(my_org, s, dev, row0=r0))
@@ -150,8 +167,9 @@ class RowSink(object):
     waits for the collective's.  `with sink.tail():` — entered when the shard is enqueued — allocates the buffer and makes that
     stream current; every band is then downloaded right behind its recomposition and finish() only waits."""
 
-    def __init__(self, shape, dev, own_stream=False):
+    def __init__(self, shape, dev, own_stream=False, nodata=None):
         self.dev = dev
+        self.nodata = nodata        # SKIP_NODATA: (slot map, bitmap) on the device; the patch buffers are then compact
         self.img = torch.empty(shape, dtype=torch.float32, device=dev)         # [H, W, cout]
         self.pinned = _pinned_wanted(shape)
         self.host, self.bands, self.stream = None, [], None
@@ -176,7 +194,8 @@ class RowSink(object):
     def rows(self, src_patches, border, r0, r1):
         """Image rows [r0, r1) from the patch buffer (whole patches with their border, or inner crops with border 0: they tile
         alike, patches.py:380-403), on the current stream; `images *= SCALE` (supres.py:29) folded into the recomposition."""
-        _patches.recompose_rows_device(src_patches, border, self.img, r0, r1, scale=SCALE)
+        slots, bits = self.nodata if self.nodata is not None else (None, None)
+        _patches.recompose_rows_device(src_patches, border, self.img, r0, r1, scale=SCALE, slots=slots, valid_bits=bits)
         if self.stream is not None:
             if self.host is not None:
                 self.host[r0:r1].copy_(self.img[r0:r1], non_blocking=True)
@@ -201,9 +220,12 @@ class RowSink(object):
         return self.host.numpy() if self.host is not None else self.img.cpu().numpy()
 
 
-def _final_bands(slots_done, per, done_rows, size, inner):
+def _final_bands(slots_done, per, done_rows, size, inner, slot_of_patch=None):
     """[(r0, r1)] image rows that became final now that the first `slots_done` slots of every shard of `per` patches are
-    there (one rank: per = all patches, slots_done = patches computed so far); `done_rows` as in patches.final_row_runs."""
+    there (one rank: per = all patches, slots_done = patches computed so far); `done_rows` as in patches.final_row_runs.
+    slot_of_patch (SKIP_NODATA): the shards hold the kept patches only, and an empty patch is final from the start."""
+    if slot_of_patch is not None:
+        return _patches.final_row_runs_slots(slot_of_patch, slots_done, per, done_rows, size, inner)
     x_tiles = _patches.recompose_grid(size, inner, 0)[0]
     return _patches.final_row_runs(np.arange(x_tiles * done_rows.size) % per < slots_done, done_rows, size, inner)
 
@@ -216,7 +238,20 @@ def _gather_chunks():
     return max(1, int(os.environ.get('DSEN2_GATHER_CHUNKS', '8')))
 
 
-def _run(dsets, scales, patch, border, deep, run_60):
+def _nodata_plan(d10_dev, patch, border, used):
+    """SKIP_NODATA: (kept patch indices, slot map on the host, (slot map, bitmap) on the device) of the uploaded 10 m raster.  The
+    flags come to the host in ONE small read — the only synchronisation the option adds, before anything is enqueued."""
+    empty_dev, bits = _patches.nodata_device(d10_dev, patch, border)
+    empty = empty_dev.cpu().numpy()
+    if empty.size != used:
+        raise ValueError('the 10 m image of %r pixels has %d patches to recompose but the tiling of the lowest resolution has %d: '
+                         'skip_nodata needs images in the exact size ratio' % (tuple(d10_dev.shape[:2]), empty.size, used))
+    kept, slot_of_patch = _patches.slot_map(empty)
+    return kept, slot_of_patch, (torch.from_numpy(slot_of_patch).to(d10_dev.device), bits)
+
+
+def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None):
+    skip_nodata = SKIP_NODATA if skip_nodata is None else bool(skip_nodata)
     _patches.check_sizes(dsets, scales)
     dev = _patches.default_device()
     rank, world = _dist.rank_world()
@@ -227,10 +262,34 @@ def _run(dsets, scales, patch, border, deep, run_60):
     model = _get_model(tuple((int(d.shape[2]), None, None) for d in dsets), deep, run_60)
     cout, size, inner = model.cout, dsets[0].shape, patch - 2 * border
     shape = (int(size[0]), int(size[1]), cout)
+    single = n_alloc == 1            # recompose_images' single-patch shortcut (patches.py:375-376): a[0] uncropped
+    _LAST_RUN.clear()
+    _LAST_RUN.update(patches=used, kept=used, skipped=0)
+    # SKIP_NODATA: the 10 m raster goes up once, whole, on every rank (it serves the flags, the gather and, through the bitmap, the
+    # recomposition), every rank computes the same flags, and everything below — origins, `used`, the shard ranges, the buffers,
+    # the gathers — works on the KEPT patches; slot_of_patch says where a patch of the grid lies among them.
+    img10 = slot_of_patch = nodata = None
+    if skip_nodata:
+        img10 = _patches._to_device_f32(dsets[0], dev)
+        if single:
+            valid = (img10 != 0).any(dim=2)
+            if tuple(valid.shape) != (patch, patch):
+                raise ValueError('skip_nodata: the single-patch shortcut returns the %d x %d patch, not the %r image' % (patch, patch, tuple(valid.shape)))
+            if not bool(valid.any()):
+                _LAST_RUN.update(kept=0, skipped=1)
+                return np.zeros((patch, patch, cout), np.float32) if rank == 0 else None
+        else:
+            kept, slot_of_patch, nodata = _nodata_plan(img10, patch, border, used)
+            _LAST_RUN.update(kept=int(kept.size), skipped=used - int(kept.size))
+            org, used = org[kept], int(kept.size)
+            if used == 0:            # nothing holds data: the zero image, no forward, no collective (every rank knows)
+                if rank != 0:
+                    return None
+                print((cout, size[0], size[1]))                            # patches.py:392
+                return np.zeros(shape, np.float32)
     # this rank's contiguous share of the USED patches (the reference's trailing all-zero patches are
     # never read by recompose_images, so they are not computed)
     first, count = _dist.shard_range(used)
-    single = n_alloc == 1            # recompose_images' single-patch shortcut (patches.py:375-376): a[0] uncropped
     done_rows = np.zeros(_patches.recompose_grid(size, patch, border)[1], bool)
     # Where this rank's predictions go and who feeds the sink.  One rank (or the single patch): whole patches; a large image
     # leaves in bands, each right after the batch that completes its rows.  Several ranks: the inner crops, in the [per, ...]
@@ -248,11 +307,11 @@ def _run(dsets, scales, patch, border, deep, run_60):
         if _chunked_gather_wanted():
             cg = _dist.ChunkedGather(send, used, _gather_chunks())
             if rank == 0:
-                sink = RowSink(shape, dev, own_stream=True)            # BEFORE the loop: its stream waits for nothing later
+                sink = RowSink(shape, dev, own_stream=True, nodata=nodata)     # BEFORE the loop: its stream waits for nothing later
     if count > 0:
-        shard = Shard(dsets, scales, patch_sizes, borders, org[first:first + count], world)
+        shard = Shard(dsets, scales, patch_sizes, borders, org[first:first + count], world, img10=img10)
         if banded:
-            sink = RowSink(shape, dev)
+            sink = RowSink(shape, dev, nodata=nodata)
         bs = model.preferred_batch(patch, patch, ensemble=True) if SELF_ENSEMBLE else model.preferred_batch(patch, patch)
         forward = model.forward_device_ensemble if SELF_ENSEMBLE else model.forward_device
         for i0 in range(0, count, bs):                                 # this loop only enqueues
@@ -261,7 +320,7 @@ def _run(dsets, scales, patch, border, deep, run_60):
             if send is None:
                 forward(xs, out=pred[i0:i0 + n])
                 if banded:
-                    for r0, r1 in _final_bands(i0 + n, used, done_rows, size, inner):
+                    for r0, r1 in _final_bands(i0 + n, used, done_rows, size, inner, slot_of_patch):
                         sink.rows(pred, border, r0, r1)
             else:
                 y = forward(xs)
@@ -271,7 +330,12 @@ def _run(dsets, scales, patch, border, deep, run_60):
                     cg.issue(issued)
                     issued += 1
     if single:
-        return (pred[0].permute(1, 2, 0).contiguous() * SCALE).cpu().numpy() if rank == 0 else None
+        if rank != 0:
+            return None
+        image = pred[0].permute(1, 2, 0).contiguous() * SCALE
+        if skip_nodata:
+            image = torch.where(valid[:, :, None], image, torch.zeros_like(image))
+        return image.cpu().numpy()
     if cg is not None:
         # every rank issues every gather (a short or empty shard too); the send buffer stays alive until every piece has left
         for c in range(issued, cg.n_chunks):
@@ -284,7 +348,7 @@ def _run(dsets, scales, patch, border, deep, run_60):
         with sink.tail():
             for c in range(cg.n_chunks):
                 cg.complete(c)                                         # this stream waits for gather c
-                for r0, r1 in _final_bands(cg.slots_done(c), cg.per, done_rows, size, inner):
+                for r0, r1 in _final_bands(cg.slots_done(c), cg.per, done_rows, size, inner, slot_of_patch):
                     sink.rows(cg.recv, 0, r0, r1)
             assert done_rows.all()
             return sink.finish()
@@ -296,12 +360,28 @@ def _run(dsets, scales, patch, border, deep, run_60):
             return None
     print((cout, size[0], size[1]))                                    # patches.py:392
     if sink is None:                 # not in bands: the whole image in one
-        sink = RowSink(shape, dev)
+        sink = RowSink(shape, dev, nodata=nodata)
         sink.rows(pred, border, 0, shape[0])
     return sink.finish()
 
 
-def DSen2_20(d10, d20, deep=False):
+def _reference_surface(fn):
+    """fn(<the reference's parameters>, skip_nodata=None) as the public function: `skip_nodata` is taken BY KEYWORD ONLY, and
+    inspect.signature() reports the reference's parameters alone (testing/supres.py:15,33) — callers and tools that bind or
+    compare the drop-in surface by introspection see exactly the reference's; the option is this project's extension."""
+    sig = inspect.signature(fn)
+    reference = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != 'skip_nodata'])
+
+    @functools.wraps(fn)
+    def call(*args, skip_nodata=None, **kwargs):
+        bound = reference.bind(*args, **kwargs)           # TypeError for anything the reference's signature would refuse
+        return fn(*bound.args, skip_nodata=skip_nodata, **bound.kwargs)
+    call.__signature__ = reference
+    return call
+
+
+@_reference_surface
+def DSen2_20(d10, d20, deep=False, skip_nodata=None):
     """20 m -> 10 m.  d10 [x, y, 4] (B2 B3 B4 B8), d20 [x/2, y/2, 6] (B5 B6 B7 B8A B11 B12), any real dtype, HWC.
     deep=True selects VDSen2 (d=32, F=256).  Returns [x, y, 6] float32.  Geometry of testing/supres.py:21-22:
     patches of 128 with an 8-pixel border.
@@ -309,12 +389,16 @@ def DSen2_20(d10, d20, deep=False):
     With torch.distributed initialised (one process per GPU; every rank must make the same call with the same
     arrays — the call contains a collective) the patches are sharded over the ranks and ONLY RANK 0 returns the
     image; every other rank returns None.  The reference script's `if sr20 is None: exit` branch
-    (testing/s2_tiles_supres.py:346-348) is what a non-root rank then takes."""
-    return _run([d10, d20], [2, 1], patch=128, border=8, deep=deep, run_60=False)
+    (testing/s2_tiles_supres.py:346-348) is what a non-root rank then takes.
+
+    skip_nodata (keyword only, not in the reference and not part of the reported signature; None = supres.SKIP_NODATA): a pixel of d10 whose bands are all exactly 0 is returned
+    as 0 in every band, and patches that decide no pixel with data are not computed; all other pixels are unchanged, bit for bit."""
+    return _run([d10, d20], [2, 1], patch=128, border=8, deep=deep, run_60=False, skip_nodata=skip_nodata)
 
 
-def DSen2_60(d10, d20, d60, deep=False):
+@_reference_surface
+def DSen2_60(d10, d20, d60, deep=False, skip_nodata=None):
     """60 m -> 10 m.  As DSen2_20 plus d60 [x/6, y/6, 2] (B1 B9; B10 is not super-resolved).  Returns [x, y, 2]
     float32.  Geometry of testing/supres.py:40-41: patches of 192 with a 12-pixel border.  Under torch.distributed: the
-    image on rank 0, None on every other rank (see DSen2_20)."""
-    return _run([d10, d20, d60], [6, 3, 1], patch=192, border=12, deep=deep, run_60=True)
+    image on rank 0, None on every other rank (see DSen2_20).  skip_nodata: as DSen2_20."""
+    return _run([d10, d20, d60], [6, 3, 1], patch=192, border=12, deep=deep, run_60=True, skip_nodata=skip_nodata)

@@ -385,6 +385,35 @@ int dsen2_recompose(const float *dev_patches, int count, int C, int P, int borde
 int dsen2_recompose_rows(const float *dev_patches, int count, int C, int P, int border, float *dev_img, int H,
                          int W, float scale, int row0, int row1, void *stream);
 
+/* ---- tile no-data: which pixels and patches of a tile hold data, and the recomposition that honours it (csrc/nodata.hip) ----------
+ * Not in the reference.  Definitions, for a 10 m raster dev_img10 [H,W,C10] (HWC float32) and dsen2_recompose's tile grid
+ * (inner = P - 2*border, x_tiles = ceil(W/inner), y_tiles = ceil(H/inner)):
+ *   NO-DATA PIXEL    every one of its C10 bands is exactly 0 (-0.0 counts as 0; a NaN or a negative value is data): the sensor's
+ *                    fill value.  This is NOT the corpus test "band 0 < 1" below: a dark pixel with one zero band is data.
+ *   OWNED RECTANGLE  of tile (ty, tx): the pixels dsen2_recompose takes from that patch — rows [ty*inner, min((ty+1)*inner,
+ *                    H-inner)) for ty < y_tiles-1 and [H-inner, H) for the last tile row, columns alike.  They partition the image.
+ *   EMPTY PATCH      its owned rectangle holds no pixel with data.
+ * dsen2_tile_nodata_geometry (host only, touches no device): the grid and the size of the bitmap, bitmap_words = H * ceil(W/32).
+ * dsen2_tile_nodata reads the raster exactly once and writes
+ *   dev_patch_empty  uint8 [y_tiles*x_tiles], row-major, 1 = empty;
+ *   dev_valid_bits   uint32 [H][ceil(W/32)]: pixel (y, x) is bit x & 31 of word y*ceil(W/32) + (x >> 5), set when the pixel holds
+ *                    data; the bits at x >= W are 0.
+ *   Two launches on `stream` (the bitmap in a row pass, the flags from the bitmap); compares, wave ballots and ORs only, no
+ *   atomics: the result depends on the inputs alone.  Nothing synchronises.
+ * dsen2_recompose_rows_nodata is dsen2_recompose_rows with the bitmap and a slot map dev_slot_of_patch (int32 [y_tiles*x_tiles]) in
+ *   front of a COMPACT patch buffer dev_patches [slots,C,P,P]: an output pixel whose bit is 0 becomes 0.0f in all C channels and no
+ *   patch is read for it; any other pixel reads patch dev_slot_of_patch[k] where dsen2_recompose_rows reads patch k.  A slot outside
+ *   [0, slots) is treated as no-data (0 is written, nothing is read): no map can make the kernel read outside dev_patches.  slots
+ *   may be 0: every pixel of the rows becomes 0 and dev_patches may be NULL.
+ * DSEN2_ERR_INVALID with nothing launched: the geometry dsen2_recompose_rows refuses (inner <= 0, H < inner, W < inner, a row range
+ *   outside 0 <= row0 <= row1 <= H), C10 outside 1..16, C < 1, slots < 0, a NULL pointer. */
+int dsen2_tile_nodata_geometry(int H, int W, int P, int border, int *x_tiles, int *y_tiles, size_t *bitmap_words);
+int dsen2_tile_nodata(const float *dev_img10, int H, int W, int C10, int P, int border, unsigned char *dev_patch_empty,
+                      unsigned int *dev_valid_bits, void *stream);
+int dsen2_recompose_rows_nodata(const float *dev_patches, int slots, int C, int P, int border, const int *dev_slot_of_patch,
+                                const unsigned int *dev_valid_bits, float *dev_img, int H, int W, float scale, int row0, int row1,
+                                void *stream);
+
 /* dsen2_down_pixel_aggr  <->  downPixelAggr                       utils/patches.py:353-371
  *   dev_img: one HWC image [H,W,C] of uint16 or float32 samples; writes the HWC image [H/scale, W/scale, C] as float32
  *   (out_f64 = 0) or float64 (1).  scipy.ndimage.gaussian_filter(band, 1/scale) + skimage block_reduce(np.mean), operation by
