@@ -388,22 +388,31 @@ class S2Model(object):
     TRAINABLE = ('fp32', 'bf16x3')
     MIXED_PRECISIONS = {None: 0, 'bf16': 1}     # dsen2_model_set_train_precision
 
-    def compile(self, optimizer='nadam', loss='mean_absolute_error', metrics=None, mixed_precision=None):
+    def compile(self, optimizer='nadam', loss='mean_absolute_error', metrics=None, mixed_precision=None, *, loss_param=None,
+                mask_nodata=False):
         """keras Model.compile for the reference's recipe: optimizer 'nadam' or a training.Nadam, loss
         'mean_absolute_error' (MSE is always reported as the metric).  The optimizer state starts fresh.
+        loss: 'mean_absolute_error' / 'mae' (the default, the reference's), 'mean_squared_error' / 'mse', 'huber' or 'charbonnier'
+        (losses.py has the table).  loss_param (keyword only): Huber's delta / Charbonnier's epsilon as a float32 > 0, required
+        for those two — errors live in the reflectance / 2000 domain, where keras's delta = 1 would just be MSE / 2 — and refused
+        for the others.  mask_nodata=True (keyword only): a pixel whose target is exactly 0 in every band carries no ground truth
+        (the fill of a swath edge): it adds nothing to the loss, the metric or any gradient; the denominator stays the number of
+        all elements.  Every training path follows these — train_on_batch (shards too), train_on_device_batch, fit,
+        fit_corpus, data_parallel, emulate_world, augment — and so do evaluate, the validation passes and therefore
+        logs['loss'] / ['val_loss'], ReduceLROnPlateau and ModelCheckpoint; 'mean_squared_error' stays the (masked) MSE.  Note
+        that ReduceLROnPlateau's absolute min_delta=1e-6 is large beside an MSE in the normalised domain: lower it with loss='mse'.
         mixed_precision='bf16' (fp32 models only): the training step — fit, train_on_batch, gradients_device — runs its
         convolutions on bf16 operands with fp32 accumulation, the arithmetic of a precision='bf16' model; the weights, the
         optimizer state, the checkpoint, predict, evaluate and fit's validation pass stay fp32.  None: the model's own
         arithmetic."""
-        from . import training
+        from . import training, losses
         if self.precision not in self.TRAINABLE:
             raise ValueError('training needs an fp32 or a bf16x3 model (this one is %r)' % self.precision)
         if mixed_precision not in self.MIXED_PRECISIONS:
             raise ValueError("mixed_precision must be None or 'bf16', got %r" % (mixed_precision,))
         if mixed_precision is not None and self.precision != 'fp32':
             raise ValueError('mixed_precision=%r is an option of an fp32 model (this one is %r)' % (mixed_precision, self.precision))
-        if loss not in ('mean_absolute_error', 'mae'):
-            raise ValueError("loss must be 'mean_absolute_error', got %r" % (loss,))
+        setting = losses.parse(loss, loss_param, mask_nodata)
         if isinstance(optimizer, str):
             if optimizer.lower() != 'nadam':
                 raise ValueError("optimizer must be 'nadam' or a dsen2_amd.training.Nadam, got %r" % optimizer)
@@ -413,6 +422,9 @@ class S2Model(object):
         if self.precision == 'fp32':
             with torch.cuda.device(self.device):
                 _lib.call('dsen2_model_set_train_precision', self._handle, self.MIXED_PRECISIONS[mixed_precision])
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_model_set_loss', self._handle, setting[0], setting[1], setting[2])
+        self.loss_setting = setting
         self.mixed_precision = mixed_precision
         self.optimizer = optimizer
         self.optimizer.reset()
@@ -661,15 +673,20 @@ class S2Model(object):
         pred = self.predict(x, batch_size=batch_size, verbose=verbose)
         if pred.shape != y.shape:
             raise ValueError('target of shape %r where %r is expected' % (y.shape, pred.shape))
-        e = pred.astype(np.float64) - y.astype(np.float64)
-        return [float(np.mean(np.abs(e))), float(np.mean(e * e))]
+        from . import losses
+        return losses.host_loss(pred, y, self._loss_setting())
+
+    def _loss_setting(self):
+        """(kind, param, mask_mode) of the last compile(); the MAE, unmasked, for a model that was never compiled."""
+        from . import losses
+        return getattr(self, 'loss_setting', losses.DEFAULT)
 
     def _evaluate_shards(self, x, y, batch_size, world, mine=None):
         """[loss, mean_squared_error] over all samples as a data-parallel group of `world` ranks forms it: shard r =
         dist.shard_range(n, r, world) of the samples is predicted on its own and gives float64 (sum |e|, sum e^2, elements) on the
         host, as evaluate() forms them; the triples are added in rank order.  mine = None: every shard here, one after the other;
         mine = r: shard r alone, the triples all-gathered.  The same number on every rank."""
-        from . import dist
+        from . import dist, losses
         y = np.asarray(y, dtype=np.float32)
         n = y.shape[0]
         triples = np.zeros((world, 3), np.float64)
@@ -677,8 +694,7 @@ class S2Model(object):
             if mine in (None, r):
                 first, cnt = dist.shard_range(n, r, world)
                 pred = self.predict([a[first:first + cnt] for a in x], batch_size=batch_size)
-                e = pred.astype(np.float64) - y[first:first + cnt].astype(np.float64)
-                triples[r] = (np.sum(np.abs(e)), np.sum(e * e), e.size)
+                triples[r] = losses.host_sums(pred, y[first:first + cnt], self._loss_setting())
         if mine is not None:
             triples = dist.all_gather_rows(torch.from_numpy(triples[mine]).to(self.device)).cpu().numpy()
         sa = sq = cnt = 0.0
@@ -734,6 +750,33 @@ class S2Model(object):
                       _stream_ptr(self.device))
         return out
 
+    def loss_sums_device(self, pred, target, out):
+        """abs_sq_error_sums_device for the compiled loss: out[0 .. 1] = (sum rho, sum d^2) over the unmasked elements of an NCHW
+        [n, c, h, w] pair (dsen2_loss_sums; its third number, the unmasked count, stays in the scratch).  With the default
+        setting this IS abs_sq_error_sums_device."""
+        kind, param, mask = self._loss_setting()
+        if (kind, mask) == (0, 0):
+            return self.abs_sq_error_sums_device(pred, target, out)
+        for t in (pred, target):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or t.dim() != 4 or \
+                    tuple(t.shape) != tuple(pred.shape):
+                raise ValueError('pred and target must be contiguous float32 %s NCHW tensors of one shape' % (self.device,))
+        if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError('out must be a contiguous float64 %s tensor of two values' % (self.device,))
+        need = ctypes.c_size_t(0)
+        _lib.call('dsen2_loss_sums_workspace_bytes', ctypes.byref(need))
+        size = need.value + 24                                                  # the entry's scratch, then its three outputs
+        work = self._error_work
+        if work is None or work.numel() < size:
+            work = self._error_work = torch.empty(size, dtype=torch.uint8, device=self.device)
+        out3 = work[need.value:need.value + 24].view(torch.float64)
+        n, c, h, w = pred.shape
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_loss_sums', _ptr(pred), _ptr(target), n, c, h * w, kind, param, mask, _ptr(work), need.value, _ptr(out3),
+                      _stream_ptr(self.device))
+        out.copy_(out3[:2])
+        return out
+
     def _validation_rows(self, corpus, table, rows):
         """The device validation pass over the sample rows `table` of `corpus`: chunks of preferred_batch crops are cut
         (corpus.batch: op 0, _check_validation_crops refuses any other; divisor SCALE), go through forward_device — what predict runs — and chunk j's pair of error
@@ -742,7 +785,7 @@ class S2Model(object):
         chunk = self._validation_chunk(corpus)
         for j, i0 in enumerate(range(0, table.shape[0], chunk)):
             xs, y = corpus.batch(table[i0:i0 + chunk], divisor=training.SCALE)
-            self.abs_sq_error_sums_device(self.forward_device(xs), y, rows[j])
+            self.loss_sums_device(self.forward_device(xs), y, rows[j])
 
     def _validation_chunk(self, corpus):
         return max(1, int(self.preferred_batch(corpus.patch, corpus.patch)))

@@ -107,6 +107,12 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p]),
     'dsen2_abs_sq_error_sums_workspace_bytes': (c_int, [ctypes.POINTER(c_size_t)]),
     'dsen2_abs_sq_error_sums': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'dsen2_model_set_loss': (c_int, [c_void_p, c_int, ctypes.c_float, c_int]),
+    'dsen2_loss_grad': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, c_void_p, c_void_p,
+                                c_void_p]),
+    'dsen2_loss_sums_workspace_bytes': (c_int, [ctypes.POINTER(c_size_t)]),
+    'dsen2_loss_sums': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_float, c_int, c_void_p, c_size_t,
+                                c_void_p, c_void_p]),
     'dsen2_down_pixel_aggr': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int,
                                       c_void_p, c_int, c_void_p]),
     'dsen2_imresize_axis': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

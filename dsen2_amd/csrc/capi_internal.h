@@ -54,6 +54,9 @@ struct dsen2_model : dsen2::NetworkPlan {   // every layer's plan and place insi
   bool loaded;
   dsen2::TrainState* train;   // NULL until the first training call
   int train_precision = 0;    // dsen2_model_set_train_precision: 0 = the model's own arithmetic, 1 = bf16 operands (fp32 models)
+  // dsen2_model_set_loss: what dsen2_model_gradients minimises (dsen2_internal.h, "losses"); the default is the MAE, unmasked
+  int loss_kind = 0, loss_mask = 0;
+  float loss_param = 0.f;
   // precision 2 with residual blocks: the packed planes (hi + lo, 16 significant bits) do not hold the fp32 weights, so the
   // keras-flat vector dsen2_model_load_weights was given is kept until a training state takes it over as its master copy
   std::vector<float> host_flat;
@@ -64,6 +67,16 @@ struct dsen2_model : dsen2::NetworkPlan {   // every layer's plan and place insi
 };
 
 namespace dsen2 {
+
+// the (kind, param, mask mode) triple of dsen2_model_set_loss, dsen2_loss_grad and dsen2_loss_sums
+inline bool loss_reads_param(int kind) { return kind == kLossHuber || kind == kLossCharbonnier; }
+inline int check_loss(const char* who, int kind, float param, int mask_mode) {
+  if (kind < 0 || kind >= kLossKinds) return fail(DSEN2_ERR_INVALID, "%s: loss kind %d unknown (0 MAE, 1 MSE, 2 Huber, 3 Charbonnier)", who, kind);
+  if (mask_mode < 0 || mask_mode >= kMaskModes) return fail(DSEN2_ERR_INVALID, "%s: mask mode %d unknown (0 none, 1 no-data)", who, mask_mode);
+  if (loss_reads_param(kind) && !(param > 0.f && param <= 3.402823466e38f))
+    return fail(DSEN2_ERR_INVALID, "%s: loss kind %d needs a finite parameter > 0, got %g", who, kind, (double)param);
+  return DSEN2_OK;
+}
 
 inline int check_shape(const dsen2_model* m, int n, int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0) return fail(DSEN2_ERR_INVALID, "bad shape n=%d h=%d w=%d", n, h, w);

@@ -357,8 +357,9 @@ TrainWs carve(const StepFormat& f, int n, int h, int w, char* base) {
   return r;
 }
 
-// dsen2_model_gradients (arguments checked, training state present) in the step format f; see the file comment
-int gradients(const StepFormat& f, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out, float* grad,
+// dsen2_model_gradients (arguments checked, training state present) in the step format f; see the file comment.  owner: the
+// handle the caller holds (f.plan is its companion under mixed precision), whose dsen2_model_set_loss settings the loss follows
+int gradients(const StepFormat& f, const dsen2_model* owner, const float* x10, const float* x20, const float* x60, const float* target, float* dev_out, float* grad,
               float* loss2, int n, int h, int w, void* ws, hipStream_t s) {
   const dsen2_model* m = f.plan;
   TrainWs W = carve(f, n, h, w, reinterpret_cast<char*>(ws));
@@ -392,7 +393,8 @@ int gradients(const StepFormat& f, const float* x10, const float* x20, const flo
   if (int rc = forward_launches(m, x10, x20, x60, dev_out, n, h, w, B, W.keep_step, true, s, nullptr)) return rc;
 
   // ---- loss, output layer (fp32 kernels) ----
-  HIP_TRY(launch_mae_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, s));
+  HIP_TRY(launch_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, owner->loss_kind, owner->loss_param,
+                           owner->loss_mask, s));
   HIP_TRY(wgrad32(W.xd, F, W.gpad, 16, m->layers.back(), 1.f));
   HIP_TRY(hipMemsetAsync(W.g, 0, fbytes, s));
   HIP_TRY(dgrad(W.gpad, m->layers.size() - 1, W.g, W.g, nullptr, 1.f, kEpiResidual));
@@ -480,7 +482,7 @@ int dsen2_model_gradients(dsen2_model* m, const float* x10, const float* x20, co
     const size_t need = carve(step_format(m), n, h, w, nullptr).bytes;
     if (ws_bytes < need) return fail(DSEN2_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
     if (int rc = ensure_train_state(m)) return rc;
-    return gradients(step_format(m), x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
+    return gradients(step_format(m), m, x10, x20, x60, target, dev_out, grad, loss2, n, h, w, ws, (hipStream_t)stream_);
   });
 }
 
@@ -530,6 +532,32 @@ int dsen2_model_set_train_precision(dsen2_model* m, int precision) {
     }
     m->train_precision = precision;
     return had_state ? ensure_train_state(m) : DSEN2_OK;
+  });
+}
+
+int dsen2_model_set_loss(dsen2_model* m, int kind, float param, int mask_mode) {
+  return guarded([&]() -> int {
+    if (int rc = check_train_model(m)) return rc;
+    if (int rc = check_loss("model_set_loss", kind, param, mask_mode)) return rc;
+    m->loss_kind = kind;
+    m->loss_param = loss_reads_param(kind) ? param : 0.f;
+    m->loss_mask = mask_mode;
+    return DSEN2_OK;
+  });
+}
+
+int dsen2_loss_grad(const float* dev_out, const float* dev_target, int n, int c, int h, int w, int kind, float param, int mask_mode,
+                    float* dev_g_nhwc16, float* dev_loss2, void* stream) {
+  return guarded([&]() -> int {
+    if (!dev_out || !dev_target || !dev_g_nhwc16 || !dev_loss2) return fail(DSEN2_ERR_INVALID, "loss_grad: NULL argument");
+    if (n <= 0 || h <= 0 || w <= 0 || c < 1 || c > 15) return fail(DSEN2_ERR_INVALID, "loss_grad: bad shape n=%d c=%d h=%d w=%d (c in 1..15)", n, c, h, w);
+    if ((size_t)n * h * w * 16 >= ((size_t)1 << 31)) return fail(DSEN2_ERR_INVALID, "loss_grad: %d x %d x %d pixels exceed one launch", n, h, w);
+    if (int rc = check_loss("loss_grad", kind, param, mask_mode)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t doubles = mae_loss_partial_doubles((size_t)n * h * w);
+    return launch_once_with_temp("loss_grad", nullptr, doubles * sizeof(double), s, [&](char* dev) {
+      return launch_loss_grad(dev_out, dev_target, dev_g_nhwc16, reinterpret_cast<double*>(dev), dev_loss2, n, c, h, w, kind, param, mask_mode, s);
+    });
   });
 }
 

@@ -3,6 +3,7 @@
 // repack, and the count-weighted sum of sharded gradients with Nadam in one pass.  Every reduction runs in a fixed order (no
 // float atomics): the same inputs give the same bits on every run.
 #include "dsen2_internal.h"
+#include "loss_terms.h"
 
 namespace dsen2 {
 
@@ -75,6 +76,51 @@ __global__ __launch_bounds__(kLossThreads) void mae_loss_final_kernel(const doub
     loss2[0] = (float)(tot[0] / count);
     loss2[1] = (float)(tot[1] / count);
   }
+}
+
+// mae_loss_grad_kernel for every other (kind, mask) pair: e = out - y in float32, d = (double)e, dL/dout = (float)(rho'(d) *
+// (double)inv_count) as NHWC16 (loss_terms.h), partial[block] = (sum rho(d), sum d^2).  MASK: a pixel whose target is 0 (or -0) in all c bands
+// adds nothing to either sum and gets a zero gradient in every band; the thread owns all bands of its pixel, so the test costs
+// no second pass.  The default pair keeps mae_loss_grad_kernel and its instruction sequence.
+template <int KIND, bool MASK>
+__global__ __launch_bounds__(kLossThreads) void loss_grad_kernel(const float* __restrict__ out, const float* __restrict__ y,
+                                                               float* __restrict__ gpad, double* __restrict__ partial, size_t pixels,
+                                                               int hw, int c, float inv_count, float param) {
+  __shared__ double s[2 * kLossThreads];
+  const double p = (double)param, inv = (double)inv_count;
+  double sa = 0.0, sq = 0.0;
+  for (size_t pix = (size_t)blockIdx.x * kLossThreads + threadIdx.x; pix < pixels; pix += (size_t)gridDim.x * kLossThreads) {
+    const size_t img = pix / hw, q = pix % hw;
+    float ev[16];
+    bool valid = !MASK;
+#pragma unroll
+    for (int ch = 0; ch < 16; ++ch) {
+      ev[ch] = 0.f;
+      if (ch < c) {
+        const size_t idx = (img * c + ch) * hw + q;
+        const float yv = y[idx];
+        ev[ch] = out[idx] - yv;
+        if (MASK) valid |= yv != 0.f;          // -0.0 compares equal to 0: no data; NaN and negative values are data
+      }
+    }
+    float gv[16];
+#pragma unroll
+    for (int ch = 0; ch < 16; ++ch) {
+      gv[ch] = 0.f;
+      if (ch < c && valid) {
+        const double d = (double)ev[ch];
+        double rho, slope;
+        loss_terms<KIND>(d, p, rho, slope);
+        gv[ch] = (float)__dmul_rn(slope, inv);
+        sa = __dadd_rn(sa, rho);
+        sq = __dadd_rn(sq, __dmul_rn(d, d));
+      }
+    }
+    f32x4* dst = reinterpret_cast<f32x4*>(gpad + pix * 16);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dst[k] = f32x4{gv[4 * k], gv[4 * k + 1], gv[4 * k + 2], gv[4 * k + 3]};
+  }
+  block_sum2(s, sa, sq, partial + 2 * (size_t)blockIdx.x);
 }
 
 // v = m > 0 ? v : 0, in place (the ReLU gradient through a saved ReLU output m)
@@ -313,6 +359,38 @@ hipError_t launch_mae_loss_grad(const float* out, const float* y, float* gpad, d
   const double count = (double)pixels * c;
   hipLaunchKernelGGL(mae_loss_grad_kernel, dim3(blocks), dim3(kLossThreads), 0, stream, out, y, gpad, partial, pixels, h * w, c,
                      (float)(1.0 / count));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mae_loss_final_kernel, dim3(1), dim3(kLossThreads), 0, stream, partial, blocks, count, loss2);
+  return hipGetLastError();
+}
+
+namespace {
+template <int KIND>
+void launch_loss_grad_kind(bool mask, int blocks, hipStream_t stream, const float* out, const float* y, float* gpad, double* partial,
+                           size_t pixels, int hw, int c, float inv, float param) {
+  if (mask)
+    hipLaunchKernelGGL((loss_grad_kernel<KIND, true>), dim3(blocks), dim3(kLossThreads), 0, stream, out, y, gpad, partial, pixels, hw, c, inv, param);
+  else
+    hipLaunchKernelGGL((loss_grad_kernel<KIND, false>), dim3(blocks), dim3(kLossThreads), 0, stream, out, y, gpad, partial, pixels, hw, c, inv, param);
+}
+}  // namespace
+
+hipError_t launch_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h, int w,
+                            int kind, float param, int mask, hipStream_t stream) {
+  if (kind == kLossMae && mask == kMaskNone) return launch_mae_loss_grad(out, y, gpad, partial, loss2, n, c, h, w, stream);
+  if (c < 1 || c > 16 || kind < 0 || kind >= kLossKinds || mask < 0 || mask >= kMaskModes) return hipErrorInvalidValue;
+  const size_t pixels = (size_t)n * h * w;
+  const int blocks = (int)(mae_loss_partial_doubles(pixels) / 2);
+  const double count = (double)pixels * c;
+  const float inv = (float)(1.0 / count);
+  const bool mk = mask == kMaskNoData;
+  switch (kind) {
+    case kLossMae: launch_loss_grad_kind<kLossMae>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
+    case kLossMse: launch_loss_grad_kind<kLossMse>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
+    case kLossHuber: launch_loss_grad_kind<kLossHuber>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
+    default: launch_loss_grad_kind<kLossCharbonnier>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(mae_loss_final_kernel, dim3(1), dim3(kLossThreads), 0, stream, partial, blocks, count, loss2);

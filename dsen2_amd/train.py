@@ -53,6 +53,15 @@ validates from the table of validation crops on the GPU and builds no host array
 its valid area; a tile left with fewer than 1 valid origin in 64 is refused.  Under --data_parallel every rank builds the same
 masks from its own copy of the corpus and the same --seed.
 
+--loss {mae,mse,huber,charbonnier} [--loss_param X] [--mask_nodata] (not in the reference; without them the output, the log and
+the checkpoint are the bytes they always were) choose what is minimised (S2Model.compile(loss=, loss_param=, mask_nodata=);
+losses.py has the table): --loss_param is Huber's delta / Charbonnier's epsilon in the reflectance / 2000 domain, required for
+those two and refused otherwise; --mask_nodata keeps every pixel whose target is 0 in all bands — the fill of a swath edge or a
+tile corner, which prediction blanks by itself — out of the loss, the validation loss and every gradient (the denominator stays
+the number of all elements).  The epoch log's loss and valid columns, ReduceLROnPlateau and the checkpoint follow the chosen loss;
+min_delta stays 1e-6, which is large beside an MSE in this domain.  They work with --path and --tiles, every precision flag,
+--data_parallel and --emulate_world; a line at start-up names the loss.
+
     python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] --path P
 is that script's predict branch (--self_ensemble, not in the reference: predict(ensemble=True), the mean over the 8 flips and
 rotations of every patch; --augment is refused here): for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
@@ -114,11 +123,24 @@ def parse_args(argv=None):
                    help='With --holdout: also keep K cells of the origin grid around every validation crop free (default 0).')
     p.add_argument('--val_on_device', action='store_true',
                    help='With --tiles: validate from the table of validation crops on the GPU; no host arrays are built.')
+    p.add_argument('--loss', choices=('mae', 'mse', 'huber', 'charbonnier'), default=None,
+                   help='Training: the loss to minimise (default mae, the mean absolute error of the reference).')
+    p.add_argument('--loss_param', type=float, default=None, metavar='X',
+                   help='With --loss huber / charbonnier (required there): delta / epsilon, in the reflectance / 2000 domain.')
+    p.add_argument('--mask_nodata', action='store_true',
+                   help='Training: a pixel whose target is 0 in every band carries no ground truth: it adds nothing to the loss, '
+                        'the validation loss or any gradient.')
     p.add_argument('--self_ensemble', action='store_true',
                    help='With --predict: average the predictions for the 8 flips and rotations of every patch (~8x the network time).')
     args = p.parse_args(argv)
     if args.augment and args.predict_file:
         p.error('--augment is an option of training: it cannot be combined with --predict')
+    if args.predict_file and (args.loss is not None or args.loss_param is not None or args.mask_nodata):
+        p.error('--loss, --loss_param and --mask_nodata are options of training: they cannot be combined with --predict')
+    if args.loss in ('huber', 'charbonnier') and not (args.loss_param is not None and 0 < args.loss_param < float('inf')):
+        p.error('--loss %s needs --loss_param X with a finite X > 0' % args.loss)
+    if args.loss_param is not None and args.loss not in ('huber', 'charbonnier'):
+        p.error('--loss_param is an option of --loss huber and --loss charbonnier')
     if args.self_ensemble and not args.predict_file:
         p.error('--self_ensemble is an option of --predict')
     if args.tiles is None and (args.steps_per_epoch is not None or args.val_crops is not None):
@@ -266,7 +288,11 @@ def run(args, rank, world):
                                                          seed=args.seed if args.seed is not None else 1))
         say('Model number is {}'.format(model_nr))
     model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
-                  loss='mean_absolute_error', mixed_precision=args.mixed_precision)
+                  loss=args.loss or 'mean_absolute_error', mixed_precision=args.mixed_precision, loss_param=args.loss_param,
+                  mask_nodata=args.mask_nodata)
+    if args.loss is not None or args.mask_nodata:                # (without the new flags: the output as it always was)
+        from . import losses
+        say('Loss: {}.'.format(losses.describe(model.loss_setting)))
 
     corpus = None
     if args.tiles is not None:

@@ -345,6 +345,48 @@ int dsen2_conv3x3_wgrad_geometry(int kind, int n, int h, int w, int ca, int cg, 
                                  size_t *workspace_floats);
 int dsen2_join3_f32(const void *dev_hx, const void *dev_lo16, float *dev_out_nhwc, int n, int h, int w, int c, void *stream);
 
+/* ---- losses and the no-data mask (csrc/loss_terms.h, train_ops.hip, error_sums.hip) -----------
+ * What dsen2_model_gradients minimises is state on the handle, like the train precision.  kind: 0 MAE (the default), 1 MSE,
+ * 2 Huber(delta = param), 3 Charbonnier(epsilon = param).  mask_mode: 0 none (the default); 1 no-data: a pixel (sample, y, x)
+ * whose TARGET is exactly 0 in every one of the cout bands carries no ground truth — the rule of "no-data in, no-data out"
+ * (csrc/nodata.hip) applied to the target: -0.0 counts as 0, NaN and negative values are data.  A masked pixel adds 0 to both
+ * sums of dev_loss2 and has dL/dout = 0 in every band.
+ * The denominator is N = n*cout*h*w in EVERY mask mode, never the number of valid elements: a batch's loss and gradient keep the
+ * weight of its sample count, so dsen2_nadam_step_shards' count-weighted mean, the ranks of a data-parallel group and epoch sums
+ * formed without a host wait stay exact, and every valid pixel of a run weighs the same however many of its neighbours are blank.
+ * Arithmetic: e = out - target in float32 (as the MAE always did), d = (double)e; rho' in double, every operation rounded on its
+ * own (no FMA; double sqrt and divide are correctly rounded); dL/dout = (float)(rho'(d) * (double)inv), inv = (float)(1.0 / N).
+ * delta and epsilon are the (double) of the float32 `param`.  sign(0) = 0.
+ *     kind         rho                                   rho'
+ *     MAE          |d|                                   sign(d)                 (dL/dout = +-inv: the bits of every earlier release)
+ *     MSE          d*d                                   2*d
+ *     Huber        |d| <= delta: 0.5*(d*d)               d
+ *                  otherwise:    delta*(|d| - 0.5*delta) delta*sign(d)
+ *     Charbonnier  s = sqrt(d*d + eps*eps)               d / s
+ * dev_loss2 = { (float)(sum rho / N), (float)(sum d*d / N) }, both sums over the unmasked elements in one fixed-order tree; for
+ * kind 1 the two are the same bits.
+ * dsen2_model_set_loss: sets (kind, param, mask_mode) of a trainable handle.  It does not drop the training state (no workspace
+ *   size changes) and does not change dsen2_model_gradients' signature; with (0, anything, 0) every bit of a step is what it was
+ *   before this entry existed.  param is read by kinds 2 and 3 alone.  DSEN2_ERR_INVALID, nothing changed: an unknown kind or
+ *   mask mode, a param that is not finite or not > 0 for kinds 2 and 3, a precision-1 handle ("training needs an fp32 model or a
+ *   bf16x3 one").
+ * dsen2_loss_grad: the step's loss kernel alone (kernel-level tests): dev_out, dev_target NCHW [n,c,h,w] float32, c in 1..15;
+ *   dev_g_nhwc16 [n*h*w][16] receives dL/dout with lanes >= c zero, dev_loss2 the pair above.  Allocates its scratch and
+ *   synchronises.
+ * dsen2_loss_sums: the validation pass's sums for a loss kind and mask mode, next to dsen2_abs_sq_error_sums (same grid rule,
+ *   element order, trees and finish kernel): dev_out3 = { sum rho(d), sum d*d, number of unmasked elements } as float64 over the
+ *   n*c*hw elements of an NCHW [n, c, hw] pair, d = (double)p - (double)t; masked elements add nothing.  The mask re-reads the c
+ *   target values of the element's pixel (they sit in L2); there is no mask buffer.  With kind 0 and mask 0 the first two
+ *   outputs are dsen2_abs_sq_error_sums' bits.  dev_work: dsen2_loss_sums_workspace_bytes() bytes of device scratch.  Refusals as
+ *   there (NULL, n*c*hw outside 1..2^31 - 1: DSEN2_ERR_INVALID; a short workspace: DSEN2_ERR_WORKSPACE) and dsen2_model_set_loss's
+ *   for (kind, param, mask_mode). */
+int dsen2_model_set_loss(dsen2_model *m, int kind, float param, int mask_mode);
+int dsen2_loss_grad(const float *dev_out, const float *dev_target, int n, int c, int h, int w, int kind, float param,
+                    int mask_mode, float *dev_g_nhwc16, float *dev_loss2, void *stream);
+int dsen2_loss_sums_workspace_bytes(size_t *bytes);
+int dsen2_loss_sums(const float *dev_pred, const float *dev_target, int n, int c, long long hw, int kind, float param,
+                    int mask_mode, void *dev_work, size_t work_bytes, double *dev_out3, void *stream);
+
 /* ---- tiling / up-sampling / recomposition (utils/patches.py) --------------------------------
  * dsen2_upsample_mirror_bilinear  <->  interp_patches            utils/patches.py:11-16
  *   planes x [h,w] -> planes x [oh,ow]; half-pixel-centre bilinear with mirror boundary (skimage

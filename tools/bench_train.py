@@ -2,7 +2,7 @@
 """Fine-tuning speed: one JSON line per configuration.
 
     python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N] [--precision fp32|bf16x3] [--mixed_precision bf16]
-                                [--shards K [K ...]]
+                                [--shards K [K ...]] [--loss mae|mse|huber|charbonnier] [--loss_param X] [--mask_nodata]
 
   step_ms            one training step on device-resident data: dsen2_model_gradients + dsen2_nadam_step + the device repack
   train_on_batch_ms  S2Model.train_on_batch from host arrays (adds the H2D copies and the loss read-back)
@@ -20,6 +20,8 @@ the step goes layer by layer).  The weight-gradient kernel timed is the one-plan
 --shards K ...: beside the plain step, shards_step_ms[K] = the same global batch as K shards on device-resident data (K x
 dsen2_model_gradients at batch / K, one dsen2_nadam_step_shards, the repack: what train_on_batch(shards=K) and one rank-local
 batch of a K-rank data-parallel run cost in kernel efficiency), and train_on_batch_shards_ms[K] from host arrays.
+--loss / --loss_param / --mask_nodata: compile()'s loss, loss_param and mask_nodata (default: the MAE, unmasked; the JSON line
+then is what it always was).  With --mask_nodata the target gets a blank corner (a quarter of every patch zero in all bands).
 DSen2 runs at batch 128, VDSen2 at batch 8, both on 32 x 32 patches (training/supres_train.py's batch sizes).
 """
 import argparse
@@ -52,16 +54,19 @@ def timed(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters
 
 
-def run(name, iters, precision='fp32', mixed_precision=None, shards=()):
+def run(name, iters, precision='fp32', mixed_precision=None, shards=(), loss=None, loss_param=None, mask_nodata=False):
     c = CONFIGS[name]
     d, F, n, h, w = c['d'], c['F'], c['batch'], 32, 32
     dev = torch.device('cuda', 0)
     m = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev, precision=precision)
     m.set_weights_flat(weights.random_he_uniform(10, 6, d, F, seed=1, bias_scale=0.05))
-    m.compile(training.Nadam(lr=1e-4), mixed_precision=mixed_precision)
+    m.compile(training.Nadam(lr=1e-4), loss=loss or 'mean_absolute_error', mixed_precision=mixed_precision, loss_param=loss_param,
+              mask_nodata=mask_nodata)
     rng = np.random.default_rng(0)
     xs = [rng.uniform(0, 0.5, (n, k, h, w)).astype(np.float32) for k in (4, 6)]
     y = rng.uniform(0, 0.5, (n, 6, h, w)).astype(np.float32)
+    if mask_nodata:
+        y[:, :, :h // 2, :w // 2] = 0.0
     xs_d = [torch.from_numpy(a).to(dev) for a in xs]
     y_d = torch.from_numpy(y).to(dev)
     st = m._train_state()
@@ -126,6 +131,8 @@ def run(name, iters, precision='fp32', mixed_precision=None, shards=()):
                patches_per_s=round(n / step_ms * 1e3, 1), wgrad_call_ms=round(wg_ms, 4),
                wgrad_tflops_lower_bound=round(flop / wg_ms / 1e9, 2), wgrad_fraction_of_peak_lower_bound=round(flop / wg_ms / 1e9 / peak, 4))
     res.update(extra)
+    if loss is not None or mask_nodata:
+        res.update(loss=loss or 'mae', loss_param=loss_param, mask_nodata=bool(mask_nodata))
     print(json.dumps(res), flush=True)
 
 
@@ -136,11 +143,14 @@ def main():
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3'])
     ap.add_argument('--mixed_precision', default=None, choices=['bf16'])
     ap.add_argument('--shards', type=int, nargs='+', default=[], help='also time the step as K shards of the same global batch')
+    ap.add_argument('--loss', default=None, choices=['mae', 'mse', 'huber', 'charbonnier'])
+    ap.add_argument('--loss_param', type=float, default=None)
+    ap.add_argument('--mask_nodata', action='store_true')
     args = ap.parse_args()
     if args.mixed_precision and args.precision != 'fp32':
         ap.error('--mixed_precision is an option of --precision fp32')
     for name in (['dsen2', 'vdsen2'] if args.config == 'both' else [args.config]):
-        run(name, args.iters, args.precision, args.mixed_precision, args.shards)
+        run(name, args.iters, args.precision, args.mixed_precision, args.shards, args.loss, args.loss_param, args.mask_nodata)
 
 
 if __name__ == '__main__':
