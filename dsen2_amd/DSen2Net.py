@@ -681,6 +681,17 @@ class S2Model(object):
         from . import losses
         return getattr(self, 'loss_setting', losses.DEFAULT)
 
+    def _means_of_triples(self, triples, mine):
+        """[sum rho / elements, sum d^2 / elements] of the ranks' float64 (sum rho, sum d^2, elements) rows, added in rank order.
+        mine = r: this process holds row r alone and the rows are all-gathered first; None: it holds them all."""
+        if mine is not None:
+            from . import dist
+            triples = dist.all_gather_rows(torch.from_numpy(triples[mine]).to(self.device)).cpu().numpy()
+        sa = sq = cnt = 0.0
+        for t in triples:
+            sa, sq, cnt = sa + t[0], sq + t[1], cnt + t[2]
+        return [float(sa / cnt), float(sq / cnt)]
+
     def _evaluate_shards(self, x, y, batch_size, world, mine=None):
         """[loss, mean_squared_error] over all samples as a data-parallel group of `world` ranks forms it: shard r =
         dist.shard_range(n, r, world) of the samples is predicted on its own and gives float64 (sum |e|, sum e^2, elements) on the
@@ -695,12 +706,7 @@ class S2Model(object):
                 first, cnt = dist.shard_range(n, r, world)
                 pred = self.predict([a[first:first + cnt] for a in x], batch_size=batch_size)
                 triples[r] = losses.host_sums(pred, y[first:first + cnt], self._loss_setting())
-        if mine is not None:
-            triples = dist.all_gather_rows(torch.from_numpy(triples[mine]).to(self.device)).cpu().numpy()
-        sa = sq = cnt = 0.0
-        for t in triples:
-            sa, sq, cnt = sa + t[0], sq + t[1], cnt + t[2]
-        return [float(sa / cnt), float(sq / cnt)]
+        return self._means_of_triples(triples, mine)
 
     def _data_parallel_plan(self, data_parallel, emulate_world):
         """None: the plain fit.  Else (world, mine): the sharded steps of a group of `world` ranks, as rank `mine` of the process
@@ -731,51 +737,47 @@ class S2Model(object):
         self.set_weights_flat(payload[:-2])
         return int(payload[-2:].view(np.uint64)[0])
 
+    def _sums_device(self, pred, target, out, setting=None):
+        """The body of the two methods below.  setting None: dsen2_abs_sq_error_sums over the flat pair, which never forms a
+        count; else dsen2_loss_sums for (kind, param, mask) over an NCHW pair, its three numbers parked behind its scratch."""
+        for t in (pred, target):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != tuple(pred.shape) \
+                    or (setting is not None and t.dim() != 4):
+                raise ValueError('pred and target must be contiguous float32 %s %stensors of one shape'
+                                 % (self.device, 'NCHW ' if setting is not None else ''))
+        if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError('out must be a contiguous float64 %s tensor of two values' % (self.device,))
+        need = ctypes.c_size_t(0)
+        _lib.call('dsen2_abs_sq_error_sums_workspace_bytes' if setting is None else 'dsen2_loss_sums_workspace_bytes', ctypes.byref(need))
+        size = need.value + (0 if setting is None else 24)
+        work = self._error_work
+        if work is None or work.numel() < size:
+            work = self._error_work = torch.empty(size, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            if setting is None:
+                _lib.call('dsen2_abs_sq_error_sums', _ptr(pred), _ptr(target), pred.numel(), _ptr(work), work.numel(), _ptr(out),
+                          _stream_ptr(self.device))
+                return out
+            out3 = work[need.value:need.value + 24].view(torch.float64)
+            n, c, h, w = pred.shape
+            kind, param, mask = setting
+            _lib.call('dsen2_loss_sums', _ptr(pred), _ptr(target), n, c, h * w, kind, param, mask, _ptr(work), need.value, _ptr(out3),
+                      _stream_ptr(self.device))
+        out.copy_(out3[:2])
+        return out
+
     def abs_sq_error_sums_device(self, pred, target, out):
         """out[0 .. 1] = (sum |pred - target|, sum (pred - target)^2) in float64, formed on the device in an order that the number
         of elements alone fixes (dsen2_abs_sq_error_sums).  pred, target: contiguous float32 device tensors of one shape; out: a
         contiguous float64 device tensor of two values.  Nothing is copied to the host and nothing synchronises."""
-        for t in (pred, target):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != tuple(pred.shape):
-                raise ValueError('pred and target must be contiguous float32 %s tensors of one shape' % (self.device,))
-        if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError('out must be a contiguous float64 %s tensor of two values' % (self.device,))
-        need = ctypes.c_size_t(0)
-        _lib.call('dsen2_abs_sq_error_sums_workspace_bytes', ctypes.byref(need))
-        work = self._error_work
-        if work is None or work.numel() < need.value:
-            work = self._error_work = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.call('dsen2_abs_sq_error_sums', _ptr(pred), _ptr(target), pred.numel(), _ptr(work), work.numel(), _ptr(out),
-                      _stream_ptr(self.device))
-        return out
+        return self._sums_device(pred, target, out)
 
     def loss_sums_device(self, pred, target, out):
         """abs_sq_error_sums_device for the compiled loss: out[0 .. 1] = (sum rho, sum d^2) over the unmasked elements of an NCHW
         [n, c, h, w] pair (dsen2_loss_sums; its third number, the unmasked count, stays in the scratch).  With the default
         setting this IS abs_sq_error_sums_device."""
         kind, param, mask = self._loss_setting()
-        if (kind, mask) == (0, 0):
-            return self.abs_sq_error_sums_device(pred, target, out)
-        for t in (pred, target):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or t.dim() != 4 or \
-                    tuple(t.shape) != tuple(pred.shape):
-                raise ValueError('pred and target must be contiguous float32 %s NCHW tensors of one shape' % (self.device,))
-        if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError('out must be a contiguous float64 %s tensor of two values' % (self.device,))
-        need = ctypes.c_size_t(0)
-        _lib.call('dsen2_loss_sums_workspace_bytes', ctypes.byref(need))
-        size = need.value + 24                                                  # the entry's scratch, then its three outputs
-        work = self._error_work
-        if work is None or work.numel() < size:
-            work = self._error_work = torch.empty(size, dtype=torch.uint8, device=self.device)
-        out3 = work[need.value:need.value + 24].view(torch.float64)
-        n, c, h, w = pred.shape
-        with torch.cuda.device(self.device):
-            _lib.call('dsen2_loss_sums', _ptr(pred), _ptr(target), n, c, h * w, kind, param, mask, _ptr(work), need.value, _ptr(out3),
-                      _stream_ptr(self.device))
-        out.copy_(out3[:2])
-        return out
+        return self._sums_device(pred, target, out, None if (kind, mask) == (0, 0) else (kind, param, mask))
 
     def _validation_rows(self, corpus, table, rows):
         """The device validation pass over the sample rows `table` of `corpus`: chunks of preferred_batch crops are cut
@@ -820,12 +822,7 @@ class S2Model(object):
                     for row in rows.cpu().numpy():
                         sa, sq = sa + row[0], sq + row[1]
                     triples[r] = (sa, sq, float(cnt * elements))
-        if mine is not None:
-            triples = dist.all_gather_rows(torch.from_numpy(triples[mine]).to(self.device)).cpu().numpy()
-        sa = sq = cnt = 0.0
-        for t in triples:
-            sa, sq, cnt = sa + t[0], sq + t[1], cnt + t[2]
-        return [float(sa / cnt), float(sq / cnt)]
+        return self._means_of_triples(triples, mine)
 
     def _end_epoch(self, epoch, epochs, sums, count, validation_data, batch_size, plan, callbacks, history, verbose, val=None):
         """The end of an epoch of fit and of fit_corpus alike: the epoch's losses from `sums` (the float64 sums of samples x batch

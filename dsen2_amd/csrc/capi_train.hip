@@ -351,7 +351,7 @@ TrainWs carve(const StepFormat& f, int n, int h, int w, char* base) {
   }
   r.wg = take(wg);
   r.wg_floats = wg;
-  r.partial = reinterpret_cast<double*>(take(2 * mae_loss_partial_doubles(pix)));
+  r.partial = reinterpret_cast<double*>(take(2 * loss_partial_doubles(pix)));
   r.loss2 = take(2);
   r.bytes = off * sizeof(float);
   return r;
@@ -554,7 +554,7 @@ int dsen2_loss_grad(const float* dev_out, const float* dev_target, int n, int c,
     if ((size_t)n * h * w * 16 >= ((size_t)1 << 31)) return fail(DSEN2_ERR_INVALID, "loss_grad: %d x %d x %d pixels exceed one launch", n, h, w);
     if (int rc = check_loss("loss_grad", kind, param, mask_mode)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t doubles = mae_loss_partial_doubles((size_t)n * h * w);
+    const size_t doubles = loss_partial_doubles((size_t)n * h * w);
     return launch_once_with_temp("loss_grad", nullptr, doubles * sizeof(double), s, [&](char* dev) {
       return launch_loss_grad(dev_out, dev_target, dev_g_nhwc16, reinterpret_cast<double*>(dev), dev_loss2, n, c, h, w, kind, param, mask_mode, s);
     });

@@ -241,21 +241,19 @@ hipError_t launch_conv3x3_wgrad16(const void* a_planes, const void* g_planes, in
 // every product is the one bf16 MFMA a*g in fp32, db = scale * sum of the bf16 values of g.  Same workspace, same reduction.
 hipError_t launch_conv3x3_wgrad16_bf16(const void* a, const void* g, int n, int h, int w, int feat, float scale, float* dw, float* db,
                                        float* ws, size_t ws_floats, hipStream_t stream);
-// keras mean_absolute_error over NCHW out / y ([n][c][h][w], c <= 16): loss2 = (mean |e|, mean e^2), gpad = dL/dout =
-// sign(e) / (n*c*h*w) as NHWC16 (channels >= c zero).  partial: mae_loss_partial_doubles(n*h*w) doubles of scratch.
-size_t mae_loss_partial_doubles(size_t pixels);
-hipError_t launch_mae_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h,
-                                int w, hipStream_t stream);
 // ---- losses (include/dsen2_hip.h, "losses and the no-data mask") ----
 // The training step's loss of kind `kind` with parameter `param` (Huber's delta, Charbonnier's epsilon; read by those two alone)
-// under mask mode `mask`.  e = out - y in float32, d = (double)e; loss2 = ((float)(sum rho(d) / N), (float)(sum d^2 / N)), gpad =
-// (float)(rho'(d) * (double)inv) with inv = (float)(1.0 / N), N = n*c*h*w in EVERY mask mode: a batch's loss keeps the weight
+// under mask mode `mask`, over NCHW out / y ([n][c][h][w], c <= 16); gpad = dL/dout as NHWC16 (channels >= c zero); partial:
+// loss_partial_doubles(n*h*w) doubles of scratch.  e = out - y in float32, d = (double)e; loss2 = ((float)(sum rho(d) / N),
+// (float)(sum d^2 / N)), gpad = (float)(rho'(d) * (double)inv) with inv = (float)(1.0 / N), N = n*c*h*w in EVERY mask mode: a batch's loss keeps the weight
 // of its sample count (dsen2_nadam_step_shards, weighted_loss, the ranks of a data-parallel group and fit_corpus's epoch sums stay
 // exact) and every valid pixel of a run weighs the same, however many of its neighbours are blank.  rho' in double, every
 // operation rounded on its own.  kMaskNoData: a pixel whose target is 0 (-0 included; NaN and negatives are data) in all c bands
-// adds nothing to either sum and has gpad = 0 in every band.  (kLossMae, kMaskNone) IS launch_mae_loss_grad, same launches.
+// adds nothing to either sum and has gpad = 0 in every band.  (kLossMae, kMaskNone), keras mean_absolute_error with gpad =
+// sign(e) / N, is an instance of the one kernel template like the other seven pairs (loss_terms.h, with_loss).
 enum { kLossMae = 0, kLossMse = 1, kLossHuber = 2, kLossCharbonnier = 3, kLossKinds = 4 };
 enum { kMaskNone = 0, kMaskNoData = 1, kMaskModes = 2 };
+size_t loss_partial_doubles(size_t pixels);
 hipError_t launch_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h, int w,
                             int kind, float param, int mask, hipStream_t stream);
 // v = m > 0 ? v : 0 (count % 4 == 0, 16-byte aligned)

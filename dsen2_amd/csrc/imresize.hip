@@ -28,17 +28,16 @@
 
 #pragma clang fp contract(off)
 
+#include "fixed_sum.h"       // kQThreads, kQMaxBands, kQMaxBlocks, sum_work_bytes and the finish kernel
 #include "resample.h"        // as_double, resample_one, kResizeMaxTaps: shared with quality_metrics.hip
 
 namespace dsen2 {
 
-constexpr int kResizeThreads = 256;
-constexpr int kErrMaxBands = 64;
-constexpr int kErrMaxBlocks = 4096;              // partial pairs per band: the workspace is kErrMaxBlocks * C * 2 doubles
-
-// the block's per-thread pairs -> one pair per band in partials[block][c][2]; blockDim.x = npix * C, band of a thread = tid % C
+// the block's per-thread pairs -> one pair per band in partials[block][c][2]; blockDim.x = npix * C, band of a thread = tid % C.
+// Not fixed_sum.h's block_tree: this tree runs over the block's npix pixels with a stride of C between them, and npix is
+// floor(256 / C), seldom a power of two, so its top level is ragged.
 __device__ __forceinline__ void block_band_sums(double sq, double sb, int C, double* __restrict__ partials) {
-  __shared__ double s_sq[kResizeThreads], s_sb[kResizeThreads];
+  __shared__ double s_sq[kQThreads], s_sb[kQThreads];
   const int tid = threadIdx.x, npix = blockDim.x / C, pix = tid / C;
   s_sq[tid] = sq;
   s_sb[tid] = sb;
@@ -62,7 +61,7 @@ __device__ __forceinline__ void block_band_sums(double sq, double sb, int C, dou
 // FUSED = false: out[a][o][b] is written.  FUSED = true: nothing is written but the block's partial error sums against gt, which has
 // the output's shape; blockDim.x is then a multiple of C and so is every step of j (M * B is one too: B is a multiple of C).
 template <typename T, typename G, bool FUSED>
-__global__ __launch_bounds__(kResizeThreads) void imresize_axis_kernel(const T* __restrict__ in, int A, int N, int B, int M,
+__global__ __launch_bounds__(kQThreads) void imresize_axis_kernel(const T* __restrict__ in, int A, int N, int B, int M,
                                                                        const double* __restrict__ w, const int* __restrict__ idx, int P,
                                                                        double* __restrict__ out, const G* __restrict__ gt, int C,
                                                                        double* __restrict__ partials) {
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(kResizeThreads) void imresize_axis_kernel(const T* 
 
 // x, gt: n = pixels * C elements, HWC.  blockDim.x and the grid's step are multiples of C.
 template <typename X, typename G>
-__global__ __launch_bounds__(kResizeThreads) void band_errors_kernel(const X* __restrict__ x, const G* __restrict__ gt, size_t n, int C,
+__global__ __launch_bounds__(kQThreads) void band_errors_kernel(const X* __restrict__ x, const G* __restrict__ gt, size_t n, int C,
                                                                      double* __restrict__ partials) {
   const size_t step = (size_t)gridDim.x * blockDim.x;
   double sq = 0.0, sb = 0.0;
@@ -99,36 +98,6 @@ __global__ __launch_bounds__(kResizeThreads) void band_errors_kernel(const X* __
     sb = __dadd_rn(sb, g);
   }
   block_band_sums(sq, sb, C, partials);
-}
-
-// one block: out[c] = {sum of squared errors, sum of gt, pixel count} from partials[blocks][C][2]
-__global__ __launch_bounds__(kResizeThreads) void band_errors_finish_kernel(const double* __restrict__ partials, int blocks, int C,
-                                                                            double pixels, double* __restrict__ out) {
-  __shared__ double s[2][kResizeThreads];
-  const int tid = threadIdx.x;
-  for (int c = 0; c < C; ++c) {
-    double sq = 0.0, sb = 0.0;
-    for (int blk = tid; blk < blocks; blk += kResizeThreads) {
-      sq = __dadd_rn(sq, partials[((size_t)blk * C + c) * 2 + 0]);
-      sb = __dadd_rn(sb, partials[((size_t)blk * C + c) * 2 + 1]);
-    }
-    s[0][tid] = sq;
-    s[1][tid] = sb;
-    __syncthreads();
-    for (int half = kResizeThreads / 2; half > 0; half >>= 1) {
-      if (tid < half) {
-        s[0][tid] = __dadd_rn(s[0][tid], s[0][tid + half]);
-        s[1][tid] = __dadd_rn(s[1][tid], s[1][tid + half]);
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      out[c * 3 + 0] = s[0][0];
-      out[c * 3 + 1] = s[1][0];
-      out[c * 3 + 2] = pixels;
-    }
-    __syncthreads();
-  }
 }
 
 struct AxisShape {
@@ -153,12 +122,12 @@ static int axis_shape(const char* who, const void* in, int dtype, int H, int W, 
 
 static int check_bands(const char* who, int C, int gt_dtype, const void* gt, const void* work, size_t work_bytes, const void* out) {
   if (!gt || !work || !out) return fail(DSEN2_ERR_INVALID, "%s: bad argument", who);
-  if (C < 1 || C > kErrMaxBands) return fail(DSEN2_ERR_INVALID, "%s: %d bands outside 1..%d", who, C, kErrMaxBands);
+  if (C < 1 || C > kQMaxBands) return fail(DSEN2_ERR_INVALID, "%s: %d bands outside 1..%d", who, C, kQMaxBands);
   if (gt_dtype != DSEN2_DTYPE_F32 && gt_dtype != DSEN2_DTYPE_F64)
     return fail(DSEN2_ERR_INVALID, "%s: dtype %d is not supported for the ground truth (float32 or float64)", who, gt_dtype);
-  if (work_bytes < (size_t)kErrMaxBlocks * C * 2 * sizeof(double))
+  if (work_bytes < sum_work_bytes(C))
     return fail(DSEN2_ERR_WORKSPACE, "%s: workspace of %zu bytes, dsen2_band_errors_workspace_bytes asks for %zu", who, work_bytes,
-                (size_t)kErrMaxBlocks * C * 2 * sizeof(double));
+                sum_work_bytes(C));
   return DSEN2_OK;
 }
 
@@ -180,14 +149,14 @@ extern "C" int dsen2_imresize_axis(const void* dev_in, int dtype, int H, int W, 
     if (!dev_out) return fail(DSEN2_ERR_INVALID, "imresize_axis: bad argument");
     if (int rc = axis_shape("imresize_axis", dev_in, dtype, H, W, C, axis, out_len, dev_weights, dev_indices, taps, &s)) return rc;
     const unsigned MB = (unsigned)s.M * (unsigned)s.B;
-    const dim3 grid((MB + kResizeThreads - 1) / kResizeThreads, s.A < 65535 ? s.A : 65535);
+    const dim3 grid((MB + kQThreads - 1) / kQThreads, s.A < 65535 ? s.A : 65535);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == DSEN2_DTYPE_U16)
-      launch_axis<uint16_t, double, false>(dev_in, s, dev_weights, dev_indices, taps, dev_out, nullptr, C, nullptr, grid, kResizeThreads, st);
+      launch_axis<uint16_t, double, false>(dev_in, s, dev_weights, dev_indices, taps, dev_out, nullptr, C, nullptr, grid, kQThreads, st);
     else if (dtype == DSEN2_DTYPE_F32)
-      launch_axis<float, double, false>(dev_in, s, dev_weights, dev_indices, taps, dev_out, nullptr, C, nullptr, grid, kResizeThreads, st);
+      launch_axis<float, double, false>(dev_in, s, dev_weights, dev_indices, taps, dev_out, nullptr, C, nullptr, grid, kQThreads, st);
     else
-      launch_axis<double, double, false>(dev_in, s, dev_weights, dev_indices, taps, dev_out, nullptr, C, nullptr, grid, kResizeThreads, st);
+      launch_axis<double, double, false>(dev_in, s, dev_weights, dev_indices, taps, dev_out, nullptr, C, nullptr, grid, kQThreads, st);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(DSEN2_ERR_HIP, "imresize_axis launch: %s", hipGetErrorString(e));
     return DSEN2_OK;
@@ -195,8 +164,8 @@ extern "C" int dsen2_imresize_axis(const void* dev_in, int dtype, int H, int W, 
 }
 
 extern "C" int dsen2_band_errors_workspace_bytes(int C, size_t* bytes) {
-  if (!bytes || C < 1 || C > kErrMaxBands) return fail(DSEN2_ERR_INVALID, "band_errors_workspace_bytes: %d bands outside 1..%d", C, kErrMaxBands);
-  *bytes = (size_t)kErrMaxBlocks * C * 2 * sizeof(double);
+  if (!bytes || C < 1 || C > kQMaxBands) return fail(DSEN2_ERR_INVALID, "band_errors_workspace_bytes: %d bands outside 1..%d", C, kQMaxBands);
+  *bytes = sum_work_bytes(C);
   return DSEN2_OK;
 }
 
@@ -208,9 +177,9 @@ extern "C" int dsen2_band_errors(const void* dev_x, int x_dtype, const void* dev
     if (x_dtype != DSEN2_DTYPE_F32 && x_dtype != DSEN2_DTYPE_F64)
       return fail(DSEN2_ERR_INVALID, "band_errors: dtype %d is not supported (float32 or float64)", x_dtype);
     const size_t pixels = (size_t)H * W, n = pixels * C;
-    const int threads = kResizeThreads / C * C;
+    const int threads = kQThreads / C * C;
     const size_t want = (n + (size_t)threads * 8 - 1) / ((size_t)threads * 8);        // about eight elements per thread
-    const int blocks = (int)(want < 1 ? 1 : (want > kErrMaxBlocks ? kErrMaxBlocks : want));
+    const int blocks = (int)(want < 1 ? 1 : (want > kQMaxBlocks ? kQMaxBlocks : want));
     double* partials = static_cast<double*>(dev_work);
     hipStream_t st = (hipStream_t)stream;
     const bool x64 = x_dtype == DSEN2_DTYPE_F64, g64 = gt_dtype == DSEN2_DTYPE_F64;
@@ -223,10 +192,7 @@ extern "C" int dsen2_band_errors(const void* dev_x, int x_dtype, const void* dev
     else
       hipLaunchKernelGGL((band_errors_kernel<float, float>), dim3(blocks), dim3(threads), 0, st, (const float*)dev_x, (const float*)dev_gt, n, C, partials);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(band_errors_finish_kernel, dim3(1), dim3(kResizeThreads), 0, st, partials, blocks, C, (double)pixels, dev_out);
-      e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch_finish(partials, blocks, C, 3, (double)pixels, dev_out, st);
     if (e != hipSuccess) return fail(DSEN2_ERR_HIP, "band_errors launch: %s", hipGetErrorString(e));
     return DSEN2_OK;
   });
@@ -239,11 +205,11 @@ extern "C" int dsen2_imresize_band_errors(const void* dev_in, int dtype, int H, 
     AxisShape s;
     if (int rc = axis_shape("imresize_band_errors", dev_in, dtype, H, W, C, axis, out_len, dev_weights, dev_indices, taps, &s)) return rc;
     if (int rc = check_bands("imresize_band_errors", C, gt_dtype, dev_gt, dev_work, work_bytes, dev_out)) return rc;
-    const int threads = kResizeThreads / C * C;
+    const int threads = kQThreads / C * C;
     const unsigned MB = (unsigned)s.M * (unsigned)s.B;
     unsigned gx = (MB + threads - 1) / threads;
-    if (gx > (unsigned)kErrMaxBlocks) gx = kErrMaxBlocks;
-    unsigned gy = kErrMaxBlocks / gx;
+    if (gx > (unsigned)kQMaxBlocks) gx = kQMaxBlocks;
+    unsigned gy = kQMaxBlocks / gx;
     if (gy > (unsigned)s.A) gy = s.A;
     const dim3 grid(gx, gy);
     double* partials = static_cast<double*>(dev_work);
@@ -259,8 +225,7 @@ extern "C" int dsen2_imresize_band_errors(const void* dev_in, int dtype, int H, 
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
       const size_t pixels = axis == 0 ? (size_t)out_len * W : (size_t)H * out_len;
-      hipLaunchKernelGGL(band_errors_finish_kernel, dim3(1), dim3(kResizeThreads), 0, st, partials, (int)(gx * gy), C, (double)pixels, dev_out);
-      e = hipGetLastError();
+      e = launch_finish(partials, (int)(gx * gy), C, 3, (double)pixels, dev_out, st);
     }
     if (e != hipSuccess) return fail(DSEN2_ERR_HIP, "imresize_band_errors launch: %s", hipGetErrorString(e));
     return DSEN2_OK;

@@ -10,6 +10,8 @@
 //                 else:     p*(|d| - 0.5*p)             p*sign(d)
 //   Charbonnier   s = sqrt(d*d + p*p)                   d / s
 #pragma once
+#include <type_traits>
+
 #include "dsen2_internal.h"
 
 namespace dsen2 {
@@ -35,6 +37,23 @@ __device__ __forceinline__ void loss_terms(double d, double p, double& rho, doub
   } else {
     rho = sqrt(__dadd_rn(__dmul_rn(d, d), __dmul_rn(p, p)));
     slope = d / rho;
+  }
+}
+
+// f(kind, mask) with the two as compile-time constants (std::integral_constant / std::bool_constant; decltype(kind)::value
+// names a template argument): the one place that turns the pair of a checked call (check_loss, launch_loss_grad) into kernels
+template <class F>
+void with_loss(int kind, int mask, F&& f) {
+  using std::integral_constant;
+  switch (kind * kMaskModes + mask) {
+    case kLossMae * kMaskModes + kMaskNone: f(integral_constant<int, kLossMae>{}, std::false_type{}); break;
+    case kLossMae * kMaskModes + kMaskNoData: f(integral_constant<int, kLossMae>{}, std::true_type{}); break;
+    case kLossMse * kMaskModes + kMaskNone: f(integral_constant<int, kLossMse>{}, std::false_type{}); break;
+    case kLossMse * kMaskModes + kMaskNoData: f(integral_constant<int, kLossMse>{}, std::true_type{}); break;
+    case kLossHuber * kMaskModes + kMaskNone: f(integral_constant<int, kLossHuber>{}, std::false_type{}); break;
+    case kLossHuber * kMaskModes + kMaskNoData: f(integral_constant<int, kLossHuber>{}, std::true_type{}); break;
+    case kLossCharbonnier * kMaskModes + kMaskNone: f(integral_constant<int, kLossCharbonnier>{}, std::false_type{}); break;
+    default: f(integral_constant<int, kLossCharbonnier>{}, std::true_type{}); break;
   }
 }
 

@@ -1,15 +1,11 @@
-// What quality_metrics.hip (UIQ, SAM) and ssim.hip share: the two image loaders their kernels are templates over, the one-block
-// finish kernel of the fused sums, the workspace size, and the argument checks of their C-ABI entries.  Include it below
+// What quality_metrics.hip (UIQ, SAM) and ssim.hip share: the two image loaders their kernels are templates over and the
+// argument checks of their C-ABI entries (the sums' pieces are fixed_sum.h's).  Include it below
 // `#pragma clang fp contract(off)` and after capi_internal.h.
 #pragma once
+#include "fixed_sum.h"     // kQThreads, kQMaxBands, kQMaxBlocks, sum_work_bytes, the finish kernel
 #include "resample.h"
 
 namespace dsen2 {
-
-constexpr int kQThreads = 256;
-constexpr int kQWaves = kQThreads / 64;
-constexpr int kQMaxBands = 64;
-constexpr int kQMaxBlocks = 4096;                  // partial pairs per band: the workspace is kQMaxBlocks * C * 2 doubles
 
 template <typename T>
 struct DirectImage {        // x[r][col][band] of an HWC image
@@ -29,37 +25,6 @@ struct ResampledImage {     // the same element of the image that dsen2_imresize
     return resample_one<T>(mid + (size_t)r * N * B + band, w, idx, P, M, N, B, (unsigned)col);
   }
 };
-
-// one block: out[c][0 .. 1] = the sums over all blocks of partials[block][c][0 .. 1], in a fixed order
-static __global__ __launch_bounds__(kQThreads) void quality_finish_kernel(const double* __restrict__ partials, int blocks, int C,
-                                                                          double* __restrict__ out) {
-  __shared__ double s[2][kQThreads];
-  const int tid = threadIdx.x;
-  for (int c = 0; c < C; ++c) {
-    double a = 0.0, b = 0.0;
-    for (int blk = tid; blk < blocks; blk += kQThreads) {
-      a = __dadd_rn(a, partials[((size_t)blk * C + c) * 2 + 0]);
-      b = __dadd_rn(b, partials[((size_t)blk * C + c) * 2 + 1]);
-    }
-    s[0][tid] = a;
-    s[1][tid] = b;
-    __syncthreads();
-    for (int half = kQThreads / 2; half > 0; half >>= 1) {
-      if (tid < half) {
-        s[0][tid] = __dadd_rn(s[0][tid], s[0][tid + half]);
-        s[1][tid] = __dadd_rn(s[1][tid], s[1][tid + half]);
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      out[c * 2 + 0] = s[0][0];
-      out[c * 2 + 1] = s[1][0];
-    }
-    __syncthreads();
-  }
-}
-
-static size_t quality_work_bytes(int C) { return (size_t)kQMaxBlocks * C * 2 * sizeof(double); }
 
 static bool float_dtype(int d) { return d == DSEN2_DTYPE_F32 || d == DSEN2_DTYPE_F64; }
 
@@ -91,8 +56,8 @@ static int check_resampled(const char* who, const void* in, int dtype, int H, in
 
 static int check_work(const char* who, int C, const void* work, size_t work_bytes, const void* out) {
   if (!work || !out) return fail(DSEN2_ERR_INVALID, "%s: bad argument", who);
-  if (work_bytes < quality_work_bytes(C))
-    return fail(DSEN2_ERR_WORKSPACE, "%s: workspace of %zu bytes, dsen2_quality_workspace_bytes asks for %zu", who, work_bytes, quality_work_bytes(C));
+  if (work_bytes < sum_work_bytes(C))
+    return fail(DSEN2_ERR_WORKSPACE, "%s: workspace of %zu bytes, dsen2_quality_workspace_bytes asks for %zu", who, work_bytes, sum_work_bytes(C));
   return DSEN2_OK;
 }
 

@@ -46,7 +46,7 @@ template <class LX, class LY, bool MAP>
 __global__ __launch_bounds__(kQThreads) void uiq_kernel(LX x, LY y, int H, int W, int C, int block, int tiles_x, int tiles,
                                                         double* __restrict__ map, double* __restrict__ partials) {
   extern __shared__ double smem[];
-  __shared__ double s_wave[kQWaves], s_acc[kQMaxBands], s_cnt;
+  __shared__ double s_acc[kQMaxBands], s_cnt;
   const int RH = kUiqTileH + block - 1, RW = kUiqTileW + block - 1, plane = RH * kUiqTileW;
   double* const rx = smem;                  // [RH][RW]
   double* const ry = rx + RH * RW;          // [RH][RW]
@@ -115,11 +115,9 @@ __global__ __launch_bounds__(kQThreads) void uiq_kernel(LX x, LY y, int H, int W
         }
       }
       if constexpr (!MAP) {
-        for (int off = 32; off > 0; off >>= 1) qsum = __dadd_rn(qsum, __shfl_down(qsum, off));
-        if ((tid & 63) == 0) s_wave[tid >> 6] = qsum;
-        __syncthreads();
+        qsum = wave_then_block_sum(qsum);
         if (tid == 0) {
-          s_acc[band] = __dadd_rn(s_acc[band], __dadd_rn(__dadd_rn(s_wave[0], s_wave[1]), __dadd_rn(s_wave[2], s_wave[3])));
+          s_acc[band] = __dadd_rn(s_acc[band], qsum);
           if (band == 0) {
             const int th = OH - r0 < kUiqTileH ? OH - r0 : kUiqTileH, tw = OW - c0 < kUiqTileW ? OW - c0 : kUiqTileW;
             s_cnt = __dadd_rn(s_cnt, (double)(th * tw));
@@ -140,7 +138,6 @@ __global__ __launch_bounds__(kQThreads) void uiq_kernel(LX x, LY y, int H, int W
 // partials[block] = { sum of the angles in degrees, pixels with a non-zero spectrum in both images }
 template <class LX, class LY>
 __global__ __launch_bounds__(kQThreads) void sam_kernel(LX x, LY y, int H, int W, int C, double* __restrict__ partials) {
-  __shared__ double s_a[kQThreads], s_n[kQThreads];
   const unsigned pixels = (unsigned)H * (unsigned)W, step = gridDim.x * kQThreads;
   const int tid = threadIdx.x;
   double sa = 0.0, sn = 0.0;
@@ -164,19 +161,11 @@ __global__ __launch_bounds__(kQThreads) void sam_kernel(LX x, LY y, int H, int W
       sn = __dadd_rn(sn, 1.0);
     }
   }
-  s_a[tid] = sa;
-  s_n[tid] = sn;
-  __syncthreads();
-  for (int half = kQThreads / 2; half > 0; half >>= 1) {
-    if (tid < half) {
-      s_a[tid] = __dadd_rn(s_a[tid], s_a[tid + half]);
-      s_n[tid] = __dadd_rn(s_n[tid], s_n[tid + half]);
-    }
-    __syncthreads();
-  }
+  double v[2] = {sa, sn};
+  block_tree<2>(v);
   if (tid == 0) {
-    partials[(size_t)blockIdx.x * 2 + 0] = s_a[0];
-    partials[(size_t)blockIdx.x * 2 + 1] = s_n[0];
+    partials[(size_t)blockIdx.x * 2 + 0] = v[0];
+    partials[(size_t)blockIdx.x * 2 + 1] = v[1];
   }
 }
 
@@ -197,10 +186,7 @@ static hipError_t launch_uiq(const LX& x, const LY& y, const QualityCall& q) {
   hipLaunchKernelGGL((uiq_kernel<LX, LY, MAP>), dim3(grid), dim3(kQThreads), lds, q.stream, x, y, q.H, q.W, q.C, q.block, tiles_x, tiles,
                      q.map, q.partials);
   hipError_t e = hipGetLastError();
-  if (!MAP && e == hipSuccess) {
-    hipLaunchKernelGGL(quality_finish_kernel, dim3(1), dim3(kQThreads), 0, q.stream, q.partials, grid, q.C, q.out);
-    e = hipGetLastError();
-  }
+  if (!MAP && e == hipSuccess) e = launch_finish(q.partials, grid, q.C, 2, 0.0, q.out, q.stream);
   return e;
 }
 
@@ -211,10 +197,7 @@ static hipError_t launch_sam(const LX& x, const LY& y, const QualityCall& q) {
   const int grid = (int)(want > (size_t)kQMaxBlocks ? (size_t)kQMaxBlocks : want);
   hipLaunchKernelGGL((sam_kernel<LX, LY>), dim3(grid), dim3(kQThreads), 0, q.stream, x, y, q.H, q.W, q.C, q.partials);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(quality_finish_kernel, dim3(1), dim3(kQThreads), 0, q.stream, q.partials, grid, 1, q.out);
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess) e = launch_finish(q.partials, grid, 1, 2, 0.0, q.out, q.stream);
   return e;
 }
 
@@ -283,7 +266,7 @@ using namespace dsen2;
 
 extern "C" int dsen2_quality_workspace_bytes(int C, size_t* bytes) {
   if (!bytes || C < 1 || C > kQMaxBands) return fail(DSEN2_ERR_INVALID, "quality_workspace_bytes: %d bands outside 1..%d", C, kQMaxBands);
-  *bytes = quality_work_bytes(C);
+  *bytes = sum_work_bytes(C);
   return DSEN2_OK;
 }
 

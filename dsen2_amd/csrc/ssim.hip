@@ -19,7 +19,7 @@
 // its tile in turn.  Samples outside the image are staged as zeros and only reach windows that are neither stored nor summed.
 // Endings: MAP stores q to map[OH][OW][C] (float64); SUMS adds q up per band and never writes the map: per thread in index
 // order, a fixed shuffle tree per wave, the four waves in order, the block's tiles in order, one partial per (block, band), and the
-// one-block finish kernel over the blocks' partials (quality_common.h).  The grid is min(tiles, kQMaxBlocks): a function of the
+// one-block finish kernel over the blocks' partials (fixed_sum.h).  The grid is min(tiles, kQMaxBlocks): a function of the
 // shape alone, no float atomics, so the sums are the same bits on every run.
 //
 // FUSED BASELINE.  The kernel is a template over the loaders of x and y (quality_common.h).  With ResampledImage for x the halo
@@ -47,7 +47,7 @@ template <class LX, class LY, bool MAP>
 __global__ __launch_bounds__(kQThreads) void ssim_kernel(LX x, LY y, int H, int W, int C, int P, SsimWindow win, double c1, double c2,
                                                          int tiles_x, int tiles, double* __restrict__ map, double* __restrict__ partials) {
   extern __shared__ double smem[];
-  __shared__ double s_w[kSsimMaxWin], s_wave[kQWaves], s_acc[kQMaxBands], s_cnt;
+  __shared__ double s_w[kSsimMaxWin], s_acc[kQMaxBands], s_cnt;
   const int RH = kSsimTileH + P - 1, RW = kSsimTileW + P - 1, plane = RH * kSsimTileW;
   double* const rx = smem;                  // [RH][RW]
   double* const ry = rx + RH * RW;          // [RH][RW]
@@ -118,11 +118,9 @@ __global__ __launch_bounds__(kQThreads) void ssim_kernel(LX x, LY y, int H, int 
         }
       }
       if constexpr (!MAP) {
-        for (int off = 32; off > 0; off >>= 1) qsum = __dadd_rn(qsum, __shfl_down(qsum, off));
-        if ((tid & 63) == 0) s_wave[tid >> 6] = qsum;
-        __syncthreads();
+        qsum = wave_then_block_sum(qsum);
         if (tid == 0) {
-          s_acc[band] = __dadd_rn(s_acc[band], __dadd_rn(__dadd_rn(s_wave[0], s_wave[1]), __dadd_rn(s_wave[2], s_wave[3])));
+          s_acc[band] = __dadd_rn(s_acc[band], qsum);
           if (band == 0) {
             const int th = OH - r0 < kSsimTileH ? OH - r0 : kSsimTileH, tw = OW - c0 < kSsimTileW ? OW - c0 : kSsimTileW;
             s_cnt = __dadd_rn(s_cnt, (double)(th * tw));
@@ -159,10 +157,7 @@ static hipError_t launch_ssim(const LX& x, const LY& y, const SsimCall& q) {
   hipLaunchKernelGGL((ssim_kernel<LX, LY, MAP>), dim3(grid), dim3(kQThreads), lds, q.stream, x, y, q.H, q.W, q.C, q.P, q.win, q.c1, q.c2,
                      tiles_x, tiles, q.map, q.partials);
   hipError_t e = hipGetLastError();
-  if (!MAP && e == hipSuccess) {
-    hipLaunchKernelGGL(quality_finish_kernel, dim3(1), dim3(kQThreads), 0, q.stream, q.partials, grid, q.C, q.out);
-    e = hipGetLastError();
-  }
+  if (!MAP && e == hipSuccess) e = launch_finish(q.partials, grid, q.C, 2, 0.0, q.out, q.stream);
   return e;
 }
 

@@ -3,6 +3,7 @@
 // repack, and the count-weighted sum of sharded gradients with Nadam in one pass.  Every reduction runs in a fixed order (no
 // float atomics): the same inputs give the same bits on every run.
 #include "dsen2_internal.h"
+#include "fixed_sum.h"
 #include "loss_terms.h"
 
 namespace dsen2 {
@@ -11,85 +12,20 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kLossThreads = 256;
 constexpr int kLossMaxBlocks = 1024;
 
-// fixed-shape tree over one block's values (blockDim.x = kLossThreads)
-__device__ void block_sum2(double* s, double a, double b, double* out) {
-  const int tid = threadIdx.x;
-  s[tid] = a;
-  s[kLossThreads + tid] = b;
-  __syncthreads();
-  for (int k = kLossThreads / 2; k > 0; k >>= 1) {
-    if (tid < k) {
-      s[tid] += s[tid + k];
-      s[kLossThreads + tid] += s[kLossThreads + tid + k];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    out[0] = s[0];
-    out[1] = s[kLossThreads];
-  }
-}
-
-// e = out - y over NCHW [n][c][hw]; dL/dout = sign(e) * inv_count written as NHWC16 [n*hw][16] (channels >= c zero);
-// partial[block] = (sum |e|, sum e^2) of the block's pixels (grid-stride, fixed grid)
-__global__ __launch_bounds__(kLossThreads) void mae_loss_grad_kernel(const float* __restrict__ out, const float* __restrict__ y,
-                                                                   float* __restrict__ gpad, double* __restrict__ partial,
-                                                                   size_t pixels, int hw, int c, float inv_count) {
-  __shared__ double s[2 * kLossThreads];
-  double sa = 0.0, sq = 0.0;
-  for (size_t pix = (size_t)blockIdx.x * kLossThreads + threadIdx.x; pix < pixels; pix += (size_t)gridDim.x * kLossThreads) {
-    const size_t img = pix / hw, q = pix % hw;
-    float gv[16];
-#pragma unroll
-    for (int ch = 0; ch < 16; ++ch) {
-      gv[ch] = 0.f;
-      if (ch < c) {
-        const size_t idx = (img * c + ch) * hw + q;
-        const float e = out[idx] - y[idx];
-        gv[ch] = e > 0.f ? inv_count : (e < 0.f ? -inv_count : 0.f);     // TensorFlow's Abs gradient: sign(0) = 0
-        sa += (double)fabsf(e);
-        sq += (double)e * (double)e;
-      }
-    }
-    f32x4* dst = reinterpret_cast<f32x4*>(gpad + pix * 16);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dst[k] = f32x4{gv[4 * k], gv[4 * k + 1], gv[4 * k + 2], gv[4 * k + 3]};
-  }
-  block_sum2(s, sa, sq, partial + 2 * (size_t)blockIdx.x);
-}
-
-__global__ __launch_bounds__(kLossThreads) void mae_loss_final_kernel(const double* __restrict__ partial, int blocks, double count,
-                                                                    float* __restrict__ loss2) {
-  __shared__ double s[2 * kLossThreads];
-  double sa = 0.0, sq = 0.0;
-  for (int i = threadIdx.x; i < blocks; i += kLossThreads) {
-    sa += partial[2 * i];
-    sq += partial[2 * i + 1];
-  }
-  __shared__ double tot[2];
-  block_sum2(s, sa, sq, tot);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    loss2[0] = (float)(tot[0] / count);
-    loss2[1] = (float)(tot[1] / count);
-  }
-}
-
-// mae_loss_grad_kernel for every other (kind, mask) pair: e = out - y in float32, d = (double)e, dL/dout = (float)(rho'(d) *
-// (double)inv_count) as NHWC16 (loss_terms.h), partial[block] = (sum rho(d), sum d^2).  MASK: a pixel whose target is 0 (or -0) in all c bands
-// adds nothing to either sum and gets a zero gradient in every band; the thread owns all bands of its pixel, so the test costs
-// no second pass.  The default pair keeps mae_loss_grad_kernel and its instruction sequence.
+// The loss of kind KIND (loss_terms.h) over NCHW [n][c][hw]: e = out - y in float32, d = (double)e, dL/dout = (float)(rho'(d) *
+// (double)inv_count) written as NHWC16 [n*hw][16] (channels >= c zero), partial[block] = (sum rho(d), sum d^2) of the block's
+// pixels (grid-stride, fixed grid; fixed_sum.h's tree).  MASK: a pixel whose target is 0 (or -0) in all c bands adds nothing to
+// either sum and gets a zero gradient in every band; the thread owns all bands of its pixel, so the test costs no second pass.
+// The default pair is the <kLossMae, false> instance: sign(e) * inv_count, TensorFlow's Abs gradient with sign(0) = 0.
 template <int KIND, bool MASK>
-__global__ __launch_bounds__(kLossThreads) void loss_grad_kernel(const float* __restrict__ out, const float* __restrict__ y,
-                                                               float* __restrict__ gpad, double* __restrict__ partial, size_t pixels,
-                                                               int hw, int c, float inv_count, float param) {
-  __shared__ double s[2 * kLossThreads];
+__global__ __launch_bounds__(kQThreads) void loss_grad_kernel(const float* __restrict__ out, const float* __restrict__ y,
+                                                              float* __restrict__ gpad, double* __restrict__ partial, size_t pixels,
+                                                              int hw, int c, float inv_count, float param) {
   const double p = (double)param, inv = (double)inv_count;
   double sa = 0.0, sq = 0.0;
-  for (size_t pix = (size_t)blockIdx.x * kLossThreads + threadIdx.x; pix < pixels; pix += (size_t)gridDim.x * kLossThreads) {
+  for (size_t pix = (size_t)blockIdx.x * kQThreads + threadIdx.x; pix < pixels; pix += (size_t)gridDim.x * kQThreads) {
     const size_t img = pix / hw, q = pix % hw;
     float ev[16];
     bool valid = !MASK;
@@ -120,7 +56,24 @@ __global__ __launch_bounds__(kLossThreads) void loss_grad_kernel(const float* __
 #pragma unroll
     for (int k = 0; k < 4; ++k) dst[k] = f32x4{gv[4 * k], gv[4 * k + 1], gv[4 * k + 2], gv[4 * k + 3]};
   }
-  block_sum2(s, sa, sq, partial + 2 * (size_t)blockIdx.x);
+  double v[2] = {sa, sq};
+  block_tree<2>(v);
+  if (threadIdx.x == 0) {
+    partial[2 * (size_t)blockIdx.x + 0] = v[0];
+    partial[2 * (size_t)blockIdx.x + 1] = v[1];
+  }
+}
+
+// one block: loss2 = ((float)(sum rho / count), (float)(sum d^2 / count)) from the blocks' partial pairs, in a fixed order
+__global__ __launch_bounds__(kQThreads) void loss_final_kernel(const double* __restrict__ partial, int blocks, double count,
+                                                               float* __restrict__ loss2) {
+  double v[2];
+  strided_partials<2>(partial, blocks, 2, v);
+  block_tree<2>(v);
+  if (threadIdx.x == 0) {
+    loss2[0] = (float)(v[0] / count);
+    loss2[1] = (float)(v[1] / count);
+  }
 }
 
 // v = m > 0 ? v : 0, in place (the ReLU gradient through a saved ReLU output m)
@@ -344,56 +297,27 @@ constexpr size_t kShardsMaxBlocks = (size_t)1 << 30;
 
 }  // namespace
 
-size_t mae_loss_partial_doubles(size_t pixels) {
-  size_t b = (pixels + kLossThreads - 1) / kLossThreads;
+size_t loss_partial_doubles(size_t pixels) {
+  size_t b = (pixels + kQThreads - 1) / kQThreads;
   if (b > (size_t)kLossMaxBlocks) b = kLossMaxBlocks;
   if (b < 1) b = 1;
   return 2 * b;
 }
 
-hipError_t launch_mae_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h,
-                                int w, hipStream_t stream) {
-  if (c < 1 || c > 16) return hipErrorInvalidValue;
-  const size_t pixels = (size_t)n * h * w;
-  const int blocks = (int)(mae_loss_partial_doubles(pixels) / 2);
-  const double count = (double)pixels * c;
-  hipLaunchKernelGGL(mae_loss_grad_kernel, dim3(blocks), dim3(kLossThreads), 0, stream, out, y, gpad, partial, pixels, h * w, c,
-                     (float)(1.0 / count));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(mae_loss_final_kernel, dim3(1), dim3(kLossThreads), 0, stream, partial, blocks, count, loss2);
-  return hipGetLastError();
-}
-
-namespace {
-template <int KIND>
-void launch_loss_grad_kind(bool mask, int blocks, hipStream_t stream, const float* out, const float* y, float* gpad, double* partial,
-                           size_t pixels, int hw, int c, float inv, float param) {
-  if (mask)
-    hipLaunchKernelGGL((loss_grad_kernel<KIND, true>), dim3(blocks), dim3(kLossThreads), 0, stream, out, y, gpad, partial, pixels, hw, c, inv, param);
-  else
-    hipLaunchKernelGGL((loss_grad_kernel<KIND, false>), dim3(blocks), dim3(kLossThreads), 0, stream, out, y, gpad, partial, pixels, hw, c, inv, param);
-}
-}  // namespace
-
 hipError_t launch_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h, int w,
                             int kind, float param, int mask, hipStream_t stream) {
-  if (kind == kLossMae && mask == kMaskNone) return launch_mae_loss_grad(out, y, gpad, partial, loss2, n, c, h, w, stream);
   if (c < 1 || c > 16 || kind < 0 || kind >= kLossKinds || mask < 0 || mask >= kMaskModes) return hipErrorInvalidValue;
   const size_t pixels = (size_t)n * h * w;
-  const int blocks = (int)(mae_loss_partial_doubles(pixels) / 2);
+  const int blocks = (int)(loss_partial_doubles(pixels) / 2);
   const double count = (double)pixels * c;
   const float inv = (float)(1.0 / count);
-  const bool mk = mask == kMaskNoData;
-  switch (kind) {
-    case kLossMae: launch_loss_grad_kind<kLossMae>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
-    case kLossMse: launch_loss_grad_kind<kLossMse>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
-    case kLossHuber: launch_loss_grad_kind<kLossHuber>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
-    default: launch_loss_grad_kind<kLossCharbonnier>(mk, blocks, stream, out, y, gpad, partial, pixels, h * w, c, inv, param); break;
-  }
+  with_loss(kind, mask, [&](auto k, auto m) {
+    hipLaunchKernelGGL((loss_grad_kernel<decltype(k)::value, decltype(m)::value>), dim3(blocks), dim3(kQThreads), 0, stream, out, y, gpad,
+                       partial, pixels, h * w, c, inv, param);
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(mae_loss_final_kernel, dim3(1), dim3(kLossThreads), 0, stream, partial, blocks, count, loss2);
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(kQThreads), 0, stream, partial, blocks, count, loss2);
   return hipGetLastError();
 }
 

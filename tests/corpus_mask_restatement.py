@@ -3,6 +3,8 @@ dsen2_corpus_origin_mask from its definitions (include/dsen2_hip.h, "corpus orig
 corpus.CorpusSampler(masks=) with plain loops, and the summation order of dsen2_abs_sq_error_sums."""
 import numpy as np
 
+from fixed_sum_restatement import fixed_order_sum as _fixed_order_sum      # the entries' order of addition
+
 CROP = 16
 
 
@@ -85,37 +87,6 @@ def validation_table(extents, crops_per_tile, seed, stream, valid=None):
 
 
 # ---- dsen2_abs_sq_error_sums ---------------------------------------------------------------------------------------------------------
-THREADS, PER_THREAD, MAX_BLOCKS = 256, 8, 4096
-
-
-def _tree(s):
-    """[rows, 256] -> [rows]: the halving tree of a workgroup."""
-    s = s.copy()
-    half = THREADS // 2
-    while half > 0:
-        s[:, :half] = s[:, :half] + s[:, half:2 * half]
-        half //= 2
-    return s[:, 0]
-
-
-def _strided(values, lanes):
-    """Lane j adds values[j], values[j + lanes], ... in index order onto 0.0.  Padding with +0.0 changes no bit: every term is
-    non-negative, and x + 0.0 == x for x >= +0.0."""
-    pad = -values.size % lanes
-    v = np.concatenate([values, np.zeros(pad)]).reshape(-1, lanes)
-    acc = np.zeros(lanes)
-    for row in v:
-        acc = acc + row
-    return acc
-
-
-def _fixed_order_sum(terms):
-    n = terms.size
-    blocks = min(max(-(-n // (THREADS * PER_THREAD)), 1), MAX_BLOCKS)
-    partials = _tree(_strided(terms, blocks * THREADS).reshape(blocks, THREADS))
-    return float(_tree(_strided(partials, THREADS).reshape(1, THREADS))[0])
-
-
 def abs_sq_error_sums(pred, target):
     """(sum |p - t|, sum (p - t)^2) in the entry's order: float64 throughout, every operation rounded on its own."""
     d = np.asarray(pred, np.float32).astype(np.float64).ravel() - np.asarray(target, np.float32).astype(np.float64).ravel()

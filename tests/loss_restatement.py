@@ -4,6 +4,8 @@ numpy rounds every operation on its own and has no FMA, which is the arithmetic 
 product's own losses.py."""
 import numpy as np
 
+from fixed_sum_restatement import fixed_order_sum as _fixed_order_sum      # the entries' order of addition
+
 MAE, MSE, HUBER, CHARBONNIER = 0, 1, 2, 3
 KINDS = (MAE, MSE, HUBER, CHARBONNIER)
 NAMES = {MAE: 'mae', MSE: 'mse', HUBER: 'huber', CHARBONNIER: 'charbonnier'}
@@ -65,35 +67,6 @@ def loss_grad(out, y, kind, param=0.0, mask=0):
 
 
 # ---- dsen2_loss_sums: dsen2_abs_sq_error_sums' order ------------------------------------------------------------------------------
-THREADS, PER_THREAD, MAX_BLOCKS = 256, 8, 4096
-
-
-def _tree(s):
-    s = s.copy()
-    half = THREADS // 2
-    while half > 0:
-        s[:, :half] = s[:, :half] + s[:, half:2 * half]
-        half //= 2
-    return s[:, 0]
-
-
-def _strided(values, lanes):
-    """Lane j adds values[j], values[j + lanes], ... in index order onto 0.0.  A masked element is skipped on the device and is a
-    +0.0 term here, like the padding: every term is >= +0.0 and x + 0.0 == x for such x, so no bit changes."""
-    v = np.concatenate([values, np.zeros(-values.size % lanes)]).reshape(-1, lanes)
-    acc = np.zeros(lanes)
-    for row in v:
-        acc = acc + row
-    return acc
-
-
-def _fixed_order_sum(terms):
-    n = terms.size
-    blocks = min(max(-(-n // (THREADS * PER_THREAD)), 1), MAX_BLOCKS)
-    partials = _tree(_strided(terms, blocks * THREADS).reshape(blocks, THREADS))
-    return float(_tree(_strided(partials, THREADS).reshape(1, THREADS))[0])
-
-
 def loss_sums(pred, y, kind, param=0.0, mask=0):
     """[sum rho, sum d^2, unmasked elements] as float64: d = (double)p - (double)t over NCHW in element order."""
     pred, y = np.asarray(pred, np.float32), np.asarray(y, np.float32)

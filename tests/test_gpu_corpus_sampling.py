@@ -179,7 +179,7 @@ def test_tile_corpus_refuses_a_tile_that_is_nearly_all_blank(capsys):
 
 
 # ---- 2. the error sums -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('count', [1, 255, 4097, 2 * 6 * 32 * 32 * 3])
+@pytest.mark.parametrize('count', [1, 255, 4097, 2 * 6 * 32 * 32 * 3, 4096 * 2048 + 257])      # the last: above the grid's cap, a ninth pass
 def test_error_sums_equal_the_restated_order_bit_for_bit(count):
     rng = np.random.default_rng(count)
     p = (rng.random(count, dtype=np.float32) * 5).astype(np.float32)

@@ -35,6 +35,8 @@ NAME = {R.MAE: 'mae', R.MSE: 'mse', R.HUBER: 'huber', R.CHARBONNIER: 'charbonnie
 # (n, c, h, w): the smallest; ragged, less than one block; ragged; the widest cout; 269 120 pixels > 1024 blocks x 256 threads, so
 # the grid-stride loop of the step's kernel takes a second pass
 SHAPES = [(1, 1, 1, 1), (3, 6, 5, 7), (2, 2, 9, 21), (2, 15, 4, 4), (5, 6, 232, 232)]
+# dsen2_loss_sums alone: 8 392 609 elements > 4096 blocks x 2048, the cap of its grid, so every thread takes a ninth pass
+ABOVE_THE_SUMS_GRID_CAP = (1, 1, 2897, 2897)
 
 
 def _compile(m, kind, mask=0, scale=1.0, **kw):
@@ -126,7 +128,7 @@ def _sums_need():
 
 
 @pytest.mark.parametrize('kind', R.KINDS)
-@pytest.mark.parametrize('shape', SHAPES)
+@pytest.mark.parametrize('shape', SHAPES + [ABOVE_THE_SUMS_GRID_CAP])
 def test_loss_sums_equal_the_restatement_bit_for_bit(shape, kind):
     out, y = _pair(shape)
     n, c, h, w = shape

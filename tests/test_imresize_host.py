@@ -126,7 +126,7 @@ def test_tap_sums_are_not_contracted_in_the_isa(tmp_path):
     kernels = asm_contract._kernels(open(out).read())
     assert len([k for k in kernels if 'imresize_axis_kernel' in k]) == 9          # {uint16, float32, float64} x {store, fused x {float32, float64}}
     assert len([k for k in kernels if 'band_errors_kernel' in k]) == 4
-    assert len([k for k in kernels if 'band_errors_finish_kernel' in k]) == 1
+    assert len([k for k in kernels if 'fixed_sum_finish_kernel' in k]) == 1
     for name, body in kernels.items():
         assert not any(ln.startswith('v_fma_f64') or ln.startswith('v_fmac_f64') for ln in body), name
         assert not any('scratch_' in ln for ln in body), name
