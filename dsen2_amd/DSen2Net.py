@@ -389,7 +389,7 @@ class S2Model(object):
     MIXED_PRECISIONS = {None: 0, 'bf16': 1}     # dsen2_model_set_train_precision
 
     def compile(self, optimizer='nadam', loss='mean_absolute_error', metrics=None, mixed_precision=None, *, loss_param=None,
-                mask_nodata=False):
+                mask_nodata=False, ssim_weight=0.0, ssim_win=11, ssim_sigma=1.5, ssim_data_range=5.0):
         """keras Model.compile for the reference's recipe: optimizer 'nadam' or a training.Nadam, loss
         'mean_absolute_error' (MSE is always reported as the metric).  The optimizer state starts fresh.
         loss: 'mean_absolute_error' / 'mae' (the default, the reference's), 'mean_squared_error' / 'mse', 'huber' or 'charbonnier'
@@ -401,6 +401,13 @@ class S2Model(object):
         fit_corpus, data_parallel, emulate_world, augment — and so do evaluate, the validation passes and therefore
         logs['loss'] / ['val_loss'], ReduceLROnPlateau and ModelCheckpoint; 'mean_squared_error' stays the (masked) MSE.  Note
         that ReduceLROnPlateau's absolute min_delta=1e-6 is large beside an MSE in the normalised domain: lower it with loss='mse'.
+        ssim_weight > 0 (keyword only) adds Zhao et al. 2017's term  ssim_weight * mean over all windows of (1 - SSIM)  to the loss,
+        with its gradient on the GPU (include/dsen2_hip.h, "the SSIM loss term"): the window is metrics.ssim_window(ssim_win,
+        ssim_sigma), ssim_win odd in 3..11, and c1 = (0.01 L)^2, c2 = (0.03 L)^2 with L = ssim_data_range in the normalised domain
+        (5.0 = the metrics' 10000 / SCALE).  Under mask_nodata a window that holds a masked pixel adds nothing; the denominator
+        stays the number of all windows.  The same paths follow it; logs['loss'] and ['val_loss'] are then the total the
+        optimiser minimises, 'mean_squared_error' is unchanged.  Patches must be at least ssim_win on a side.  0 (the default):
+        every bit as without the term.
         mixed_precision='bf16' (fp32 models only): the training step — fit, train_on_batch, gradients_device — runs its
         convolutions on bf16 operands with fp32 accumulation, the arithmetic of a precision='bf16' model; the weights, the
         optimizer state, the checkpoint, predict, evaluate and fit's validation pass stay fp32.  None: the model's own
@@ -412,7 +419,7 @@ class S2Model(object):
             raise ValueError("mixed_precision must be None or 'bf16', got %r" % (mixed_precision,))
         if mixed_precision is not None and self.precision != 'fp32':
             raise ValueError('mixed_precision=%r is an option of an fp32 model (this one is %r)' % (mixed_precision, self.precision))
-        setting = losses.parse(loss, loss_param, mask_nodata)
+        setting = losses.parse_ssim(losses.parse(loss, loss_param, mask_nodata), ssim_weight, ssim_win, ssim_sigma, ssim_data_range)
         if isinstance(optimizer, str):
             if optimizer.lower() != 'nadam':
                 raise ValueError("optimizer must be 'nadam' or a dsen2_amd.training.Nadam, got %r" % optimizer)
@@ -424,6 +431,10 @@ class S2Model(object):
                 _lib.call('dsen2_model_set_train_precision', self._handle, self.MIXED_PRECISIONS[mixed_precision])
         with torch.cuda.device(self.device):
             _lib.call('dsen2_model_set_loss', self._handle, setting[0], setting[1], setting[2])
+            ssim = losses.ssim_part(setting) or (0.0, 11, 1.5, 5.0)
+            window, c1, c2 = losses.ssim_constants(ssim)
+            _lib.call('dsen2_model_set_loss_ssim', self._handle, ssim[0], (ctypes.c_double * window.size)(*window.tolist()),
+                      int(window.size), c1, c2)
         self.loss_setting = setting
         self.mixed_precision = mixed_precision
         self.optimizer = optimizer
@@ -677,7 +688,8 @@ class S2Model(object):
         return losses.host_loss(pred, y, self._loss_setting())
 
     def _loss_setting(self):
-        """(kind, param, mask_mode) of the last compile(); the MAE, unmasked, for a model that was never compiled."""
+        """The setting of the last compile() (losses.py: (kind, param, mask_mode), with the SSIM part behind it when its weight is
+        > 0); the MAE, unmasked, for a model that was never compiled."""
         from . import losses
         return getattr(self, 'loss_setting', losses.DEFAULT)
 
@@ -776,8 +788,32 @@ class S2Model(object):
         """abs_sq_error_sums_device for the compiled loss: out[0 .. 1] = (sum rho, sum d^2) over the unmasked elements of an NCHW
         [n, c, h, w] pair (dsen2_loss_sums; its third number, the unmasked count, stays in the scratch).  With the default
         setting this IS abs_sq_error_sums_device."""
-        kind, param, mask = self._loss_setting()
-        return self._sums_device(pred, target, out, None if (kind, mask) == (0, 0) else (kind, param, mask))
+        from . import losses
+        setting = self._loss_setting()
+        kind, param, mask = losses.pointwise(setting)
+        self._sums_device(pred, target, out, None if (kind, mask) == (0, 0) else (kind, param, mask))
+        if losses.ssim_part(setting):
+            # out[0] = sum rho + ssim_fold * sum (1 - q), as losses.host_sums forms it: a float64 product, then a float64 sum
+            s3 = self._ssim_sums_device(pred, target, setting)
+            out[0:1].add_(s3[0:1] * losses.ssim_fold(setting, tuple(pred.shape)))
+        return out
+
+    def _ssim_sums_device(self, pred, target, setting):
+        """{ sum (1 - q), Nw, unmasked windows } of the compiled SSIM term over an NCHW pair (dsen2_ssim_loss_sums), a float64
+        device tensor of three values behind the call's scratch; the next call overwrites it."""
+        from . import losses
+        window, c1, c2 = losses.ssim_constants(losses.ssim_part(setting))
+        need = ctypes.c_size_t(0)
+        _lib.call('dsen2_ssim_loss_sums_workspace_bytes', ctypes.byref(need))
+        work = getattr(self, '_ssim_work', None)
+        if work is None or work.numel() < need.value + 24 or work.device != self.device:
+            work = self._ssim_work = torch.empty(need.value + 24, dtype=torch.uint8, device=self.device)
+        out3 = work[need.value:need.value + 24].view(torch.float64)
+        n, c, h, w = pred.shape
+        with torch.cuda.device(self.device):
+            _lib.call('dsen2_ssim_loss_sums', _ptr(pred), _ptr(target), n, c, h, w, (ctypes.c_double * window.size)(*window.tolist()),
+                      int(window.size), c1, c2, setting[2], _ptr(work), need.value, _ptr(out3), _stream_ptr(self.device))
+        return out3
 
     def _validation_rows(self, corpus, table, rows):
         """The device validation pass over the sample rows `table` of `corpus`: chunks of preferred_batch crops are cut

@@ -113,6 +113,12 @@ SIGNATURES = {
     'dsen2_loss_sums_workspace_bytes': (c_int, [ctypes.POINTER(c_size_t)]),
     'dsen2_loss_sums': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, ctypes.c_float, c_int, c_void_p, c_size_t,
                                 c_void_p, c_void_p]),
+    'dsen2_model_set_loss_ssim': (c_int, [c_void_p, ctypes.c_float, ctypes.POINTER(c_double), c_int, c_double, c_double]),
+    'dsen2_ssim_loss_grad': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float, ctypes.POINTER(c_double), c_int,
+                                     c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    'dsen2_ssim_loss_sums_workspace_bytes': (c_int, [ctypes.POINTER(c_size_t)]),
+    'dsen2_ssim_loss_sums': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_double, c_double,
+                                     c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'dsen2_down_pixel_aggr': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int,
                                       c_void_p, c_int, c_void_p]),
     'dsen2_imresize_axis': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

@@ -57,6 +57,7 @@ struct dsen2_model : dsen2::NetworkPlan {   // every layer's plan and place insi
   // dsen2_model_set_loss: what dsen2_model_gradients minimises (dsen2_internal.h, "losses"); the default is the MAE, unmasked
   int loss_kind = 0, loss_mask = 0;
   float loss_param = 0.f;
+  dsen2::SsimLossTerm loss_ssim;      // dsen2_model_set_loss_ssim: weight 0 (the default) = no SSIM term, nothing of it is launched
   // precision 2 with residual blocks: the packed planes (hi + lo, 16 significant bits) do not hold the fp32 weights, so the
   // keras-flat vector dsen2_model_load_weights was given is kept until a training state takes it over as its master copy
   std::vector<float> host_flat;
@@ -75,6 +76,26 @@ inline int check_loss(const char* who, int kind, float param, int mask_mode) {
   if (mask_mode < 0 || mask_mode >= kMaskModes) return fail(DSEN2_ERR_INVALID, "%s: mask mode %d unknown (0 none, 1 no-data)", who, mask_mode);
   if (loss_reads_param(kind) && !(param > 0.f && param <= 3.402823466e38f))
     return fail(DSEN2_ERR_INVALID, "%s: loss kind %d needs a finite parameter > 0, got %g", who, kind, (double)param);
+  return DSEN2_OK;
+}
+
+// the SSIM term of dsen2_model_set_loss_ssim, dsen2_ssim_loss_grad and dsen2_ssim_loss_sums; fills *term, or changes nothing
+inline int check_ssim_loss_term(const char* who, float weight, const double* host_window, int win, double c1, double c2, SsimLossTerm* term) {
+  if (!(weight >= 0.f && weight <= 3.402823466e38f)) return fail(DSEN2_ERR_INVALID, "%s: the SSIM weight must be finite and >= 0, got %g", who, (double)weight);
+  if (win < kSsimLossMinWin || win > kSsimLossMaxWin || win % 2 == 0)
+    return fail(DSEN2_ERR_INVALID, "%s: window size %d is not odd or outside %d..%d", who, win, kSsimLossMinWin, kSsimLossMaxWin);
+  if (!host_window) return fail(DSEN2_ERR_INVALID, "%s: NULL window", who);
+  for (int i = 0; i < win; ++i)
+    if (!(host_window[i] - host_window[i] == 0.0)) return fail(DSEN2_ERR_INVALID, "%s: window entry %d is not finite", who, i);
+  if (!(c1 > 0.0 && c1 - c1 == 0.0) || !(c2 > 0.0 && c2 - c2 == 0.0))
+    return fail(DSEN2_ERR_INVALID, "%s: constants c1 = %g and c2 = %g must be finite and positive", who, c1, c2);
+  SsimLossTerm t;
+  t.weight = weight;
+  t.win = win;
+  for (int i = 0; i < win; ++i) t.w[i] = host_window[i];
+  t.c1 = c1;
+  t.c2 = c2;
+  *term = t;
   return DSEN2_OK;
 }
 

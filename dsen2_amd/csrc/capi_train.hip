@@ -301,7 +301,7 @@ struct TrainWs {
   size_t keep_step;                        // forward keeps them (planes 0: x_0 .. x_d, so x0f and xd lie inside; else l < d)
   char* du;
   void *s0, *s1, *gs0, *gs1, *zs0, *zs1;   // planes 1 / 2: the forward's stream, g as a stream, the zero stream
-  double* partial;
+  double *partial, *ssim_work;              // the loss kernel's partial pairs; the SSIM term's partials and sums
   size_t wg_floats;
   size_t bytes;
 };
@@ -353,6 +353,7 @@ TrainWs carve(const StepFormat& f, int n, int h, int w, char* base) {
   r.wg_floats = wg;
   r.partial = reinterpret_cast<double*>(take(2 * loss_partial_doubles(pix)));
   r.loss2 = take(2);
+  r.ssim_work = reinterpret_cast<double*>(take(2 * ssim_loss_work_doubles()));
   r.bytes = off * sizeof(float);
   return r;
 }
@@ -393,8 +394,9 @@ int gradients(const StepFormat& f, const dsen2_model* owner, const float* x10, c
   if (int rc = forward_launches(m, x10, x20, x60, dev_out, n, h, w, B, W.keep_step, true, s, nullptr)) return rc;
 
   // ---- loss, output layer (fp32 kernels) ----
+  const bool ssim = owner->loss_ssim.weight > 0.f;
   HIP_TRY(launch_loss_grad(dev_out, target, W.gpad, W.partial, loss2, n, m->cout, h, w, owner->loss_kind, owner->loss_param,
-                           owner->loss_mask, s));
+                           owner->loss_mask, s, ssim ? &owner->loss_ssim : nullptr, ssim ? W.ssim_work : nullptr));
   HIP_TRY(wgrad32(W.xd, F, W.gpad, 16, m->layers.back(), 1.f));
   HIP_TRY(hipMemsetAsync(W.g, 0, fbytes, s));
   HIP_TRY(dgrad(W.gpad, m->layers.size() - 1, W.g, W.g, nullptr, 1.f, kEpiResidual));
@@ -479,6 +481,9 @@ int dsen2_model_gradients(dsen2_model* m, const float* x10, const float* x20, co
     if ((m->c60 > 0) != (x60 != nullptr)) return fail(DSEN2_ERR_INVALID, "x60 must be given iff the model has a 60 m input");
     if (!m->loaded) return fail(DSEN2_ERR_NO_WEIGHTS, "no weights: dsen2_model_load_weights or dsen2_model_set_weights_device first");
     if (int rc = check_shape(m, n, h, w)) return rc;
+    if (m->loss_ssim.weight > 0.f && (h < m->loss_ssim.win || w < m->loss_ssim.win))
+      return fail(DSEN2_ERR_INVALID, "a patch of %d x %d is smaller than the %d x %d window of the SSIM term", h, w, m->loss_ssim.win,
+                  m->loss_ssim.win);
     const size_t need = carve(step_format(m), n, h, w, nullptr).bytes;
     if (ws_bytes < need) return fail(DSEN2_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
     if (int rc = ensure_train_state(m)) return rc;
@@ -543,6 +548,13 @@ int dsen2_model_set_loss(dsen2_model* m, int kind, float param, int mask_mode) {
     m->loss_param = loss_reads_param(kind) ? param : 0.f;
     m->loss_mask = mask_mode;
     return DSEN2_OK;
+  });
+}
+
+int dsen2_model_set_loss_ssim(dsen2_model* m, float weight, const double* host_window, int win, double c1, double c2) {
+  return guarded([&]() -> int {
+    if (int rc = check_train_model(m)) return rc;
+    return check_ssim_loss_term("model_set_loss_ssim", weight, host_window, win, c1, c2, &m->loss_ssim);
   });
 }
 

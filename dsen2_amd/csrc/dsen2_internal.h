@@ -254,8 +254,24 @@ hipError_t launch_conv3x3_wgrad16_bf16(const void* a, const void* g, int n, int 
 enum { kLossMae = 0, kLossMse = 1, kLossHuber = 2, kLossCharbonnier = 3, kLossKinds = 4 };
 enum { kMaskNone = 0, kMaskNoData = 1, kMaskModes = 2 };
 size_t loss_partial_doubles(size_t pixels);
+// The SSIM term of the loss (ssim_loss.hip): weight 0 = off.  w: the normalised separable window of `win` taps (odd, 3..11).
+constexpr int kSsimLossMinWin = 3, kSsimLossMaxWin = 11;
+struct SsimLossTerm {
+  float weight = 0.f;
+  int win = 0;
+  double w[kSsimLossMaxWin] = {};
+  double c1 = 0.0, c2 = 0.0;
+};
+// work: ssim_loss_work_doubles() doubles; its last three receive { sum (1 - q) over the unmasked windows, Nw [, unmasked windows
+// (three)] }.  gpad != NULL: gpad[pixel][band] = (float)((double)gpad[pixel][band] - ((double)weight / Nw) * G); NULL: sums alone.
+size_t ssim_loss_work_doubles();
+hipError_t launch_ssim_loss(const float* out, const float* y, int n, int c, int h, int w, const SsimLossTerm& term, int mask, float* gpad,
+                            double* work, bool three, hipStream_t stream);
+// ssim (or NULL; weight > 0) with ssim_work (ssim_loss_work_doubles() doubles): the term's gradient is added to gpad after the
+// pointwise kernel wrote it, and loss2[0] = (float)(sum rho / N + ((double)weight / Nw) * sum (1 - q)): one cast
 hipError_t launch_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h, int w,
-                            int kind, float param, int mask, hipStream_t stream);
+                            int kind, float param, int mask, hipStream_t stream, const SsimLossTerm* ssim = nullptr,
+                            double* ssim_work = nullptr);
 // v = m > 0 ? v : 0 (count % 4 == 0, 16-byte aligned)
 hipError_t launch_relu_mask(float* v, const float* m, size_t count, hipStream_t stream);
 // the precision-2 residual stream (hx: hi | xl planes, lo16) -> fp32 NHWC: the exact inverse of launch_split3_f32 (xl is not read)

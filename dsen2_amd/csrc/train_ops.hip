@@ -65,13 +65,15 @@ __global__ __launch_bounds__(kQThreads) void loss_grad_kernel(const float* __res
 }
 
 // one block: loss2 = ((float)(sum rho / count), (float)(sum d^2 / count)) from the blocks' partial pairs, in a fixed order
+// ssim_sums (or NULL): { sum (1 - q), Nw } of the SSIM term (ssim_loss.hip), added as tscale * sum, tscale = weight / Nw, in double
 __global__ __launch_bounds__(kQThreads) void loss_final_kernel(const double* __restrict__ partial, int blocks, double count,
-                                                               float* __restrict__ loss2) {
+                                                               float* __restrict__ loss2, const double* __restrict__ ssim_sums,
+                                                               double tscale) {
   double v[2];
   strided_partials<2>(partial, blocks, 2, v);
   block_tree<2>(v);
   if (threadIdx.x == 0) {
-    loss2[0] = (float)(v[0] / count);
+    loss2[0] = ssim_sums ? (float)__dadd_rn(v[0] / count, __dmul_rn(tscale, ssim_sums[0])) : (float)(v[0] / count);
     loss2[1] = (float)(v[1] / count);
   }
 }
@@ -305,8 +307,9 @@ size_t loss_partial_doubles(size_t pixels) {
 }
 
 hipError_t launch_loss_grad(const float* out, const float* y, float* gpad, double* partial, float* loss2, int n, int c, int h, int w,
-                            int kind, float param, int mask, hipStream_t stream) {
+                            int kind, float param, int mask, hipStream_t stream, const SsimLossTerm* ssim, double* ssim_work) {
   if (c < 1 || c > 16 || kind < 0 || kind >= kLossKinds || mask < 0 || mask >= kMaskModes) return hipErrorInvalidValue;
+  if (ssim && (!ssim_work || !(ssim->weight > 0.f))) return hipErrorInvalidValue;
   const size_t pixels = (size_t)n * h * w;
   const int blocks = (int)(loss_partial_doubles(pixels) / 2);
   const double count = (double)pixels * c;
@@ -317,7 +320,15 @@ hipError_t launch_loss_grad(const float* out, const float* y, float* gpad, doubl
   });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(kQThreads), 0, stream, partial, blocks, count, loss2);
+  const double* ssim_sums = nullptr;
+  double tscale = 0.0;
+  if (ssim) {
+    e = launch_ssim_loss(out, y, n, c, h, w, *ssim, mask, gpad, ssim_work, false, stream);
+    if (e != hipSuccess) return e;
+    ssim_sums = ssim_work + ssim_loss_work_doubles() - 3;
+    tscale = (double)ssim->weight / ((double)n * c * (h - ssim->win + 1) * (double)(w - ssim->win + 1));
+  }
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(kQThreads), 0, stream, partial, blocks, count, loss2, ssim_sums, tscale);
   return hipGetLastError();
 }
 

@@ -62,6 +62,11 @@ the number of all elements).  The epoch log's loss and valid columns, ReduceLROn
 min_delta stays 1e-6, which is large beside an MSE in this domain.  They work with --path and --tiles, every precision flag,
 --data_parallel and --emulate_world; a line at start-up names the loss.
 
+--ssim_weight X [--ssim_win 11] [--ssim_sigma 1.5] [--ssim_data_range 5.0] add Zhao et al. 2017's term, X times the mean over all
+windows of (1 - SSIM), to whatever --loss chose (S2Model.compile(ssim_weight=, ...); the gradient is a GPU kernel of its own).  The
+window is odd, 3..11; the data range lives in the reflectance / 2000 domain.  Patches must be at least the window on a side.  With
+--mask_nodata a window that holds a masked pixel adds nothing.  The loss and valid columns are then the total that is minimised.
+
     python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] --path P
 is that script's predict branch (--self_ensemble, not in the reference: predict(ensemble=True), the mean over the 8 flips and
 rotations of every patch; --augment is refused here): for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
@@ -130,6 +135,13 @@ def parse_args(argv=None):
     p.add_argument('--mask_nodata', action='store_true',
                    help='Training: a pixel whose target is 0 in every band carries no ground truth: it adds nothing to the loss, '
                         'the validation loss or any gradient.')
+    p.add_argument('--ssim_weight', type=float, default=0.0, metavar='X',
+                   help='Training: add X * mean over all windows of (1 - SSIM) to the loss (default 0: no such term).')
+    p.add_argument('--ssim_win', type=int, default=11, metavar='P', help='With --ssim_weight: the window, odd, 3..11 (default 11).')
+    p.add_argument('--ssim_sigma', type=float, default=1.5, help="With --ssim_weight: the Gaussian window's sigma (default 1.5).")
+    p.add_argument('--ssim_data_range', type=float, default=5.0, metavar='L',
+                   help='With --ssim_weight: the data range of c1 = (0.01 L)^2, c2 = (0.03 L)^2 in the reflectance / 2000 domain '
+                        '(default 5.0 = 10000 / 2000).')
     p.add_argument('--self_ensemble', action='store_true',
                    help='With --predict: average the predictions for the 8 flips and rotations of every patch (~8x the network time).')
     args = p.parse_args(argv)
@@ -141,6 +153,14 @@ def parse_args(argv=None):
         p.error('--loss %s needs --loss_param X with a finite X > 0' % args.loss)
     if args.loss_param is not None and args.loss not in ('huber', 'charbonnier'):
         p.error('--loss_param is an option of --loss huber and --loss charbonnier')
+    if args.predict_file and args.ssim_weight:
+        p.error('--ssim_weight is an option of training: it cannot be combined with --predict')
+    if not 0.0 <= args.ssim_weight < float('inf'):
+        p.error('--ssim_weight must be finite and >= 0')
+    if args.ssim_win % 2 == 0 or not 3 <= args.ssim_win <= 11:
+        p.error('--ssim_win must be odd and in 3..11')
+    if not (0.0 < args.ssim_sigma < float('inf') and 0.0 < args.ssim_data_range < float('inf')):
+        p.error('--ssim_sigma and --ssim_data_range must be finite and > 0')
     if args.self_ensemble and not args.predict_file:
         p.error('--self_ensemble is an option of --predict')
     if args.tiles is None and (args.steps_per_epoch is not None or args.val_crops is not None):
@@ -289,8 +309,9 @@ def run(args, rank, world):
         say('Model number is {}'.format(model_nr))
     model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
                   loss=args.loss or 'mean_absolute_error', mixed_precision=args.mixed_precision, loss_param=args.loss_param,
-                  mask_nodata=args.mask_nodata)
-    if args.loss is not None or args.mask_nodata:                # (without the new flags: the output as it always was)
+                  mask_nodata=args.mask_nodata, ssim_weight=args.ssim_weight, ssim_win=args.ssim_win, ssim_sigma=args.ssim_sigma,
+                  ssim_data_range=args.ssim_data_range)
+    if args.loss is not None or args.mask_nodata or args.ssim_weight:     # (without the new flags: the output as it always was)
         from . import losses
         say('Loss: {}.'.format(losses.describe(model.loss_setting)))
 

@@ -387,6 +387,43 @@ int dsen2_loss_sums_workspace_bytes(size_t *bytes);
 int dsen2_loss_sums(const float *dev_pred, const float *dev_target, int n, int c, long long hw, int kind, float param,
                     int mask_mode, void *dev_work, size_t work_bytes, double *dev_out3, void *stream);
 
+/* ---- the SSIM loss term (csrc/ssim_loss.hip) ---------------------------------------------------
+ * Zhao et al. 2017's restoration objective: what dsen2_model_gradients minimises becomes  pointwise loss + T,
+ *     T = weight * (1/Nw) * sum over the unmasked windows of (1 - q),      Nw = n*cout*(h-P+1)*(w-P+1),
+ * q the SSIM of dsen2_ssim_map (same filter over valid windows, same operation order, float32 promoted to float64) of every
+ * window of every (sample, band) plane of out against target, for a normalised separable window g[0 .. P-1] and c1, c2 > 0.
+ * A sample's band of q equals dsen2_ssim_map of that plane bit for bit.  With
+ *     A1 = 2*mx*my + c1   A2 = 2*(exy - mx*my) + c2   B1 = mx*mx + my*my + c1   B2 = (exx - mx*mx) + (eyy - my*my) + c2
+ *     a = 2*my*(A2 - A1)/(B1*B2) - 2*mx*q*(B2 - B1)/(B1*B2)     b = -q/B2     d = 2*A1/(B1*B2)
+ * and Gt the transposed ("full") separable filter,  G = Gt a + 2*x*Gt b + y*Gt d  and  dT/dout = -(weight/Nw) * G.  It ADDS to
+ * what the pointwise kernel wrote:  g[pixel][band] = (float)((double)g[pixel][band] + scale*G), scale = -(double)weight/Nw: one
+ * rounding.  T is added to the loss in double before dev_loss2[0]'s one cast to float; dev_loss2[1] (the MSE) is untouched.
+ * Float64 throughout, every operation rounded on its own, taps summed k = 0 .. P-1 in order; csrc/ssim_loss.hip lists every
+ * operation, tests/ssim_loss_restatement.py and dsen2_amd/losses.py restate them in numpy.  Sums run in an order the shape alone
+ * fixes (no atomics): the same bits on every run.
+ * Mask mode 1 (the no-data mask above): a window that holds at least one pixel whose target is 0 in all bands of that sample
+ * adds nothing to the sum and has a = b = d = 0, so a masked pixel's SSIM gradient is 0.  Nw stays the number of ALL windows,
+ * for the reason N does above.
+ * dsen2_model_set_loss_ssim: state on a trainable handle next to dsen2_model_set_loss.  weight 0 (the default): nothing of the
+ *   term is launched and every bit of a step is what it was without it (the window and constants are still checked).
+ *   DSEN2_ERR_INVALID, nothing changed: a weight that is not finite or < 0; win even or outside 3..11; a window entry that is not
+ *   finite; c1 or c2 not finite or not > 0; a precision-1 handle.  With weight > 0 dsen2_model_gradients returns
+ *   DSEN2_ERR_INVALID with nothing launched when h < win or w < win.
+ * dsen2_ssim_loss_grad: the kernel alone (kernel-level tests): dev_out, dev_target NCHW [n,c,h,w] float32, c in 1..15; it
+ *   ACCUMULATES into lanes 0 .. c-1 of dev_g_nhwc16 [n*h*w][16] (the other lanes are not touched) and writes dev_sums2 =
+ *   { sum (1 - q) over the unmasked windows, Nw } as float64.  Allocates its scratch and synchronises.
+ * dsen2_ssim_loss_sums: the sums alone, for validation: dev_out3 = { sum (1 - q), Nw, unmasked windows } as float64, the first
+ *   the bits dsen2_ssim_loss_grad gives.  dev_work: dsen2_ssim_loss_sums_workspace_bytes() bytes of device scratch.  Refusals:
+ *   NULL, a bad shape, window or constants, h or w < win: DSEN2_ERR_INVALID; a short workspace: DSEN2_ERR_WORKSPACE. */
+int dsen2_model_set_loss_ssim(dsen2_model *m, float weight, const double *host_window, int win, double c1, double c2);
+int dsen2_ssim_loss_grad(const float *dev_out, const float *dev_target, int n, int c, int h, int w, float weight,
+                         const double *host_window, int win, double c1, double c2, int mask_mode, float *dev_g_nhwc16,
+                         double *dev_sums2, void *stream);
+int dsen2_ssim_loss_sums_workspace_bytes(size_t *bytes);
+int dsen2_ssim_loss_sums(const float *dev_pred, const float *dev_target, int n, int c, int h, int w, const double *host_window,
+                         int win, double c1, double c2, int mask_mode, void *dev_work, size_t work_bytes, double *dev_out3,
+                         void *stream);
+
 /* ---- tiling / up-sampling / recomposition (utils/patches.py) --------------------------------
  * dsen2_upsample_mirror_bilinear  <->  interp_patches            utils/patches.py:11-16
  *   planes x [h,w] -> planes x [oh,ow]; half-pixel-centre bilinear with mirror boundary (skimage

@@ -2,7 +2,7 @@
 """Fine-tuning speed: one JSON line per configuration.
 
     python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N] [--precision fp32|bf16x3] [--mixed_precision bf16]
-                                [--shards K [K ...]] [--loss mae|mse|huber|charbonnier] [--loss_param X] [--mask_nodata]
+                                [--shards K [K ...]] [--loss mae|mse|huber|charbonnier] [--loss_param X] [--mask_nodata] [--ssim_weight X]
 
   step_ms            one training step on device-resident data: dsen2_model_gradients + dsen2_nadam_step + the device repack
   train_on_batch_ms  S2Model.train_on_batch from host arrays (adds the H2D copies and the loss read-back)
@@ -25,6 +25,7 @@ then is what it always was).  With --mask_nodata the target gets a blank corner 
 DSen2 runs at batch 128, VDSen2 at batch 8, both on 32 x 32 patches (training/supres_train.py's batch sizes).
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -37,6 +38,7 @@ from dsen2_amd import _lib, training, weights  # noqa: E402
 from dsen2_amd.DSen2Net import _ptr, _stream_ptr, bf16_plane_f32, s2model, split3_f32  # noqa: E402
 
 PEAK_TF = 157.3   # fp32 MFMA peak of the MI355X (MI355X_MICROARCH.md)
+HBM_BYTES_PER_S = 8.0e12   # the MI355X's HBM3E peak, for the floor of a memory-bound kernel
 PEAK_TF_BF16 = 2500.0   # dense bf16 MFMA peak
 CONFIGS = {'dsen2': dict(d=6, F=128, batch=128), 'vdsen2': dict(d=32, F=256, batch=8)}
 
@@ -54,14 +56,14 @@ def timed(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters
 
 
-def run(name, iters, precision='fp32', mixed_precision=None, shards=(), loss=None, loss_param=None, mask_nodata=False):
+def run(name, iters, precision='fp32', mixed_precision=None, shards=(), loss=None, loss_param=None, mask_nodata=False, ssim_weight=0.0):
     c = CONFIGS[name]
     d, F, n, h, w = c['d'], c['F'], c['batch'], 32, 32
     dev = torch.device('cuda', 0)
     m = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev, precision=precision)
     m.set_weights_flat(weights.random_he_uniform(10, 6, d, F, seed=1, bias_scale=0.05))
     m.compile(training.Nadam(lr=1e-4), loss=loss or 'mean_absolute_error', mixed_precision=mixed_precision, loss_param=loss_param,
-              mask_nodata=mask_nodata)
+              mask_nodata=mask_nodata, ssim_weight=ssim_weight)
     rng = np.random.default_rng(0)
     xs = [rng.uniform(0, 0.5, (n, k, h, w)).astype(np.float32) for k in (4, 6)]
     y = rng.uniform(0, 0.5, (n, 6, h, w)).astype(np.float32)
@@ -133,6 +135,22 @@ def run(name, iters, precision='fp32', mixed_precision=None, shards=(), loss=Non
     res.update(extra)
     if loss is not None or mask_nodata:
         res.update(loss=loss or 'mae', loss_param=loss_param, mask_nodata=bool(mask_nodata))
+    if ssim_weight:
+        # the term's kernel alone through its test entry, which allocates its scratch and synchronises on every call: an upper
+        # bound of the kernel time (the step with the weight at 0 is the other way to read it); and its HBM floor: out and target
+        # read, the NHWC16 gradient read and written
+        from dsen2_amd import losses
+        window, c1, c2 = losses.ssim_constants(losses.ssim_part(m.loss_setting))
+        cwin = (ctypes.c_double * window.size)(*window.tolist())
+        out_d = torch.from_numpy(rng.uniform(0, 0.5, y.shape).astype(np.float32)).to(dev)
+        g16 = torch.zeros((n * h * w, 16), device=dev)
+        sums2 = torch.zeros(2, dtype=torch.float64, device=dev)
+        call_ms = timed(lambda: _lib.call('dsen2_ssim_loss_grad', _ptr(out_d), _ptr(y_d), n, 6, h, w, float(ssim_weight), cwin,
+                                          int(window.size), c1, c2, int(bool(mask_nodata)), _ptr(g16), _ptr(sums2), _stream_ptr(dev)),
+                        iters, warm=2)
+        hbm_bytes = 2 * y.size * 4 + 2 * g16.numel() * 4
+        res.update(ssim_weight=ssim_weight, ssim_loss_call_ms=round(call_ms, 4), ssim_loss_hbm_bytes=hbm_bytes,
+                   ssim_loss_hbm_floor_ms=round(hbm_bytes / HBM_BYTES_PER_S * 1e3, 5))
     print(json.dumps(res), flush=True)
 
 
@@ -146,11 +164,12 @@ def main():
     ap.add_argument('--loss', default=None, choices=['mae', 'mse', 'huber', 'charbonnier'])
     ap.add_argument('--loss_param', type=float, default=None)
     ap.add_argument('--mask_nodata', action='store_true')
+    ap.add_argument('--ssim_weight', type=float, default=0.0, help="compile()'s ssim_weight (window 11, sigma 1.5, data range 5.0)")
     args = ap.parse_args()
     if args.mixed_precision and args.precision != 'fp32':
         ap.error('--mixed_precision is an option of --precision fp32')
     for name in (['dsen2', 'vdsen2'] if args.config == 'both' else [args.config]):
-        run(name, args.iters, args.precision, args.mixed_precision, args.shards, args.loss, args.loss_param, args.mask_nodata)
+        run(name, args.iters, args.precision, args.mixed_precision, args.shards, args.loss, args.loss_param, args.mask_nodata, args.ssim_weight)
 
 
 if __name__ == '__main__':
