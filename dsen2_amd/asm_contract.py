@@ -16,7 +16,9 @@ the two translation units to ISA with exactly the product's flags and fails (Asm
     belongs to the next workgroup);
   * the bf16 kernel's epilogues contain exactly the number of vector-memory operations its first-chunk waits count
     as younger than their target (conv3x3_body16w.hip, E_OPS): an over-count there would be a weaker wait;
-  * nothing is called out of line (an epilogue that is not inlined passes 128 accumulators through memory).
+  * nothing is called out of line (an epilogue that is not inlined passes 128 accumulators through memory);
+  * in the fp32 kernel's DeferAsym form (waves 0-3 issue every DMA) one copy of the item loop holds all the DMAs, in whole
+    statements of two or four between one M0 save and one restore, and the other copy holds no `... lds` load and no M0 use.
 
 The matrix-core output convolution (conv3x3_out_mfma.hip) has no inline-asm DMA, but its speed rests on where hipcc
 puts the waits for its operand loads (one unit = 8 loads ahead, issued in two halves): `check_out_mfma_listing` fails unless
@@ -150,6 +152,33 @@ def check_listing(text, src):
         need(back and back[-1].replace(' ', '') in ('s_waitcntvmcnt(0)', 's_waitcntvmcnt(0)lgkmcnt(0)'),
              'kernel %s does not drain its DMAs before s_endpgm' % name, back[-3:])
     need(n_dma_kernels > 0, 'no LDS-DMA kernel found')
+    if src == 'conv3x3_body32.hip':
+        # Body32Form::DeferAsym (template argument STG >= 2): two copies of the item loop, each 2 (first / other input chunks) x 9
+        # steps x 64 MFMAs.  One copy (waves 0-3) holds every DMA of the loop, whole statements of four (weight chunk) or two
+        # (input round) DMAs between one M0 save and one restore; the other (waves 4-7) holds no `... lds` load and no M0 use.
+        ITEM_MFMAS = 2 * 9 * 64
+        asym = {k: v for k, v in kernels.items() if re.search(r'conv3x3_body32_kernelILi\d+ELi\d+ELi\d+ELi\d+ELi\d+ELi[2-9]E', k)}
+        need(asym, 'no DeferAsym instantiation of the fp32 body kernel found')
+        for name, body in asym.items():
+            mf = [i for i, ln in enumerate(body) if ln.startswith('v_mfma')]
+            need(len(mf) == 2 * ITEM_MFMAS, 'kernel %s: %d MFMAs, expected two copies of the item loop' % (name, len(mf)))
+            copies = [body[mf[0]:mf[ITEM_MFMAS - 1]], body[mf[ITEM_MFMAS]:mf[-1]]]
+            n_dma = [sum(1 for ln in c if ln.startswith('buffer_load_dword') and ln.endswith('lds')) for c in copies]
+            need(min(n_dma) == 0 and max(n_dma) > 0, 'kernel %s: DMAs in both copies of the item loop' % name, n_dma)
+            quiet, loud = (copies[0], copies[1]) if n_dma[0] == 0 else (copies[1], copies[0])
+            need(not any(re.search(r'\bm0\b', ln) for ln in quiet), 'kernel %s: M0 use in the compute-only copy' % name)
+            # one save per statement: every run of DMAs between a save and a restore is 2 or 4 long
+            run = None
+            for ln in loud:
+                if re.match(r's_mov_b32 (s\d+|vcc_lo|vcc_hi), m0$', ln):
+                    need(run is None, 'kernel %s: M0 saved twice in one DMA statement' % name)
+                    run = 0
+                elif ln.startswith('buffer_load_dword') and ln.endswith('lds'):
+                    need(run is not None, 'kernel %s: DMA outside a statement that saves M0' % name)
+                    run += 1
+                elif run and not re.match(r'(s_mov_b32 m0, |s_nop 0$)', ln):
+                    need(run in (2, 4), 'kernel %s: a DMA statement of %d instructions' % (name, run))
+                    run = None
     if src == 'conv3x3_body16w.hip':
         # E_OPS of the kernel: epilogue 0 = 16 stores; 1 and 3 = 32 loads + 32 stores (compiler-visible buffer
         # operations only: the DMAs are `... lds`), once in each of the two copies of the item loop (issuing waves
@@ -247,10 +276,10 @@ def check_first16_listing(text, src='conv3x3_first16.hip'):
 # library at build time (kernel_isa.json) and next to the traffic figure when tools/update_traffic_json.py records it, so
 # bench.py can refuse a figure measured on another instruction stream.
 TRAFFIC_KERNELS = {
-    'dsen2_20_fp32': ('conv3x3_body32.hip', r'conv3x3_body32_kernelILi128ELi128ELi0ELi0ELi0ELb1ELb1E'),
+    'dsen2_20_fp32': ('conv3x3_body32.hip', r'conv3x3_body32_kernelILi128ELi128ELi0ELi0ELi0ELi4ELb1E'),
     'vdsen2_20_bf16': ('conv3x3_body16w.hip', r'conv3x3_body16w_chain_kernelILi128ELi256ELi0E'),
     'dsen2_20_bf16x3': ('conv3x3_body16w.hip', r'conv3x3_body16w_x3_chain_kernelILi64ELi128E'),
-    'vdsen2_20_fp32': ('conv3x3_body32.hip', r'conv3x3_body32_kernelILi256ELi256ELi0ELi0ELi0ELb1ELb1E'),
+    'vdsen2_20_fp32': ('conv3x3_body32.hip', r'conv3x3_body32_kernelILi256ELi256ELi0ELi0ELi0ELi4ELb1E'),
     'dsen2_20_bf16': ('conv3x3_body16w.hip', r'conv3x3_body16w_chain_kernelILi64ELi128ELi0E'),
     'vdsen2_20_bf16x3': ('conv3x3_body16w.hip', r'conv3x3_body16w_x3_chain_kernelILi128ELi256E'),
 }

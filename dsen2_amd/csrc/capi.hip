@@ -477,18 +477,18 @@ const char* dsen2_last_error(void) { return g_err; }
 
 #ifdef DSEN2_DIAG
 // Diagnostic build only — not declared in include/dsen2_hip.h.  The integer keys and values are the wire format of tools/ and
-// of DSEN2_DIAG_SET, translated to Tuning's typed fields here and nowhere else.  key 0: fp32 body convolution (14 default, 11-13
-// the other forms of conv3x3_body32.hip, 0 one tile per workgroup — and the first convolution over all 16 padded channels);
+// of DSEN2_DIAG_SET, translated to Tuning's typed fields here and nowhere else.  key 0: fp32 body convolution (15 default, 11-14
+// and 16-19 the other forms of conv3x3_body32.hip, 0 one tile per workgroup — and the first convolution over all 16 padded channels);
 // key 1: timing-only ablation mask of the persistent body kernels (outputs are WRONG while non-zero); key 2: output-layer
 // kernel (2 = matrix cores where the shape fits, 3 = vector units, 0 = padded MFMA block).
 int dsen2_diag_set(int key, int value) {
   Tuning& t = g_diag_tuning;
   switch (key) {
     case 0:
-      if (value != 0 && (value < 11 || value > 14)) return fail(DSEN2_ERR_INVALID, "body variant %d unknown", value);
+      if (value != 0 && (value < 11 || value > 19)) return fail(DSEN2_ERR_INVALID, "body variant %d unknown", value);
       t.first = value == 0 ? FirstKernel::Tile16 : FirstKernel::Direct;
       t.body = value == 0 ? BodyKernel::Tile : BodyKernel::Body32;
-      t.body32 = value == 0 ? Body32Form::DeferStagger : static_cast<Body32Form>(value - 11);
+      t.body32 = value == 0 ? Body32Form::DeferAsym : static_cast<Body32Form>(value - 11);
       return DSEN2_OK;
     case 2:
       if (value != 0 && value != 2 && value != 3) return fail(DSEN2_ERR_INVALID, "output variant %d unknown", value);

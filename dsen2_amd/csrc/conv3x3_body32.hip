@@ -17,7 +17,8 @@
 //     registers — and written out in 16 pieces inside the next item's first 8 steps, residual quads fetched one
 //     step ahead; without DEFER the residual tile is fetched under the item's last step (PRE) and the epilogue's
 //     stores drain under the next item's first step (3.5 us);
-//   * waves 4-7 issue their DMAs half a step after waves 0-3 (STG).
+//   * waves 4-7 issue their DMAs half a step after waves 0-3 (STG 1), or waves 0-3 issue every DMA and waves 4-7 none
+//     (STG 2 and up, Body32Form::DeferAsym: dma::Role::Issuer in conv3x3_dma.h).
 //
 // Per wave: 64 channels x 64 pixels = 2 x 2 accumulators of 32x32; one step = 4 k-steps of 16 MFMAs and
 // 4 ds_read_b128.  Same arithmetic order per output element as the one-tile-per-workgroup kernel of conv3x3_mfma.hip:
@@ -40,16 +41,21 @@ static_assert((8 * kHalo) % 16 == 0, "rows R and R+8 of a pixel block sit on the
 
 // ABL: timing-only ablation mask (1 no stores, 2 no residual loads, 4 no weight stream, 8 no input stream,
 // 16 no barriers).  PRE: 32-channel blocks (0-2) whose residual values are fetched under the item's last step.
-// STG: waves 4-7 issue their DMAs half a step after waves 0-3 (two copies of the item loop).
+// STG: 1 = waves 4-7 issue their DMAs half a step after waves 0-3 (two copies of the item loop); 2 and up = waves 0-3 issue
+// every DMA, waves 4-7 run a copy of the item loop with no DMA statement and no hand-counted wait: STG - 2 = the k-step
+// (0-3) at which the issuers issue, + 4 for waves 4-7 at s_setprio 1 (the product's is 4: half a step into the step, measured
+// in profiles/body32_asym.md; the others exist in the diagnostic build only).
 // DEFER: the epilogue of item i is cut into 16 pieces (one 16-byte register quad each) that run inside the first
 // 8 steps of item i+1, out of a copy of the accumulators: loads and stores trickle out under MFMAs instead of in a
 // burst between items (PRE is then unused: a piece's residual quad is fetched one step before the piece runs).
-template <int CIN, int COUT, int EPI, int ABL, int PRE, bool STG, bool DEFER>
+template <int CIN, int COUT, int EPI, int ABL, int PRE, int STG, bool DEFER>
 __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvParams p, const int n_items) {
   constexpr int NCC = CIN / KC;
   constexpr int NS = COUT / NT;
   static_assert(NCC % 2 == 0, "input double buffer parity");
-  constexpr int N_W = (ABL & 4) ? 0 : 2;                   // weight DMAs per wave and step
+  constexpr bool ASYM = STG >= 2;
+  using Stage = dma::Stage<CIN, NS, false, ASYM ? dma::Role::Issuer : dma::Role::All>;
+  constexpr int N_W = (ABL & 4) ? 0 : Stage::N_W;          // weight DMAs per issuing wave and step
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* const in_s = smem;                            // [2][8][QS][4 words]
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
   const size_t img_pix = (size_t)p.h * p.w;
 
   // ---- the two DMA streams (conv3x3_dma.h) ----
-  dma::Stage<CIN, NS> st;
+  Stage st;
   st.init(p, in_s, w_s, lane, wave, lid, G, n_items);
 
   // ---- per-lane operand addresses (words) ----
@@ -84,15 +90,17 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
   const int w_lane = (hsel * NT + wn * 64 + l31) * 4;
 
   // ---- prologue: first item's input chunk 0, weight chunks 0-2 ----
-  st.set_stage_item(lid);
-  if constexpr (!(ABL & 8)) {
+  if (!ASYM || wave < 4) {
+    st.set_stage_item(lid);
+    if constexpr (!(ABL & 8)) {
 #pragma unroll
-    for (int b = 0; b < IN_BLOCKS; ++b) st.issue_in(0, b, 0);
-  }
-  if constexpr (!(ABL & 4)) {
-    st.issue_w();
-    st.issue_w();
-    st.issue_w();
+      for (int b = 0; b < IN_BLOCKS; ++b) st.issue_in(0, b, 0);
+    }
+    if constexpr (!(ABL & 4)) {
+      st.issue_w();
+      st.issue_w();
+      st.issue_w();
+    }
   }
   if (tid < COUT) bias_s[tid] = p.bias[tid];
   wait_vmcnt<0>();
@@ -130,8 +138,10 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
     return g_.col_ok && g_.ey + pb < p.h ? (g_.lane_eoff + (unsigned)(pb * p.w * COUT + mb * 32 + 8 * g)) * 4u : 0x80000000u;
   };
 
-  auto run = [&](auto mid_c) {
+  // ISSUE: this copy of the item loop issues DMAs (and waits for them); without it the copy holds no DMA statement
+  auto run = [&](auto mid_c, auto issue_c) {
   constexpr int MIDS = decltype(mid_c)::value;
+  constexpr bool ISSUE = decltype(issue_c)::value;
   f32x16 acc[MB][PB];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
@@ -231,14 +241,16 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
       // (on the very last item: its own chunk 0 again, which nobody reads)
       const bool last_cc = cc == NCC - 1;
       const int in_cc = last_cc ? 0 : cc + 1;
-      if (last_cc && have_next_item) st.set_stage_item(item + G);
+      if constexpr (ISSUE) {
+        if (last_cc && have_next_item) st.set_stage_item(item + G);
+      }
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const float* const wb = w_s + mf_slot * WCH;
         const int nx_slot = mf_slot == NWBUF - 1 ? 0 : mf_slot + 1;
         const float* const wb_nx = w_s + nx_slot * WCH;
         constexpr int kNoIn = (ABL & 8) ? 1 : 0;
-        const int n_in = (tap < IN_BLOCKS && !kNoIn) ? 1 : 0;     // folds: tap is an unrolled constant
+        const int n_in = (tap < IN_BLOCKS && !kNoIn) ? Stage::N_IN : 0;     // folds: tap is an unrolled constant
 
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
@@ -252,7 +264,9 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
           if constexpr (DEFER) {
             // first input chunk of an item only (this copy of the code): step `tap` finishes pieces 2*tap and
             // 2*tap + 1 of the previous item; their residual quads were fetched one step earlier, BEFORE that
-            // step's DMAs in issue order, so waiting for them never waits for a DMA younger than a step
+            // step's DMAs in issue order, so waiting for them never waits for a DMA younger than a step (issuers of
+            // the DeferAsym form, which issue at k-step 2 and finish piece 2*tap at k-step 1: three quarters of a step;
+            // issuing at k-step 0 put six fresh DMAs in front of that wait and cost conv-B 0.5 %)
             if (kFirst && tap < 8) {
               if (s == MIDS && kRes && tap < 7) {
                 rq[2 * ((tap + 1) & 1)] = load_res(2 * tap + 2);
@@ -260,10 +274,12 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
               }
             }
           }
-          if (s == MIDS) {
-            // this step's DMAs: input round first, then the weight chunk three steps ahead
-            if (n_in) st.issue_in((cc + 1) & 1, tap < IN_BLOCKS ? tap : 0, in_cc);
-            if constexpr (!(ABL & 4)) st.issue_w();
+          if constexpr (ISSUE) {
+            if (s == MIDS) {
+              // this step's DMAs: input round first, then the weight chunk three steps ahead
+              if (n_in) st.issue_in((cc + 1) & 1, tap < IN_BLOCKS ? tap : 0, in_cc);
+              if constexpr (!(ABL & 4)) st.issue_w();
+            }
           }
           if constexpr (DEFER) {
             if (kFirst && tap < 8 && (s == 1 || s == 3)) {
@@ -306,7 +322,10 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
         __builtin_amdgcn_sched_barrier(0);
         // retire the weight chunk issued in the PREVIOUS step (and everything older): what this wave issued after
         // it is AT LEAST this step's input round and weight chunk (anything more only makes the wait stricter)
-        if (n_in) wait_vmcnt<N_W + 1>(); else wait_vmcnt<N_W>();
+        // (a copy that issues none takes the data from the barrier behind the issuers' wait)
+        if constexpr (ISSUE) {
+          if (n_in) wait_vmcnt<N_W + Stage::N_IN>(); else wait_vmcnt<N_W>();
+        }
         if constexpr (!(ABL & 16)) __syncthreads();
       }
     };
@@ -315,36 +334,53 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_body32_kernel(const ConvPa
     for (int cc = 1; cc < NCC; ++cc) do_cc(cc, std::false_type{});
   }
   };   // run
-  if constexpr (STG) {
+  if constexpr (ASYM) {
+    if (wave < 4) {
+      run(std::integral_constant<int, (STG - 2) % KSTEPS>{}, std::true_type{});
+    } else {
+      // static priority for the half that is dispatched second (wave-uniform: `wave` is a scalar)
+      if constexpr ((STG - 2) / KSTEPS == 1) __builtin_amdgcn_s_setprio(1);
+      run(std::integral_constant<int, 0>{}, std::false_type{});
+    }
+  } else if constexpr (STG == 1) {
     if (wave < 4)
-      run(std::integral_constant<int, 0>{});
+      run(std::integral_constant<int, 0>{}, std::true_type{});
     else
-      run(std::integral_constant<int, KSTEPS / 2>{});
+      run(std::integral_constant<int, KSTEPS / 2>{}, std::true_type{});
   } else {
-    run(std::integral_constant<int, 0>{});
+    run(std::integral_constant<int, 0>{}, std::true_type{});
   }
   wait_vmcnt<0>();       // no DMA may still be writing this workgroup's LDS when it is released
 }
 
-template <int CIN, int COUT, int EPI, int ABL = 0, int PRE = 0, bool STG = false, bool DEFER = false>
+template <int CIN, int COUT, int EPI, int ABL = 0, int PRE = 0, int STG = 0, bool DEFER = false>
 static hipError_t launch_body32_one(const ConvParams& p, hipStream_t stream) {
   const long long items = (long long)p.n * p.tiles_x * p.tiles_y * (COUT / NT);
   return launch_persistent<conv3x3_body32_kernel<CIN, COUT, EPI, ABL, PRE, STG, DEFER>>(LDS_BYTES, THREADS, items, 1, 0, stream, p);
 }
+
+constexpr int kAsym = 2 + KSTEPS / 2;      // STG of Body32Form::DeferAsym: the issuers' DMAs half a step into the step
 
 template <int F>
 static hipError_t launch_body32_feat(const ConvParams& p, int epilogue, Body32Form form, hipStream_t stream) {
   const bool relu = epilogue == kEpiRelu;
 #ifdef DSEN2_DIAG
   if (form == Body32Form::Plain || form == Body32Form::StaggerA) {
-    if (!relu) return launch_body32_one<F, F, kEpiResidual, 0, 2, false>(p, stream);
-    return form == Body32Form::Plain ? launch_body32_one<F, F, kEpiRelu, 0, 0, false>(p, stream) : launch_body32_one<F, F, kEpiRelu, 0, 0, true>(p, stream);
+    if (!relu) return launch_body32_one<F, F, kEpiResidual, 0, 2, 0>(p, stream);
+    return form == Body32Form::Plain ? launch_body32_one<F, F, kEpiRelu, 0, 0, 0>(p, stream) : launch_body32_one<F, F, kEpiRelu, 0, 0, 1>(p, stream);
   }
-  if (form == Body32Form::DeferStaggerA && !relu) return launch_body32_one<F, F, kEpiResidual, 0, 0, false, true>(p, stream);
+  if (form == Body32Form::DeferStaggerA && !relu) return launch_body32_one<F, F, kEpiResidual, 0, 0, 0, true>(p, stream);
+  if (form == Body32Form::DeferStagger || form == Body32Form::DeferStaggerA)
+    return relu ? launch_body32_one<F, F, kEpiRelu, 0, 0, 1, true>(p, stream) : launch_body32_one<F, F, kEpiResidual, 0, 0, 1, true>(p, stream);
+#define DSEN2_ASYM(FORM, STG)                                                                                      \
+  if (form == Body32Form::FORM)                                                                                    \
+    return relu ? launch_body32_one<F, F, kEpiRelu, 0, 0, STG, true>(p, stream) : launch_body32_one<F, F, kEpiResidual, 0, 0, STG, true>(p, stream);
+  DSEN2_ASYM(DeferAsymS0, 2) DSEN2_ASYM(DeferAsymS1, 3) DSEN2_ASYM(DeferAsymS3, 5) DSEN2_ASYM(DeferAsymPrio, 8)
+#undef DSEN2_ASYM
 #else
-  if (form != Body32Form::DeferStagger) return hipErrorInvalidValue;     // the other forms exist in the diagnostic build only
+  if (form != Body32Form::DeferAsym) return hipErrorInvalidValue;     // the other forms exist in the diagnostic build only
 #endif
-  return relu ? launch_body32_one<F, F, kEpiRelu, 0, 0, true, true>(p, stream) : launch_body32_one<F, F, kEpiResidual, 0, 0, true, true>(p, stream);
+  return relu ? launch_body32_one<F, F, kEpiRelu, 0, 0, kAsym, true>(p, stream) : launch_body32_one<F, F, kEpiResidual, 0, 0, kAsym, true>(p, stream);
 }
 
 hipError_t launch_conv3x3_body32(const ConvParams& p, int feat, int epilogue, Body32Form form, int ablate, hipStream_t stream) {
@@ -352,6 +388,13 @@ hipError_t launch_conv3x3_body32(const ConvParams& p, int feat, int epilogue, Bo
   if ((size_t)p.h * p.w * feat * 4 >= 0x80000000ull) return hipErrorNotSupported;
 #ifdef DSEN2_DIAG
   if (feat == 128 && ablate != 0) {
+    // the masks of the DeferAsym form that the mask table of profiles/body32_asym.md needs
+#define DSEN2_ABL_ASYM(M)                                                                                \
+  if (ablate == M && form == Body32Form::DeferAsym)                                                      \
+    return epilogue == kEpiRelu ? launch_body32_one<128, 128, kEpiRelu, M, 0, kAsym, true>(p, stream)    \
+                                : launch_body32_one<128, 128, kEpiResidual, M, 0, kAsym, true>(p, stream);
+    DSEN2_ABL_ASYM(3) DSEN2_ABL_ASYM(15) DSEN2_ABL_ASYM(16)
+#undef DSEN2_ABL_ASYM
 #define DSEN2_ABL(M)                                                                             \
   if (ablate == M)                                                                               \
     return epilogue == kEpiRelu ? launch_body32_one<128, 128, kEpiRelu, M>(p, stream)            \

@@ -23,6 +23,29 @@
 //   * a wait that assumes FEWER younger operations than there are is stricter, never weaker — so is every wait
 //     hipcc inserts for the loads it does track (it counts none of the DMAs);
 //   * a workgroup must not end with a DMA in flight (its LDS may already belong to the next one): vmcnt(0) at exit.
+//
+// Role::Issuer (Body32Form::DeferAsym): waves 0-3 move everything, waves 4-7 never touch a Stage and run a copy of the
+// item loop without a DMA statement, set_stage_item or hand-counted wait.  Same chunks, same steps, same slots — only who
+// issues changes, so every rule above holds with these counts:
+//   * a weight chunk is 16 wave instructions = FOUR per issuing wave (bytes 1024*wave + 4096*k, k = 0..3, of the chunk:
+//     N_W = 4), in one asm statement with one M0 save and restore;
+//   * an input round is TWO instructions per issuing wave: wave q moves channel groups q and q + 4 of the round's 64 halo
+//     pixels (the second one 64 bytes further into the pixel — through soffset, which the range check ignores, so an
+//     out-of-range lane stays out of range and writes the zero padding — and 4*QS*16 bytes further into LDS); the 16-lane
+//     tail round keeps its EXEC mask around both;
+//   * the step-end wait of an issuing wave retires the weight chunk of the PREVIOUS step: younger than it are at least this
+//     step's input round (2, taps 0-5) and weight chunk (4), so vmcnt(6) in taps 0-5 and vmcnt(4) in taps 6-8.  Whatever
+//     else the wave issued in between (two residual quads, two stores of the deferred epilogue) only makes the wait
+//     stricter.  The six rounds of an input chunk are still older than the weight chunk of tap 5, retired at the end of
+//     tap 6;
+//   * waves 4-7 take the data from the barrier that follows the issuers' wait (a DMA that has left vmcnt has written its
+//     LDS); their own vmcnt queue holds only their epilogue's loads and stores, which hipcc counts exactly;
+//   * in flight per issuing wave: a step issues at most 2 residual loads + 2 + 4 DMAs + 2 stores = 10 and ends with at most
+//     6 + 2 outstanding, so the peak is below 20; the prologue (12 input + 12 weight DMAs + the bias load) reaches 25 and
+//     the last item's epilogue 32 on top of at most 8 — all far below the 6-bit field's 63;
+//   * LDS addresses: an input DMA ends at most at (7*QS + 64*4)*16 + 1024 = 42,752 <= IN_BYTES (tail round: (7*QS + 320)*16
+//     + 256 = IN_BYTES exactly), a weight DMA at 1024*3 + 4096*3 + 1024 = WCH*4 inside its ring slot;
+//   * every wave still ends with vmcnt(0).
 #pragma once
 #include "conv3x3_items.h"
 
@@ -51,11 +74,17 @@ __device__ __forceinline__ unsigned lds_address(const float* p) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const float*)p;
 }
 
+// Who issues the DMAs: All = every one of the eight waves its share (wave q: channel group q, 2 KiB of a weight chunk);
+// Issuer = waves 0-3 everything (the rules above), waves 4-7 never call into the Stage.
+enum class Role { All, Issuer };
+
 // Per-thread state of the two streams.  CINW = 32-bit words per input pixel; NS = output slabs per tile.
 // LAZY_VOFF: do not keep the six per-lane input offsets in registers across the item but recompute the one a round
 // needs from the staged tile's origin (a dozen VALU operations per step; for kernels that are out of VGPRs).
-template <int CINW, int NS, bool LAZY_VOFF = false>
+template <int CINW, int NS, bool LAZY_VOFF = false, Role ROLE = Role::All>
 struct Stage {
+  static constexpr int N_W = ROLE == Role::Issuer ? 4 : 2;      // wave instructions per weight chunk and issuing wave
+  static constexpr int N_IN = ROLE == Role::Issuer ? 2 : 1;     // ... per input round
   static constexpr int NCC = CINW / KC;
   static constexpr int NCHUNK = NCC * 9;
 
@@ -106,11 +135,30 @@ struct Stage {
     }
   }
 
-  // round b of input chunk cc into buffer `buf` (one wave instruction per wave)
+  // round b of input chunk cc into buffer `buf` (N_IN wave instructions per issuing wave)
   __device__ __forceinline__ void issue_in(int buf, int b, int cc) {
     const unsigned m0v = lds_in + buf * IN_BYTES + (wave * QS + 64 * b) * 16;
     const unsigned so = cc * (KC * 4);
     const unsigned voff = LAZY_VOFF ? voff_of(b, st_y0, st_x0) : in_voff[LAZY_VOFF ? 0 : b];
+    if constexpr (ROLE == Role::Issuer) {
+      // channel groups `wave` and `wave + 4`: 64 bytes further into the pixel, 4 group rows further into LDS
+      const unsigned m1v = m0v + 4 * QS * 16, so1 = so + 64;
+      unsigned saved_m0;
+      if (b < IN_BLOCKS - 1) {
+        asm volatile("s_mov_b32 %0, m0\n\t"
+                     "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %5 offen lds\n\t"
+                     "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %6 offen lds\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(saved_m0) : "s"(m0v), "s"(m1v), "v"(voff), "s"(in_rsrc), "s"(so), "s"(so1) : "memory");
+      } else if (lane < 16) {
+        asm volatile("s_mov_b32 %0, m0\n\t"
+                     "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %5 offen lds\n\t"
+                     "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %6 offen lds\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(saved_m0) : "s"(m0v), "s"(m1v), "v"(voff), "s"(in_rsrc), "s"(so), "s"(so1) : "memory");
+      }
+      return;
+    }
     // M0 is saved and restored inside the statement: hipcc reserves M0 and rejects it in a clobber list, so the
     // compiler's own uses of M0 (none today) must never see the DMA's value
     unsigned saved_m0;
@@ -123,12 +171,25 @@ struct Stage {
     }
   }
 
-  // the next weight chunk of the stream (16 wave instructions of 1 KiB, two per wave) into the next ring slot; the
-  // stream runs over item boundaries and, past the last item, wraps to this workgroup's first one (harmless)
+  // the next weight chunk of the stream (16 wave instructions of 1 KiB, N_W per issuing wave) into the next ring slot;
+  // the stream runs over item boundaries and, past the last item, wraps to this workgroup's first one (harmless)
   __device__ __forceinline__ void issue_w() {
     const unsigned so = (unsigned)(((wl_item % NS) * NCHUNK + wl_chunk) * (WCH * 4) + wave * 1024);
     const unsigned l0 = lds_w + st_slot * (WCH * 4) + wave * 1024;
     unsigned saved_m0;
+    if constexpr (ROLE == Role::Issuer)
+      asm volatile(
+          "s_mov_b32 %0, m0\n\t"
+          "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %6, %7 offen lds\n\t"
+          "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %6, %8 offen lds\n\t"
+          "s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %6, %9 offen lds\n\t"
+          "s_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %6, %10 offen lds\n\t"
+          "s_mov_b32 m0, %0"
+          : "=&s"(saved_m0)
+          : "s"(l0), "s"(l0 + 4096u), "s"(l0 + 8192u), "s"(l0 + 12288u), "v"(w_voff), "s"(w_rsrc), "s"(so), "s"(so + 4096u),
+            "s"(so + 8192u), "s"(so + 12288u)
+          : "memory");
+    else
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
         "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %5 offen lds\n\t"

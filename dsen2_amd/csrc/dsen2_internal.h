@@ -56,18 +56,20 @@ struct ConvParams {
 // First: Direct = conv3x3_first.hip / conv3x3_first16.hip where they take the band groups, else the tile kernel issuing the
 // MFMAs of the 10 / 12 real channels only; Tile16 = the tile kernel over all 16 padded channels.  Body (fp32 F->F):
 // conv3x3_body32.hip, or one tile per workgroup (conv3x3_mfma.hip, the independent first implementation).  Body32Form:
-// DeferStagger = deferred epilogue + wave-group stagger for both convolutions (the product's, the only one outside DSEN2_DIAG
-// builds); DeferStaggerA = conv-B not staggered; StaggerA = no deferral: conv-A staggered, conv-B with the whole residual tile
-// prefetched under the last step; Plain = StaggerA without the stagger.  Out (Cout <= 8): conv3x3_out_mfma.hip where the shape
+// DeferStagger = deferred epilogue + wave-group stagger for both convolutions; DeferStaggerA = conv-B not staggered;
+// StaggerA = no deferral: conv-A staggered, conv-B with the whole residual tile prefetched under the last step; Plain = StaggerA without the stagger; DeferAsym = deferred epilogue, waves 0-3 issue every
+// DMA, half a step into the step, and waves 4-7 none (conv3x3_dma.h, Role::Issuer): the product's at both widths and the only
+// one outside DSEN2_DIAG builds (profiles/body32_asym.md); DeferAsymS0 / S1 / S3 / DeferAsymPrio = its measured alternatives
+// (the issuers' DMAs at another k-step / waves 4-7 at s_setprio 1).  Out (Cout <= 8): conv3x3_out_mfma.hip where the shape
 // fits it, else conv3x3_out.hip; always conv3x3_out.hip; Tile (and Cout > 8) = padded 32-wide block of conv3x3_mfma.hip.
 enum class FirstKernel { Direct, Tile16 };
 enum class BodyKernel { Body32, Tile };
-enum class Body32Form { StaggerA, Plain, DeferStaggerA, DeferStagger };
+enum class Body32Form { StaggerA, Plain, DeferStaggerA, DeferStagger, DeferAsym, DeferAsymS0, DeferAsymS1, DeferAsymS3, DeferAsymPrio };
 enum class OutKernel { MfmaThenValu, Valu, Tile };
 struct Tuning {
   FirstKernel first = FirstKernel::Direct;
   BodyKernel body = BodyKernel::Body32;
-  Body32Form body32 = Body32Form::DeferStagger;
+  Body32Form body32 = Body32Form::DeferAsym;
   OutKernel out = OutKernel::MfmaThenValu;
   int ablate = 0;          // timing-only ablation mask of the persistent body kernels (DSEN2_DIAG builds; wrong outputs)
   int grid_cap = 0;        // DSEN2_DIAG builds: launch at most this many workgroups of the bf16 body kernel (0 = one per CU)

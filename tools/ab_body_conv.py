@@ -3,10 +3,11 @@
 Needs the DIAGNOSTIC library (the product library has no structure switch):
 
     python -m dsen2_amd.build --diag
-    DSEN2_HIP_LIB=build/libdsen2_hip_diag.so python tools/ab_body_conv.py [--variants 0,11,12,13,14] [--rounds 5] [--batch 512]
+    DSEN2_HIP_LIB=build/libdsen2_hip_diag.so python tools/ab_body_conv.py [--variants 0,11,12,13,14,15] [--rounds 5] [--batch 512] [--feat 128] [--hw 32]
 
-14 = default (conv3x3_body32.hip: deferred epilogue + wave-group stagger), 11-13 its sub-variants, 0 = one tile per
-workgroup (conv3x3_mfma.hip).
+14 = conv3x3_body32.hip with the deferred epilogue + wave-group stagger, 11-13 its sub-variants, 15 = deferred epilogue with
+waves 0-3 issuing every DMA, half a step into the step (the default), 16-18 = 15 with the issuers' DMAs at k-step
+0, 1, 3 of the step, 19 = 15 with waves 4-7 at s_setprio 1, 0 = one tile per workgroup (conv3x3_mfma.hip).
 """
 import argparse
 import json
@@ -26,21 +27,23 @@ ap.add_argument('--rounds', type=int, default=5)
 ap.add_argument('--batch', type=int, default=512)
 ap.add_argument('--hw', type=int, default=32)
 ap.add_argument('--iters', type=int, default=10)
+ap.add_argument('--feat', type=int, default=128)
 args = ap.parse_args()
 variants = [int(v) for v in args.variants.split(',')]
 
-flat = W.random_he_uniform(10, 6, 6, 128, seed=1, bias_scale=0.05)
+F = args.feat
+flat = W.random_he_uniform(10, 6, 6, F, seed=1, bias_scale=0.05)
 models = {}
 for v in variants:
     _lib.diag_set(0, v)
-    m = s2model(((4, None, None), (6, None, None)), num_layers=6, feature_size=128)
+    m = s2model(((4, None, None), (6, None, None)), num_layers=6, feature_size=F)
     m.set_weights_flat(flat)
     models[v] = m
 _lib.diag_set(0, 14)
 
 B, H = args.batch, args.hw
-a = torch.randn((B, H, H, 128), device='cuda')
-r = torch.randn((B, H, H, 128), device='cuda')
+a = torch.randn((B, H, H, F), device='cuda')
+r = torch.randn((B, H, H, F), device='cuda')
 outs = {}
 for v, m in models.items():
     o = torch.empty_like(a)
@@ -52,7 +55,7 @@ for v in variants[1:]:
     print('variant %d max|diff| vs variant %d: %.3e' % (v, variants[0], d))
     assert d < 1e-4
 
-flops = B * H * H * 2 * 9 * 128 * 128
+flops = B * H * H * 2 * 9 * F * F
 times = {v: {'relu': [], 'res': []} for v in variants}
 o = torch.empty_like(a)
 for _ in range(args.rounds):

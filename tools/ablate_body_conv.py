@@ -4,9 +4,11 @@ Masks: 1 no stores, 2 no residual loads, 4 no weight stream, 8 no input stream, 
 by construction).  Needs the DIAGNOSTIC library:
 
     python -m dsen2_amd.build --diag
-    DSEN2_HIP_LIB=build/libdsen2_hip_diag.so python tools/ablate_body_conv.py [fp32|bf16]
+    DSEN2_HIP_LIB=build/libdsen2_hip_diag.so python tools/ablate_body_conv.py [fp32|bf16|15]
 
-fp32: conv3x3_body32.hip at F=128, batch 512; bf16: conv3x3_body16w.hip at F=256, batch 256 (32x32 patches).
+fp32: conv3x3_body32.hip at F=128, batch 512 (mask 0 = variant 14, the other masks the form without deferral or stagger);
+15: variant 15 of that kernel (waves 0-3 issue every DMA), masks 0, 3, 15 and 16 of that very form;
+bf16: conv3x3_body16w.hip at F=256, batch 256 (32x32 patches).
 A model copies the mask when it is created, so there is one model per mask."""
 import json
 import os
@@ -20,9 +22,12 @@ from dsen2_amd import _lib, weights as W          # noqa: E402
 from dsen2_amd.DSen2Net import s2model            # noqa: E402
 
 bf = len(sys.argv) > 1 and sys.argv[1] == 'bf16'
+asym = len(sys.argv) > 1 and sys.argv[1] == '15'
 F, B, H, D = (256, 256, 32, 3) if bf else (128, 512, 32, 2)
 flat = W.random_he_uniform(10, 6, D, F, seed=1)
-masks = ([int(m) for m in os.environ['ABLATE_MASKS'].split(',')] if os.environ.get('ABLATE_MASKS') else [0, 1, 3, 4, 8, 12, 15, 16, 31]) if bf else [0, 1, 2, 3, 4, 8, 12, 15, 16, 31]
+masks = ([int(m) for m in os.environ['ABLATE_MASKS'].split(',')] if os.environ.get('ABLATE_MASKS') else [0, 1, 3, 4, 8, 12, 15, 16, 31]) if bf else [0, 3, 15, 16] if asym else [0, 1, 2, 3, 4, 8, 12, 15, 16, 31]
+if not bf:
+    _lib.diag_set(0, 15 if asym else 14)
 models = {}
 for k in masks:
     _lib.diag_set(1, k)

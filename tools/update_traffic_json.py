@@ -7,7 +7,7 @@ the hash of the instruction stream it was measured on.
 (output.json: default profiles/body_conv_traffic.json, updated in place; tools/profile_round.sh on the GPU box writes
 gpurun_out/<tag>/body_conv_traffic.json — the repo's file with this config's entry replaced — to be copied over it.)
 
-<pmc summary> = what tools/summarize_pmc.py wrote from the separate `rocprofv3 --kernel-trace --pmc FETCH_SIZE` /
+<pmc summary> = what tools/summarize_pmc.py wrote from the separate `rocprofv3 --pmc FETCH_SIZE` /
 `--pmc WRITE_SIZE` passes of tools/profile_round.sh (mean per dispatch, KiB).  Corrections as MI355X_MICROARCH.md §HBM
 prescribes for gfx950: FETCH_SIZE is doubled (it under-reports 16-byte-per-lane reads by 2), WRITE_SIZE is taken as it is;
 both are in KiB.  `isa_sha256` comes from dsen2_amd/kernel_isa.json (written by the product build from the ISA it has just
