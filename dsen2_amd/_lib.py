@@ -99,6 +99,8 @@ SIGNATURES = {
     'dsen2_tile_nodata': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'dsen2_recompose_rows_nodata': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                             ctypes.c_float, c_int, c_int, c_void_p]),
+    'dsen2_recompose_rows_blend': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                           ctypes.c_float, c_int, c_int, c_void_p]),
     'dsen2_corpus_create': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
     'dsen2_corpus_destroy': (None, [c_void_p]),
     'dsen2_corpus_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -5,7 +5,7 @@
                                   [--roi_lon_lat lon1,lat1,lon2,lat2] [--list_bands] [--list_UTM]
                                   [--list_output_file_formats]
                                   [--bands10 B4,B3,B2,B8] [--models DIR] [--precision fp32|bf16|bf16x3] [--deep]
-                                  [--self_ensemble] [--skip_nodata]
+                                  [--self_ensemble] [--skip_nodata] [--border20 B] [--border60 B] [--feather F]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         -m dsen2_amd.cli INPUT [OUTPUT] ...                       one process per GPU: the patches of the tile are
         sharded over the ranks (dsen2_amd/dist.py: RCCL over xGMI), rank 0 receives the predictions, recomposes
@@ -342,6 +342,14 @@ def main(argv=None):
     ap.add_argument('--skip_nodata', action='store_true',
                     help='no-data in, no-data out: a 10 m pixel that is 0 in every band is written as 0 in every super-resolved band, '
                          'and patches without any data are not computed')
+    ap.add_argument('--border20', type=int, default=None, metavar='B',
+                    help='overlap of neighbouring 128-pixel patches of the 20 m path in 10 m pixels: a multiple of 2 up to 32 (default 8, '
+                         'the reference)')
+    ap.add_argument('--border60', type=int, default=None, metavar='B',
+                    help='overlap of neighbouring 192-pixel patches of the 60 m path: a multiple of 6 up to 48 (default 12, the reference)')
+    ap.add_argument('--feather', type=int, default=None, metavar='F',
+                    help='blend neighbouring patches across F pixels either side of every seam, 1 <= F <= border (default 0: the '
+                         "reference's hard cut)")
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='under torch.distributed.run: nccl = RCCL, one GPU per rank; gloo = rehearsal with shared GPUs')
     args = ap.parse_args(argv)
@@ -388,6 +396,12 @@ def _run(args):
         supres.SELF_ENSEMBLE = True
     if args.skip_nodata:
         supres.SKIP_NODATA = True
+    if args.border20 is not None:
+        supres.BORDER_20 = args.border20
+    if args.border60 is not None:
+        supres.BORDER_60 = args.border60
+    if args.feather is not None:
+        supres.FEATHER = args.feather or None
 
     roi = [float(v) for v in re.split(',', args.roi_x_y)] if args.roi_x_y else None
     product = None

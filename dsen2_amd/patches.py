@@ -4,7 +4,7 @@ Same function names, arguments, defaults, return types and quirks as the referen
   interp_patches(image_20, image_10_shape)                              utils/patches.py:11-16
   get_test_patches(dset_10, dset_20, patchSize=128, border=4, interp)   utils/patches.py:19-80
   get_test_patches60(dset_10, dset_20, dset_60, patchSize=128, border=8, interp)   :83-156
-  recompose_images(a, border, size=None)                                utils/patches.py:374-405
+  recompose_images(a, border, size=None)                                utils/patches.py:374-405  (+ feather=)
 and of its training-set half (python -m dsen2_amd.create_patches):
   downPixelAggr(img, SCALE=2)                                           utils/patches.py:353-371
   save_test_patches / save_test_patches60(..., file, ...)               utils/patches.py:159-178
@@ -17,6 +17,7 @@ up-sampling and the recomposition are HIP kernels behind the C ABI (include/dsen
 O(#patches) origin arithmetic runs on the host.
 """
 import ctypes
+import inspect
 import json
 import random
 from math import ceil
@@ -279,6 +280,54 @@ def final_row_runs_slots(slot_of_patch, slots_done, per, done_rows, size, inner)
     return final_row_runs(have, done_rows, size, inner)
 
 
+# ---- feathered blend (not in the reference; csrc/recompose_blend.hip) -----------------------------
+def feather_width(feather, border):
+    """The `feather` argument of the recomposition as an int: None, False or 0 -> 0 (the reference's hard cut), True -> border,
+    an int in 1..border -> itself; ValueError for anything else."""
+    if feather is None or feather is False or (not isinstance(feather, bool) and isinstance(feather, (int, np.integer)) and feather == 0):
+        return 0
+    if feather is True:
+        feather = border
+    if not isinstance(feather, (int, np.integer)) or not 1 <= feather <= border:
+        raise ValueError('feather must be None, a bool or an int in 1..border = 1..%d, got %r' % (border, feather))
+    return int(feather)
+
+
+def blend_row_support(ty, size, inner, feather):
+    """Image rows [r0, r1) on which tile row ty carries weight in the blend: [s - feather, s + inner + feather) cut to the image,
+    s = ty * inner, the last tile row's start clamped to H - inner (include/dsen2_hip.h, "feathered recomposition")."""
+    H = int(size[0])
+    y_tiles = recompose_grid(size, inner, 0)[1]
+    s = H - inner if ty == y_tiles - 1 else int(ty) * inner
+    return max(0, s - feather), min(H, s + inner + feather)
+
+
+def final_row_runs_blend(have, done_rows, size, inner, feather):
+    """final_row_runs for the blend: an image row is final once EVERY tile row whose support (blend_row_support) holds it is
+    complete.  `have` as in final_row_runs; `done_rows`: bool per IMAGE ROW, rows already recomposed (updated in place).  Returns
+    merged [(row0, row1)] runs in ascending order."""
+    H = int(size[0])
+    x_tiles, y_tiles = recompose_grid(size, inner, 0)
+    complete = np.asarray(have[:x_tiles * y_tiles], bool).reshape(y_tiles, x_tiles).all(axis=1)
+    final = ~done_rows
+    for ty in np.nonzero(~complete)[0]:
+        r0, r1 = blend_row_support(int(ty), size, inner, feather)
+        final[r0:r1] = False
+    edges = np.flatnonzero(np.diff(np.concatenate(([0], final.astype(np.int8), [0]))))
+    done_rows |= final
+    return [(int(a), int(b)) for a, b in zip(edges[0::2], edges[1::2])]
+
+
+def final_row_runs_slots_blend(slot_of_patch, slots_done, per, done_rows, size, inner, feather):
+    """final_row_runs_slots for the blend (`done_rows` per image row): a patch without a slot carries no weight and is final from
+    the start."""
+    slot = np.asarray(slot_of_patch)
+    have = slot < 0
+    if per > 0:
+        have = have | ((slot >= 0) & (slot % per < slots_done))
+    return final_row_runs_blend(have, done_rows, size, inner, feather)
+
+
 # ---- no-data (not in the reference; csrc/nodata.hip) ---------------------------------------------
 def nodata_geometry(size, patch, border):
     """(x_tiles, y_tiles, bitmap_words) of dsen2_tile_nodata_geometry: host only; DSen2Error for a geometry the recomposition
@@ -315,24 +364,30 @@ def slot_map(patch_empty):
     return kept, slot_of_patch
 
 
-def recompose_device(a_dev, border, size, scale=1.0):
-    """[N,C,P,P] CUDA tensor -> [size0,size1,C] CUDA tensor (N > 1)."""
+def recompose_device(a_dev, border, size, scale=1.0, feather=None):
+    """[N,C,P,P] CUDA tensor -> [size0,size1,C] CUDA tensor (N > 1).  feather: see recompose_rows_device."""
     n, c, p, _ = a_dev.shape
     H, W = int(size[0]), int(size[1])
     img = torch.empty((H, W, c), dtype=torch.float32, device=a_dev.device)
+    if feather_width(feather, border):
+        recompose_rows_device(a_dev, border, img, 0, H, scale=scale, feather=feather)
+        return img
     with torch.cuda.device(a_dev.device):
         _lib.call('dsen2_recompose', _ptr(a_dev), n, c, p, border, _ptr(img), H, W, float(scale),
                   _stream(a_dev.device))
     return img
 
 
-def recompose_rows_device(a_dev, border, img, row0, row1, scale=1.0, slots=None, valid_bits=None):
+def recompose_rows_device(a_dev, border, img, row0, row1, scale=1.0, slots=None, valid_bits=None, feather=None):
     """Rows [row0, row1) of `img` ([H,W,C] CUDA tensor) from the patch buffer a_dev [N,C,P,P] (dsen2_recompose_rows): only the
     patches those rows read need to be final.  slots (int32 device tensor, patch index -> index in a_dev or -1: `slot_map`) and
     valid_bits (`nodata_device`), given together: a_dev is the compact buffer of the kept patches, and a pixel without data, or
-    whose patch has no slot in a_dev, becomes 0 (dsen2_recompose_rows_nodata)."""
+    whose patch has no slot in a_dev, becomes 0 (dsen2_recompose_rows_nodata).  feather (None, False or 0: the hard cut; True:
+    border; 1..border): the patches are blended across `feather` pixels either side of every seam instead
+    (dsen2_recompose_rows_blend), with or without the two maps."""
     n, c, p, _ = a_dev.shape
     H, W = int(img.shape[0]), int(img.shape[1])
+    feather = feather_width(feather, border)
     if (slots is None) != (valid_bits is None):
         raise ValueError('slots and valid_bits go together')
     if slots is not None:
@@ -342,8 +397,15 @@ def recompose_rows_device(a_dev, border, img, row0, row1, scale=1.0, slots=None,
         if slots.numel() != xt * yt or valid_bits.numel() != words:
             raise ValueError('slot map of %d entries and bitmap of %d words for a %d x %d grid and %d words'
                              % (slots.numel(), valid_bits.numel(), yt, xt, words))
-        if int(img.shape[2]) != c:
-            raise ValueError('image of %d channels for patches of %d' % (int(img.shape[2]), c))
+    if (slots is not None or feather) and int(img.shape[2]) != c:
+        raise ValueError('image of %d channels for patches of %d' % (int(img.shape[2]), c))
+    if feather:
+        with torch.cuda.device(img.device):
+            _lib.call('dsen2_recompose_rows_blend', _ptr(a_dev) if n else None, n, c, p, border, feather,
+                      _ptr(slots) if slots is not None else None, _ptr(valid_bits) if slots is not None else None, _ptr(img), H, W,
+                      float(scale), int(row0), int(row1), _stream(img.device))
+        return
+    if slots is not None:
         with torch.cuda.device(img.device):
             _lib.call('dsen2_recompose_rows_nodata', _ptr(a_dev) if n else None, n, c, p, border, _ptr(slots), _ptr(valid_bits),
                       _ptr(img), H, W, float(scale), int(row0), int(row1), _stream(img.device))
@@ -353,15 +415,23 @@ def recompose_rows_device(a_dev, border, img, row0, row1, scale=1.0, slots=None,
                   _stream(a_dev.device))
 
 
-def recompose_images(a, border, size=None):
-    """utils/patches.py:374-405 — including the single-patch shortcut (:375-376) and the shape print (:392)."""
+def recompose_images(a, border, size=None, *, feather=None):
+    """utils/patches.py:374-405 — including the single-patch shortcut (:375-376) and the shape print (:392).  feather (keyword
+    only, not in the reference and not part of the reported signature; see recompose_rows_device): a blend across the seams
+    instead of the hard cut; the single-patch shortcut stays."""
     if a.shape[0] == 1:
         images = np.asarray(a[0]) if not isinstance(a, torch.Tensor) else a[0].cpu().numpy()
         return images.transpose((1, 2, 0))
+    feather_width(feather, border)              # a bad value is refused before anything reaches the GPU
     dev = default_device()
     x = _to_device_f32(a, dev)
     print((a.shape[1], size[0], size[1]))
-    return recompose_device(x, border, size).cpu().numpy()
+    return recompose_device(x, border, size, feather=feather).cpu().numpy()
+
+
+# inspect.signature() reports the reference's parameters alone, as for supres.DSen2_20 / DSen2_60
+recompose_images.__signature__ = inspect.Signature([p for p in inspect.signature(recompose_images).parameters.values()
+                                                    if p.name != 'feather'])
 
 
 # ---- training-set creation (utils/patches.py:159-271, :353-371) --------------------------------

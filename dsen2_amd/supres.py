@@ -43,6 +43,28 @@ SELF_ENSEMBLE = os.environ.get('DSEN2_SELF_ENSEMBLE', '0') not in ('', '0')
 # (csrc/nodata.hip); everywhere else the image is the one the option off returns, bit for bit.  Default off.
 SKIP_NODATA = os.environ.get('DSEN2_SKIP_NODATA', '0') not in ('', '0')
 
+
+def _env_int(name, default):
+    v = os.environ.get(name, '')
+    return int(v) if v.strip() else default
+
+
+def _env_feather(v):
+    v = v.strip().lower()
+    if v in ('', '0', 'false', 'off', 'none'):
+        return None
+    return True if v in ('true', 'on', 'border') else int(v)
+
+
+# Nor these: the overlap of neighbouring patches and what happens in it.  BORDER_20 / BORDER_60 replace the reference's 8 / 12
+# pixels (testing/supres.py:22,41; a multiple of 2 / 6, at most a quarter of the patch of 128 / 192, which keeps its size: a wider
+# border means more patches).  FEATHER: None = the reference's hard cut ("the last tile wins"); F in 1..border, or True = border,
+# blends neighbouring predictions across F pixels either side of every seam (csrc/recompose_blend.hip).  The
+# defaults are the reference's image, bit for bit.
+BORDER_20 = _env_int('DSEN2_BORDER_20', 8)
+BORDER_60 = _env_int('DSEN2_BORDER_60', 12)
+FEATHER = _env_feather(os.environ.get('DSEN2_FEATHER', ''))
+
 _MODEL_CACHE = {}
 _LAST_RUN = {}
 
@@ -191,11 +213,14 @@ class RowSink(object):
         with torch.cuda.stream(self.stream):
             yield
 
-    def rows(self, src_patches, border, r0, r1):
+    def rows(self, src_patches, border, r0, r1, feather=0):
         """Image rows [r0, r1) from the patch buffer (whole patches with their border, or inner crops with border 0: they tile
-        alike, patches.py:380-403), on the current stream; `images *= SCALE` (supres.py:29) folded into the recomposition."""
+        alike, patches.py:380-403), on the current stream; `images *= SCALE` (supres.py:29) folded into the recomposition.
+        feather > 0: the blend (whole patches with (border, feather), or crops of side inner + 2 * feather with (feather,
+        feather): the same weights on the same values)."""
         slots, bits = self.nodata if self.nodata is not None else (None, None)
-        _patches.recompose_rows_device(src_patches, border, self.img, r0, r1, scale=SCALE, slots=slots, valid_bits=bits)
+        _patches.recompose_rows_device(src_patches, border, self.img, r0, r1, scale=SCALE, slots=slots, valid_bits=bits,
+                                       feather=feather)
         if self.stream is not None:
             if self.host is not None:
                 self.host[r0:r1].copy_(self.img[r0:r1], non_blocking=True)
@@ -220,14 +245,28 @@ class RowSink(object):
         return self.host.numpy() if self.host is not None else self.img.cpu().numpy()
 
 
-def _final_bands(slots_done, per, done_rows, size, inner, slot_of_patch=None):
+def _final_bands(slots_done, per, done_rows, size, inner, slot_of_patch=None, feather=0):
     """[(r0, r1)] image rows that became final now that the first `slots_done` slots of every shard of `per` patches are
     there (one rank: per = all patches, slots_done = patches computed so far); `done_rows` as in patches.final_row_runs.
-    slot_of_patch (SKIP_NODATA): the shards hold the kept patches only, and an empty patch is final from the start."""
+    slot_of_patch (SKIP_NODATA): the shards hold the kept patches only, and an empty patch is final from the start.
+    feather > 0: a row waits for every tile row that carries weight on it, and `done_rows` is per image row
+    (patches.final_row_runs_blend)."""
+    x_tiles, y_tiles = _patches.recompose_grid(size, inner, 0)
+    if feather:
+        if slot_of_patch is not None:
+            return _patches.final_row_runs_slots_blend(slot_of_patch, slots_done, per, done_rows, size, inner, feather)
+        return _patches.final_row_runs_blend(np.arange(x_tiles * y_tiles) % per < slots_done, done_rows, size, inner, feather)
     if slot_of_patch is not None:
         return _patches.final_row_runs_slots(slot_of_patch, slots_done, per, done_rows, size, inner)
-    x_tiles = _patches.recompose_grid(size, inner, 0)[0]
-    return _patches.final_row_runs(np.arange(x_tiles * done_rows.size) % per < slots_done, done_rows, size, inner)
+    return _patches.final_row_runs(np.arange(x_tiles * y_tiles) % per < slots_done, done_rows, size, inner)
+
+
+def _check_overlap(patch, ratio, border, feather):
+    """(border, feather width) of a call, or ValueError: border a multiple of `ratio` (the patch origins lie on the lowest
+    resolution's grid) in 1..patch/4, feather None / False / 0 (off), True (= border) or 1..border."""
+    if isinstance(border, bool) or not isinstance(border, (int, np.integer)) or border % ratio or not 1 <= border <= patch // 4:
+        raise ValueError('border must be a multiple of %d in %d..%d for patches of %d, got %r' % (ratio, ratio, patch // 4, patch, border))
+    return int(border), _patches.feather_width(feather, int(border))
 
 
 def _chunked_gather_wanted():
@@ -250,7 +289,8 @@ def _nodata_plan(d10_dev, patch, border, used):
     return kept, slot_of_patch, (torch.from_numpy(slot_of_patch).to(d10_dev.device), bits)
 
 
-def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None):
+def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None, feather=None):
+    border, feather = _check_overlap(patch, scales[0], border, feather)            # before anything touches the GPU
     skip_nodata = SKIP_NODATA if skip_nodata is None else bool(skip_nodata)
     _patches.check_sizes(dsets, scales)
     dev = _patches.default_device()
@@ -290,20 +330,23 @@ def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None):
     # this rank's contiguous share of the USED patches (the reference's trailing all-zero patches are
     # never read by recompose_images, so they are not computed)
     first, count = _dist.shard_range(used)
-    done_rows = np.zeros(_patches.recompose_grid(size, patch, border)[1], bool)
+    # what is already recomposed: per tile row, or, for the blend, per image row (_final_bands)
+    done_rows = np.zeros(shape[0] if feather else _patches.recompose_grid(size, patch, border)[1], bool)
     # Where this rank's predictions go and who feeds the sink.  One rank (or the single patch): whole patches; a large image
-    # leaves in bands, each right after the batch that completes its rows.  Several ranks: the inner crops, in the [per, ...]
+    # leaves in bands, each right after the batch that completes its rows.  Several ranks: the inner crops (for the blend: the
+    # crops of side inner + 2 * feather, everything that carries weight, recomposed with border = feather), in the [per, ...]
     # buffer the gather sends as it is (2.95 GB for a 10980^2 tile over all ranks instead of 3.85 GB of whole patches to EVERY
     # rank): one gather at the end, or, with DSEN2_CHUNKED_GATHER=1, DSEN2_GATHER_CHUNKS (8) pieces that travel while the
     # shards still compute (dist.ChunkedGather; off by default until an N > 1 box has measured RCCL's kernels
     # next to two CU-filling persistent ones).  The image is the same.
     pred = send = cg = sink = None
+    crop, sent_border = border - feather, feather            # what a rank cuts off a prediction, and the border of what it sends
     banded, issued = False, 0
     if world == 1 or single:
         pred = torch.empty((count, cout, patch, patch), dtype=torch.float32, device=dev)
         banded = not single and _pinned_wanted(shape) and os.environ.get('DSEN2_BANDED_OUTPUT', '1') != '0'
     else:
-        send = torch.empty((_dist.per_rank(used, world), cout, inner, inner), dtype=torch.float32, device=dev)
+        send = torch.empty((_dist.per_rank(used, world), cout, patch - 2 * crop, patch - 2 * crop), dtype=torch.float32, device=dev)
         if _chunked_gather_wanted():
             cg = _dist.ChunkedGather(send, used, _gather_chunks())
             if rank == 0:
@@ -320,11 +363,11 @@ def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None):
             if send is None:
                 forward(xs, out=pred[i0:i0 + n])
                 if banded:
-                    for r0, r1 in _final_bands(i0 + n, used, done_rows, size, inner, slot_of_patch):
-                        sink.rows(pred, border, r0, r1)
+                    for r0, r1 in _final_bands(i0 + n, used, done_rows, size, inner, slot_of_patch, feather):
+                        sink.rows(pred, border, r0, r1, feather)
             else:
                 y = forward(xs)
-                send[i0:i0 + n].copy_(y[:, :, border:patch - border, border:patch - border])
+                send[i0:i0 + n].copy_(y[:, :, crop:patch - crop, crop:patch - crop])
                 # a piece whose slots this rank has all written (a short shard: all it will ever write) goes out now
                 while cg is not None and issued < cg.n_chunks and i0 + n >= min(cg.bounds[issued][1], count):
                     cg.issue(issued)
@@ -348,40 +391,44 @@ def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None):
         with sink.tail():
             for c in range(cg.n_chunks):
                 cg.complete(c)                                         # this stream waits for gather c
-                for r0, r1 in _final_bands(cg.slots_done(c), cg.per, done_rows, size, inner, slot_of_patch):
-                    sink.rows(cg.recv, 0, r0, r1)
+                for r0, r1 in _final_bands(cg.slots_done(c), cg.per, done_rows, size, inner, slot_of_patch, feather):
+                    sink.rows(cg.recv, sent_border, r0, r1, feather)
             assert done_rows.all()
             return sink.finish()
     if world > 1:
         # gather to root: rank 0 receives every rank's inner crops into views of one buffer; the other ranks return None —
         # no page-locked buffer, no download, nothing received
-        pred, border = _dist.gather_to_root(send, used), 0
+        pred, border = _dist.gather_to_root(send, used), sent_border
         if rank != 0:
             return None
     print((cout, size[0], size[1]))                                    # patches.py:392
     if sink is None:                 # not in bands: the whole image in one
         sink = RowSink(shape, dev, nodata=nodata)
-        sink.rows(pred, border, 0, shape[0])
+        sink.rows(pred, border, 0, shape[0], feather)
     return sink.finish()
 
 
+_EXTENSIONS = ('skip_nodata', 'border', 'feather')
+
+
 def _reference_surface(fn):
-    """fn(<the reference's parameters>, skip_nodata=None) as the public function: `skip_nodata` is taken BY KEYWORD ONLY, and
-    inspect.signature() reports the reference's parameters alone (testing/supres.py:15,33) — callers and tools that bind or
-    compare the drop-in surface by introspection see exactly the reference's; the option is this project's extension."""
+    """fn(<the reference's parameters>, skip_nodata=None, border=None, feather=None) as the public function: this project's
+    options (_EXTENSIONS) are taken BY KEYWORD ONLY, and inspect.signature() reports the reference's parameters alone
+    (testing/supres.py:15,33) — callers and tools that bind or compare the drop-in surface by introspection see exactly the
+    reference's."""
     sig = inspect.signature(fn)
-    reference = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != 'skip_nodata'])
+    reference = sig.replace(parameters=[p for p in sig.parameters.values() if p.name not in _EXTENSIONS])
 
     @functools.wraps(fn)
-    def call(*args, skip_nodata=None, **kwargs):
+    def call(*args, skip_nodata=None, border=None, feather=None, **kwargs):
         bound = reference.bind(*args, **kwargs)           # TypeError for anything the reference's signature would refuse
-        return fn(*bound.args, skip_nodata=skip_nodata, **bound.kwargs)
+        return fn(*bound.args, skip_nodata=skip_nodata, border=border, feather=feather, **bound.kwargs)
     call.__signature__ = reference
     return call
 
 
 @_reference_surface
-def DSen2_20(d10, d20, deep=False, skip_nodata=None):
+def DSen2_20(d10, d20, deep=False, skip_nodata=None, border=None, feather=None):
     """20 m -> 10 m.  d10 [x, y, 4] (B2 B3 B4 B8), d20 [x/2, y/2, 6] (B5 B6 B7 B8A B11 B12), any real dtype, HWC.
     deep=True selects VDSen2 (d=32, F=256).  Returns [x, y, 6] float32.  Geometry of testing/supres.py:21-22:
     patches of 128 with an 8-pixel border.
@@ -392,13 +439,20 @@ def DSen2_20(d10, d20, deep=False, skip_nodata=None):
     (testing/s2_tiles_supres.py:346-348) is what a non-root rank then takes.
 
     skip_nodata (keyword only, not in the reference and not part of the reported signature; None = supres.SKIP_NODATA): a pixel of d10 whose bands are all exactly 0 is returned
-    as 0 in every band, and patches that decide no pixel with data are not computed; all other pixels are unchanged, bit for bit."""
-    return _run([d10, d20], [2, 1], patch=128, border=8, deep=deep, run_60=False, skip_nodata=skip_nodata)
+    as 0 in every band, and patches that decide no pixel with data are not computed; all other pixels are unchanged, bit for bit.
+
+    border, feather (keyword only too; None = supres.BORDER_20 / BORDER_60 and supres.FEATHER): the overlap of neighbouring patches
+    in 10 m pixels (a multiple of 2 / 6, at most 32 / 48; the patch keeps its size, so a wider border means more patches) and
+    the width of the blend either side of every seam (1..border, True = border; None, False or 0 = the reference's hard cut).
+    ValueError for anything else, before the GPU is touched."""
+    return _run([d10, d20], [2, 1], patch=128, border=BORDER_20 if border is None else border, deep=deep, run_60=False,
+                skip_nodata=skip_nodata, feather=FEATHER if feather is None else feather)
 
 
 @_reference_surface
-def DSen2_60(d10, d20, d60, deep=False, skip_nodata=None):
+def DSen2_60(d10, d20, d60, deep=False, skip_nodata=None, border=None, feather=None):
     """60 m -> 10 m.  As DSen2_20 plus d60 [x/6, y/6, 2] (B1 B9; B10 is not super-resolved).  Returns [x, y, 2]
     float32.  Geometry of testing/supres.py:40-41: patches of 192 with a 12-pixel border.  Under torch.distributed: the
-    image on rank 0, None on every other rank (see DSen2_20).  skip_nodata: as DSen2_20."""
-    return _run([d10, d20, d60], [6, 3, 1], patch=192, border=12, deep=deep, run_60=True, skip_nodata=skip_nodata)
+    image on rank 0, None on every other rank (see DSen2_20).  skip_nodata, border, feather: as DSen2_20."""
+    return _run([d10, d20, d60], [6, 3, 1], patch=192, border=BORDER_60 if border is None else border, deep=deep, run_60=True,
+                skip_nodata=skip_nodata, feather=FEATHER if feather is None else feather)

@@ -144,7 +144,12 @@ def parse_args(argv=None):
                         '(default 5.0 = 10000 / 2000).')
     p.add_argument('--self_ensemble', action='store_true',
                    help='With --predict: average the predictions for the 8 flips and rotations of every patch (~8x the network time).')
+    p.add_argument('--feather', type=int, default=None, metavar='F',
+                   help='With --predict: blend neighbouring patches across F pixels either side of every seam when the image is '
+                        "recomposed, 1 <= F <= the border of the patch files (default: the reference's hard cut).")
     args = p.parse_args(argv)
+    if args.feather is not None and (not args.predict_file or args.feather < 1):
+        p.error('--feather F (F >= 1) is an option of --predict')
     if args.augment and args.predict_file:
         p.error('--augment is an option of training: it cannot be combined with --predict')
     if args.predict_file and (args.loss is not None or args.loss_param is not None or args.mask_nodata):
@@ -210,7 +215,11 @@ def predict(model, args, path):
             prediction = model.predict(train, batch_size=8, verbose=1, ensemble=True)
         else:
             prediction = model.predict(train, batch_size=8, verbose=1)
-        images = patches.recompose_images(prediction, border=border, size=(image_size[1], image_size[0]))     # (rows, columns): see above
+        size = (image_size[1], image_size[0])                                                                 # (rows, columns): see above
+        if args.feather:
+            images = patches.recompose_images(prediction, border=border, size=size, feather=args.feather)
+        else:
+            images = patches.recompose_images(prediction, border=border, size=size)
         print('Writing to file...')
         np.save(path + folder + dset + '/' + model_nr + '-predict', images * SCALE)
         print('Elapsed time: {}.'.format(time.time() - start))

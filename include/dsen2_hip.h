@@ -493,6 +493,31 @@ int dsen2_recompose_rows_nodata(const float *dev_patches, int slots, int C, int 
                                 const unsigned int *dev_valid_bits, float *dev_img, int H, int W, float scale, int row0, int row1,
                                 void *stream);
 
+/* ---- feathered recomposition: a weighted blend in the overlap of neighbouring patches (csrc/recompose_blend.hip) -------------------
+ * Not in the reference.  dsen2_recompose_rows with a blend in place of "the last patch wins".  The grid is dsen2_recompose's: along
+ * an axis of length L, inner = P - 2*border, T = ceil(L/inner), tile t starts at s_t = t*inner, the last one at L - inner; patch t
+ * covers image coordinates [s_t - border, s_t - border + P) (what falls outside [0, L) is padding and is never read).
+ *   WEIGHT   for u = x - (s_t - border) in [0, P):  w(u) = clamp(min(u + 1, P - u) - (border - feather), 0, 2*feather); a patch's
+ *            weight at a pixel is wy * wx, an integer.  It is positive on [s_t - feather, s_t + inner + feather) only.
+ *   OUTPUT   out[y][x][c] = float32( sum_k w_k * p_k[c] / sum_k w_k ) * scale: the sums over the patches with w_k > 0 in ascending
+ *            (ty, tx) order, a left fold that starts at its first term, products and sums in float64 (every product is exact), one
+ *            float64 division, one rounding to float32, then the float32 multiply by `scale` of dsen2_recompose.
+ *   Where one patch carries weight the pixel is that patch's value, bit for bit what dsen2_recompose_rows writes there; at most 3
+ *   patches per axis carry weight (3 where the clamped last tile reaches back over two neighbours).  The weights of (P, border,
+ *   feather) are those of (P - 2*(border - feather), feather, feather) on patches cropped by border - feather.
+ *   One thread per output pixel, no atomics: the image depends on the inputs alone, and any split of [0, H) into row bands gives
+ *   the bits of the whole-image call.
+ * dev_slot_of_patch and dev_valid_bits (dsen2_tile_nodata; both or neither): dev_patches is the compact buffer [slots,C,P,P]; a
+ *   pixel whose bit is 0 becomes 0.0f and reads nothing; a patch whose slot is outside [0, slots) has weight 0 and is never read; a
+ *   pixel left without any weighted patch becomes 0.0f.  slots may be 0 (dev_patches may then be NULL).  Without the maps
+ *   count_or_slots is the patch count of dsen2_recompose_rows (>= x_tiles*y_tiles).
+ * DSEN2_ERR_INVALID with nothing launched: the geometry dsen2_recompose_rows refuses (inner <= 0, H < inner, W < inner, too few
+ *   patches, a row range outside 0 <= row0 <= row1 <= H), border > P/4, feather outside 1..border, C < 1, a negative count, a NULL
+ *   pointer, one of the two maps without the other. */
+int dsen2_recompose_rows_blend(const float *dev_patches, int count_or_slots, int C, int P, int border, int feather,
+                               const int *dev_slot_of_patch, const unsigned int *dev_valid_bits, float *dev_img, int H, int W,
+                               float scale, int row0, int row1, void *stream);
+
 /* dsen2_down_pixel_aggr  <->  downPixelAggr                       utils/patches.py:353-371
  *   dev_img: one HWC image [H,W,C] of uint16 or float32 samples; writes the HWC image [H/scale, W/scale, C] as float32
  *   (out_f64 = 0) or float64 (1).  scipy.ndimage.gaussian_filter(band, 1/scale) + skimage block_reduce(np.mean), operation by
