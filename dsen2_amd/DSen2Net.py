@@ -904,6 +904,8 @@ class S2Model(object):
         permutations are those of the un-augmented fit.  Under data_parallel every rank draws the ops of the GLOBAL batch from
         the broadcast seed and takes its shard's slice.  Validation is never augmented."""
         from . import training
+        if getattr(y, 'class_masked', False) or (validation_data is not None and getattr(validation_data[1], 'class_masked', False)):
+            training.check_masked_target(self._loss_setting(), True, 'fit')
         plan = self._data_parallel_plan(data_parallel, emulate_world)
         x = [np.ascontiguousarray(a, dtype=np.float32) for a in x]
         y = np.ascontiguousarray(y, dtype=np.float32)
@@ -969,6 +971,8 @@ class S2Model(object):
         its samples, and the ranks' (sum |e|, sum e^2, elements) triples are all-gathered and added in rank order."""
         from . import training
         from .corpus import CorpusSampler
+        if getattr(corpus, 'class_masked', False):
+            training.check_masked_target(self._loss_setting(), True, 'fit_corpus')
         plan = self._data_parallel_plan(data_parallel, emulate_world)
         if plan is not None and shards is not None:
             raise ValueError('shards is the one-process cut of a batch: it cannot be combined with data_parallel')

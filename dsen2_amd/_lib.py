@@ -107,6 +107,10 @@ SIGNATURES = {
                                    c_void_p]),
     'dsen2_corpus_origin_mask': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p]),
+    'dsen2_class_valid_bits': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'dsen2_tile_flags_from_bits': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'dsen2_raster_apply_valid': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'dsen2_cells_from_valid_bits': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'dsen2_abs_sq_error_sums_workspace_bytes': (c_int, [ctypes.POINTER(c_size_t)]),
     'dsen2_abs_sq_error_sums': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_size_t, c_void_p, c_void_p]),
     'dsen2_model_set_loss': (c_int, [c_void_p, c_int, ctypes.c_float, c_int]),

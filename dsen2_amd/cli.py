@@ -6,6 +6,7 @@
                                   [--list_output_file_formats]
                                   [--bands10 B4,B3,B2,B8] [--models DIR] [--precision fp32|bf16|bf16x3] [--deep]
                                   [--self_ensemble] [--skip_nodata] [--border20 B] [--border60 B] [--feather F]
+                                  [--mask NAME_OR_FILE] [--mask_classes 0,1,3,8,9,10] [--mask_dilate N]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         -m dsen2_amd.cli INPUT [OUTPUT] ...                       one process per GPU: the patches of the tile are
         sharded over the ranks (dsen2_amd/dist.py: RCCL over xGMI), rank 0 receives the predictions, recomposes
@@ -99,6 +100,37 @@ def _load(path, lazy=False):
                                                         for k in ('im10', 'im20', 'im60')),
                                   'convert to .npz with keys data10/data20/data60')
     raise ValueError('unsupported input %r (use .npz or .mat)' % path)
+
+
+def load_mask(spec, data_file=None):
+    """The class raster of --mask: a .npy file, or — data_file being an array file — the key `spec` of the .npz, or the dataset
+    `spec` of the .mat (transposed like its images).  ValueError for anything else."""
+    if spec.lower().endswith('.npy'):
+        return np.load(spec)
+    ext = os.path.splitext(data_file)[1].lower() if data_file else ''
+    if ext == '.npz':
+        z = np.load(data_file)
+        if spec in z:
+            return z[spec]
+        raise ValueError('--mask %s: %s has no such key and it is not a .npy file' % (spec, data_file))
+    if ext == '.mat':
+        from . import hdf5_min
+        m = hdf5_min.read_with(data_file, lambda f: np.array(f[spec]).transpose() if spec in f else None,
+                               'save the mask as a .npy file')
+        if m is not None:
+            return m
+        raise ValueError('--mask %s: %s has no such dataset and it is not a .npy file' % (spec, data_file))
+    raise ValueError('--mask %s: with this input the mask must be a .npy file' % spec)
+
+
+def crop_mask(mask, size, xmin, ymin, xmax, ymax):
+    """The part of the class raster `mask` (on the 10, 20 or 60 m grid of a tile whose 10 m grid is `size`) that covers the 10 m
+    pixel region [ymin, ymax] x [xmin, xmax] (snap_roi: on 60 m boundaries)."""
+    from . import masks
+    up, down = masks.ratio(mask.shape, size)
+    if down > 1:
+        return mask[ymin * down:(ymax + 1) * down, xmin * down:(xmax + 1) * down]
+    return mask[ymin // up:-(-(ymax + 1) // up), xmin // up:-(-(xmax + 1) // up)]
 
 
 def snap_roi(x1, y1, x2, y2, width, height, step=6):
@@ -350,9 +382,28 @@ def main(argv=None):
     ap.add_argument('--feather', type=int, default=None, metavar='F',
                     help='blend neighbouring patches across F pixels either side of every seam, 1 <= F <= border (default 0: the '
                          "reference's hard cut)")
+    ap.add_argument('--mask', default=None, metavar='NAME_OR_FILE',
+                    help='a 2-D uint8 class raster on the 10, 20 or 60 m grid of the tile (Sentinel-2 SCL, cloud probability, ...): a key '
+                         'of the input .npz / .mat, or a .npy file.  A pixel of an invalid class is written as 0 in every '
+                         'super-resolved band, and patches without a valid pixel are not computed')
+    ap.add_argument('--mask_classes', default=None, metavar='C,C,...',
+                    help='with --mask: the class values that are invalid (default 0,1,3,8,9,10: SCL no data, saturated or defective, '
+                         'cloud shadow, cloud medium and high probability, thin cirrus)')
+    ap.add_argument('--mask_dilate', type=int, default=None, metavar='N',
+                    help='with --mask: grow the invalid area by N 10 m pixels, 0..32 (default 0)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='under torch.distributed.run: nccl = RCCL, one GPU per rank; gloo = rehearsal with shared GPUs')
     args = ap.parse_args(argv)
+    if args.mask is None and (args.mask_classes is not None or args.mask_dilate is not None):
+        ap.error('--mask_classes and --mask_dilate are options of --mask')
+    if args.mask_dilate is not None and not 0 <= args.mask_dilate <= 32:
+        ap.error('--mask_dilate N: N is in 10 m pixels, 0..32')
+    if args.mask is not None:
+        from . import masks
+        try:
+            args.mask_classes = masks.parse_classes(args.mask_classes)
+        except ValueError as e:
+            ap.error(str(e))
 
     if args.list_output_file_formats:                              # s2_tiles_supres.py:64-80: before anything is opened
         try:
@@ -406,6 +457,14 @@ def _run(args):
     roi = [float(v) for v in re.split(',', args.roi_x_y)] if args.roi_x_y else None
     product = None
     is_array = os.path.splitext(args.data_file)[1].lower() in ARRAY_EXTENSIONS
+    mask_kw = {}
+    if args.mask is not None:
+        try:
+            mask_kw = dict(mask=load_mask(args.mask, args.data_file if is_array else None), mask_classes=args.mask_classes,
+                           mask_dilate=args.mask_dilate or 0)
+        except (ValueError, IOError) as e:
+            print(e)
+            return 2
     if is_array:
         from . import dist as _dist
         data10, data20, data60 = _load(args.data_file, lazy=_dist.rank_world()[1] > 1)
@@ -434,6 +493,8 @@ def _run(args):
             if xmax < xmin or ymax < ymin:                         # smaller than one 60 m cell (s2_tiles_supres.py:196-198)
                 print('Invalid region of interest / UTM Zone combination')
                 return 0
+            if mask_kw:
+                mask_kw['mask'] = crop_mask(mask_kw['mask'], data10.shape[:2], xmin, ymin, xmax, ymax)
             data10 = data10[ymin:ymax + 1, xmin:xmax + 1]
             data20 = data20[ymin // 2:(ymax + 1) // 2, xmin // 2:(xmax + 1) // 2]
             if data60 is not None:
@@ -505,9 +566,9 @@ def _run(args):
     sr60 = None
     if args.run_60 and data60 is not None:
         print('Super-resolving the 60m data into 10m bands')
-        sr60 = supres.DSen2_60(data10, data20, data60, deep=args.deep)
+        sr60 = supres.DSen2_60(data10, data20, data60, deep=args.deep, **mask_kw)     # (without --mask: the call as it always was)
     print('Super-resolving the 20m data into 10m bands')
-    sr20 = supres.DSen2_20(data10, data20, deep=args.deep)
+    sr20 = supres.DSen2_20(data10, data20, deep=args.deep, **mask_kw)
     if isinstance(data10, LazyRows):
         sys.stderr.write('rank %d read %d of %d rows of the 10 m bands\n' % (_dist.rank_world()[0], data10.rows_read, data10.shape[0]))
     if sr20 is None:                                               # a rank other than 0 of a multi-GPU run

@@ -26,6 +26,12 @@ Opt-in: which origins may be drawn.  TileCorpus(skip_blank=True) / origin_masks(
 (dsen2_corpus_origin_mask, csrc/corpus_mask.hip), one bitmap of VALID origins per tile: an origin is valid when none of the 16 x 16
 cells of its crop is blank (a band-0 sample of the raw 10 m raster in the cell's footprint fails v >= 1) or lies within `margin`
 cells of a hold-out (validation) crop.  CorpusSampler(masks=) and validation_table(masks=) redraw what is not valid.
+
+Opt-in: class masks.  TileCorpus(class_masks=[raster or None per tile], mask_classes=, mask_dilate=) builds every masked tile's
+validity bitmap on the ground-truth grid (masks.valid_bits_device) and zeroes the ground truth there, once
+(dsen2_raster_apply_valid): to everything downstream — corpus.batch, the sampler, fit_corpus, validation — the masked pixels are
+no-data, which a model compiled with mask_nodata=True keeps out of every loss and gradient (fit_corpus refuses any other model).
+The low-resolution INPUTS are not touched.  skip_masked=True also ORs the mask into the blank map, so that no crop touches it.
 """
 import ctypes
 import sys
@@ -33,7 +39,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, patches, training
+from . import _lib, masks as masks_mod, patches, training
 
 PATCH_LR = 16                  # edge of a crop on the origin grid
 BANDS = (4, 6, 2)              # the Sentinel-2 band groups of the 10 m, 20 m and 60 m inputs
@@ -207,17 +213,34 @@ class TileCorpus(object):
     (origin_mask_device: a cell of the origin grid is blank when a BAND-0 sample of d10 in its footprint fails v >= 1, the
     reference's `chan3 < 1`; no other band and no other raster is looked at) and kept, one byte per cell, with a host copy of the
     packed bitmap of origins whose crops are free of blank cells (under 1 MB for a 10980^2 tile).  One line per tile is printed.
-    origin_masks() returns the bitmaps; CorpusSampler(masks=) and validation_table(masks=) draw from them."""
+    origin_masks() returns the bitmaps; CorpusSampler(masks=) and validation_table(masks=) draw from them.
 
-    def __init__(self, tiles, run_60=False, device=None, skip_blank=False):
+    class_masks (default None): one 2-D uint8 class raster (Sentinel-2's SCL layer, a cloud-probability layer, ...; on the 10, 20 or
+    60 m grid of the tile) or None per tile; mask_classes: the class values that are invalid (None = masks.SCL_INVALID);
+    mask_dilate: a dilation of the invalid area in GROUND-TRUTH pixels, 0..32.  While a tile is set up its validity bitmap is built
+    on the ground-truth grid ([2 grid_h, 2 grid_w]; run_60: [6 grid_h, 6 grid_w]) and the ground truth is zeroed there, once: the
+    masked pixels are no-data from then on, and `class_masked` is True (fit_corpus then wants mask_nodata=True).  The inputs stay
+    as they are.  skip_masked=True (needs class_masks): a cell of the origin grid that holds a masked pixel counts as blank — the
+    mask is OR-ed into the blank map (into an empty one without skip_blank), origin_masks() returns bitmaps free of it, and the
+    rule "fewer than 1 valid origin in 64: refused" applies unchanged."""
+
+    def __init__(self, tiles, run_60=False, device=None, skip_blank=False, class_masks=None, mask_classes=None, mask_dilate=0,
+                 skip_masked=False):
         self.run_60 = bool(run_60)
         self.skip_blank = bool(skip_blank)
+        self.skip_masked = bool(skip_masked)
         self.scale = 6 if self.run_60 else 2
         self.patch = PATCH_LR * self.scale
         tiles = [tuple(t) for t in tiles]
         if not tiles:
             raise ValueError('a corpus needs at least one tile')
         self.extents = [_check_tile(i, t, self.run_60) for i, t in enumerate(tiles)]      # every refusal before any upload
+        class_masks = self._check_class_masks(class_masks, mask_classes, mask_dilate, len(tiles))
+        self.class_masked = any(m is not None for m in class_masks)
+        if self.skip_masked and not self.class_masked:
+            raise ValueError('skip_masked needs class_masks: there is no mask to keep the crops out of')
+        mask_classes = masks_mod.SCL_INVALID if mask_classes is None else tuple(mask_classes)
+        masked_cells = self.skip_blank or self.skip_masked         # the corpus keeps cell maps and origin bitmaps
         self.device = torch.device(device) if device is not None else patches.default_device()
         if self.device.type == 'cuda' and self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
@@ -235,23 +258,61 @@ class TileCorpus(object):
                     pending.append(origin_mask_device(t, self.extents[i], self.footprint))
                 lr.append(patches.down_pixel_aggr_device(t, self.scale, dt))
                 if k == want - 1:
+                    if class_masks[i] is not None:         # (after the down-sampling: the inputs see the raster as it was)
+                        bits = masks_mod.valid_bits_device(class_masks[i], t.shape[:2], mask_classes, mask_dilate, device=self.device)
+                        masks_mod.raster_apply_valid_device(t, bits)
+                        if self.skip_masked:
+                            blank = pending.pop() if self.skip_blank else None
+                            pending.append(self._with_masked_cells(blank, bits, t.shape[:2], i))
+                        del bits
+                    elif self.skip_masked and not self.skip_blank:
+                        blank = torch.zeros(mask_shapes(self.extents[i])[0], dtype=torch.uint8, device=self.device)
+                        pending.append(origin_mask_device(blank, self.extents[i], self.footprint))
                     self.gt.append(t)
                     self.gt_dtypes.append(dt)
                 del t
             self.lr.append(lr)
         self.cout = BANDS[want - 1]
         self._handle = ctypes.c_void_p(0)
-        if self.skip_blank:                                # (a nearly blank tile is refused before the handle is made)
+        if masked_cells:                                   # (a nearly blank tile is refused before the handle is made)
             self.blank_cells = [cells for cells, _, _ in pending]
             self._blank_masks = _download_masks(pending)
+            what = ' and '.join(w for w, on in (('blank', self.skip_blank), ('masked', self.skip_masked)) if on)
             for i, (n, (gh, gw)) in enumerate(zip(self._blank_masks[1], self.extents)):
-                print('tile %d: %d of %d origins free of blank pixels' % (i, n, (gh - PATCH_LR + 1) * (gw - PATCH_LR + 1)))
+                print('tile %d: %d of %d origins free of %s pixels' % (i, n, (gh - PATCH_LR + 1) * (gw - PATCH_LR + 1), what))
             check_origin_counts(self.extents, self._blank_masks[1])
         table = (_lib.CorpusTile * len(tiles))()
         for i, (lr, gt, dt, grid) in enumerate(zip(self.lr, self.gt, self.gt_dtypes, self.extents)):
             table[i] = _lib.CorpusTile(lr[0].data_ptr(), lr[1].data_ptr(), lr[2].data_ptr() if self.run_60 else None, gt.data_ptr(),
                                        grid[0], grid[1], _lib.DTYPE_U16 if dt == np.uint16 else _lib.DTYPE_F32)
         _lib.call('dsen2_corpus_create', table, len(tiles), int(self.run_60), ctypes.byref(self._handle))
+
+    @staticmethod
+    def _check_class_masks(class_masks, mask_classes, mask_dilate, n_tiles):
+        """One 2-D uint8 raster or None per tile (None: no tile has one), after the refusals that need no GPU."""
+        if class_masks is None:
+            return [None] * n_tiles
+        class_masks = list(class_masks)
+        if len(class_masks) != n_tiles:
+            raise ValueError('%d class masks for %d tiles (one raster or None per tile)' % (len(class_masks), n_tiles))
+        for i, m in enumerate(class_masks):
+            if m is None:
+                continue
+            if len(np.shape(m)) != 2 or m.dtype != (torch.uint8 if isinstance(m, torch.Tensor) else np.uint8):
+                raise ValueError('tile %d: a class mask is a 2-D uint8 raster, got shape %r dtype %s' % (i, tuple(np.shape(m)), m.dtype))
+        masks_mod.lut(mask_classes)
+        if isinstance(mask_dilate, bool) or int(mask_dilate) != mask_dilate or not 0 <= mask_dilate <= masks_mod.MAX_DILATE:
+            raise ValueError('mask_dilate is in ground-truth pixels, 0..%d, got %r' % (masks_mod.MAX_DILATE, mask_dilate))
+        return class_masks
+
+    def _with_masked_cells(self, blank, bits, gt_shape, i):
+        """skip_masked: the (cells, bitmap, count) triple of tile i whose blank map — `blank`'s (skip_blank), or an empty one — has
+        the cells that hold a pixel masked in `bits` OR-ed in (dsen2_cells_from_valid_bits, S = 2 or 6 ground-truth pixels per
+        cell), handed to dsen2_corpus_origin_mask as DSEN2_MASK_BLANK_MAP."""
+        grid = self.extents[i]
+        cells = blank[0] if blank is not None else torch.zeros(mask_shapes(grid)[0], dtype=torch.uint8, device=self.device)
+        masks_mod.cells_from_bits_device(bits, gt_shape, self.scale, cells=cells)
+        return origin_mask_device(cells, grid, self.footprint)
 
     def origin_masks(self, holdout=None, margin=0):
         """([packed bitmap per tile], [valid origins per tile]) on the host: bit (oy, ox) of a tile's bitmap (mask_shapes;
@@ -372,6 +433,8 @@ class TileCorpus(object):
             dx, dy = self.batch(table[i0:i0 + chunk])
             for a, t in zip(xs + [y], dx + [dy]):
                 a[i0:i0 + chunk] = t.cpu().numpy()
+        if self.class_masked:                  # (the same bytes; fit then insists on mask_nodata, as fit_corpus does)
+            y = y.view(training.MaskedTarget)
         return xs, y
 
     def __del__(self):

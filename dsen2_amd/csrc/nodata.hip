@@ -11,6 +11,7 @@
 //              Every pixel is read once, every word written once; bits at x >= W are 0.
 //   2. flags   nodata_flags_kernel: a workgroup per patch ORs the bitmap words of its owned rectangle (first and last word of a
 //              row masked to the rectangle's columns) and writes one byte.
+// dsen2_tile_flags_from_bits: launch 2 alone, for a bitmap that came from elsewhere (valid_mask.hip: a class mask).
 // dsen2_recompose_rows_nodata: recompose_kernel (patch_ops.hip) with the bitmap and a slot map in front of the patch read.
 #include <cstdint>
 
@@ -191,6 +192,19 @@ extern "C" int dsen2_tile_nodata(const float* dev_img10, int H, int W, int C10, 
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(nodata_flags_kernel, dim3((unsigned)(x_tiles * y_tiles)), block, 0, st, dev_valid_bits, H, W, P - 2 * border,
                        x_tiles, y_tiles, wpr, dev_patch_empty);
+    HIP_TRY(hipGetLastError());
+    return DSEN2_OK;
+  });
+}
+
+extern "C" int dsen2_tile_flags_from_bits(const unsigned int* dev_valid_bits, int H, int W, int P, int border,
+                                          unsigned char* dev_patch_empty, void* stream) {
+  return guarded([&]() -> int {
+    if (!dev_valid_bits || !dev_patch_empty) return fail(DSEN2_ERR_INVALID, "tile_flags_from_bits: NULL argument");
+    int x_tiles = 0, y_tiles = 0, wpr = 0;
+    if (int rc = nodata_geometry("tile_flags_from_bits", H, W, P, border, &x_tiles, &y_tiles, &wpr)) return rc;
+    hipLaunchKernelGGL(nodata_flags_kernel, dim3((unsigned)(x_tiles * y_tiles)), dim3(kNThreads), 0, (hipStream_t)stream, dev_valid_bits,
+                       H, W, P - 2 * border, x_tiles, y_tiles, wpr, dev_patch_empty);
     HIP_TRY(hipGetLastError());
     return DSEN2_OK;
   });

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import dist as _dist
+from . import masks as _masks
 from . import patches as _patches
 from .DSen2Net import s2model
 
@@ -71,7 +72,7 @@ _LAST_RUN = {}
 
 def last_run_stats():
     """{'patches': ..., 'kept': ..., 'skipped': ...} of the last DSen2_20 / DSen2_60 call of this process (a copy): the patches of
-    the tile, those that were predicted and those SKIP_NODATA left out (always 0 with the option off)."""
+    the tile, those that were predicted and those SKIP_NODATA or a class mask (mask=) left out (always 0 with neither)."""
     return dict(_LAST_RUN)
 
 
@@ -277,22 +278,49 @@ def _gather_chunks():
     return max(1, int(os.environ.get('DSEN2_GATHER_CHUNKS', '8')))
 
 
-def _nodata_plan(d10_dev, patch, border, used):
+def _nodata_plan(d10_dev, patch, border, used, size=None, mask=None, dev=None):
     """SKIP_NODATA: (kept patch indices, slot map on the host, (slot map, bitmap) on the device) of the uploaded 10 m raster.  The
-    flags come to the host in ONE small read — the only synchronisation the option adds, before anything is enqueued."""
-    empty_dev, bits = _patches.nodata_device(d10_dev, patch, border)
+    flags come to the host in ONE small read — the only synchronisation the option adds, before anything is enqueued.
+    mask = (class raster, classes, dilate): the bitmap is the class mask's on the 10 m grid `size` (masks.valid_bits_device), ANDed
+    with the no-data bitmap where d10_dev is given (None: the mask alone), and the flags are formed from THAT bitmap."""
+    empty_dev = bits = None
+    if d10_dev is not None:
+        empty_dev, bits = _patches.nodata_device(d10_dev, patch, border)
+        size, dev = tuple(d10_dev.shape[:2]), d10_dev.device
+    if mask is not None:
+        cls, classes, dilate = mask
+        bits = _masks.valid_bits_device(cls, size, classes, dilate, and_bits=bits, device=dev, out=bits)
+        empty_dev = _masks.tile_flags_device(bits, size, patch, border)
     empty = empty_dev.cpu().numpy()
     if empty.size != used:
         raise ValueError('the 10 m image of %r pixels has %d patches to recompose but the tiling of the lowest resolution has %d: '
-                         'skip_nodata needs images in the exact size ratio' % (tuple(d10_dev.shape[:2]), empty.size, used))
+                         'skip_nodata and mask need images in the exact size ratio' % (tuple(size[:2]), empty.size, used))
     kept, slot_of_patch = _patches.slot_map(empty)
-    return kept, slot_of_patch, (torch.from_numpy(slot_of_patch).to(d10_dev.device), bits)
+    return kept, slot_of_patch, (torch.from_numpy(slot_of_patch).to(dev), bits)
 
 
-def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None, feather=None):
+def _check_mask(mask, classes, dilate, size):
+    """(class raster, classes, dilate) of a call, or ValueError / TypeError before anything touches the GPU: a 2-D uint8 raster
+    whose shape fits the 10 m grid `size` (masks.ratio), classes in 0..255 (None = masks.SCL_INVALID), dilate in 0..32."""
+    shape = tuple(int(s) for s in np.shape(mask))
+    if not isinstance(mask, torch.Tensor):
+        mask = np.asarray(mask)
+    if len(shape) != 2 or mask.dtype != (torch.uint8 if isinstance(mask, torch.Tensor) else np.uint8):
+        raise ValueError('mask is a 2-D uint8 class raster, got shape %r dtype %s' % (shape, mask.dtype))
+    _masks.ratio(shape, size[:2])
+    classes = _masks.SCL_INVALID if classes is None else tuple(classes)
+    _masks.lut(classes)
+    if isinstance(dilate, bool) or not isinstance(dilate, (int, np.integer)) or not 0 <= dilate <= _masks.MAX_DILATE:
+        raise ValueError('mask_dilate is in 10 m pixels, 0..%d, got %r' % (_masks.MAX_DILATE, dilate))
+    return mask, classes, int(dilate)
+
+
+def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None, feather=None, mask=None, mask_classes=None, mask_dilate=0):
     border, feather = _check_overlap(patch, scales[0], border, feather)            # before anything touches the GPU
     skip_nodata = SKIP_NODATA if skip_nodata is None else bool(skip_nodata)
     _patches.check_sizes(dsets, scales)
+    if mask is not None:
+        mask = _check_mask(mask, mask_classes, mask_dilate, dsets[0].shape)
     dev = _patches.default_device()
     rank, world = _dist.rank_world()
     patch_sizes = [patch // (scales[0] // s) for s in scales]          # P, P//2(, P//6)
@@ -308,9 +336,15 @@ def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None, feather=N
     # SKIP_NODATA: the 10 m raster goes up once, whole, on every rank (it serves the flags, the gather and, through the bitmap, the
     # recomposition), every rank computes the same flags, and everything below — origins, `used`, the shard ranges, the buffers,
     # the gathers — works on the KEPT patches; slot_of_patch says where a patch of the grid lies among them.
+    # mask: the class mask's bitmap, built on the device by every rank from the class raster itself (it is small), takes the place
+    # of the no-data bitmap — or is ANDed with it — and everything after is the same run.
     img10 = slot_of_patch = nodata = None
-    if skip_nodata:
-        img10 = _patches._to_device_f32(dsets[0], dev)
+    if mask is not None and single:
+        raise ValueError('mask: the single-patch shortcut returns the %d x %d patch uncropped, not the %r image; a mask needs a tile of '
+                         'more than one patch' % (patch, patch, tuple(size[:2])))
+    if skip_nodata or mask is not None:
+        if skip_nodata:
+            img10 = _patches._to_device_f32(dsets[0], dev)
         if single:
             valid = (img10 != 0).any(dim=2)
             if tuple(valid.shape) != (patch, patch):
@@ -319,7 +353,7 @@ def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None, feather=N
                 _LAST_RUN.update(kept=0, skipped=1)
                 return np.zeros((patch, patch, cout), np.float32) if rank == 0 else None
         else:
-            kept, slot_of_patch, nodata = _nodata_plan(img10, patch, border, used)
+            kept, slot_of_patch, nodata = _nodata_plan(img10, patch, border, used, size=(int(size[0]), int(size[1])), mask=mask, dev=dev)
             _LAST_RUN.update(kept=int(kept.size), skipped=used - int(kept.size))
             org, used = org[kept], int(kept.size)
             if used == 0:            # nothing holds data: the zero image, no forward, no collective (every rank knows)
@@ -408,27 +442,31 @@ def _run(dsets, scales, patch, border, deep, run_60, skip_nodata=None, feather=N
     return sink.finish()
 
 
-_EXTENSIONS = ('skip_nodata', 'border', 'feather')
+_EXTENSIONS = ('skip_nodata', 'border', 'feather', 'mask', 'mask_classes', 'mask_dilate')
 
 
 def _reference_surface(fn):
-    """fn(<the reference's parameters>, skip_nodata=None, border=None, feather=None) as the public function: this project's
+    """fn(<the reference's parameters>, skip_nodata=None, border=None, feather=None, mask=None, mask_classes=None, mask_dilate=0) as
+    the public function: this project's
     options (_EXTENSIONS) are taken BY KEYWORD ONLY, and inspect.signature() reports the reference's parameters alone
     (testing/supres.py:15,33) — callers and tools that bind or compare the drop-in surface by introspection see exactly the
     reference's."""
     sig = inspect.signature(fn)
     reference = sig.replace(parameters=[p for p in sig.parameters.values() if p.name not in _EXTENSIONS])
 
+    defaults = dict((name, sig.parameters[name].default) for name in _EXTENSIONS)
+
     @functools.wraps(fn)
-    def call(*args, skip_nodata=None, border=None, feather=None, **kwargs):
+    def call(*args, **kwargs):
+        ours = dict((name, kwargs.pop(name, default)) for name, default in defaults.items())
         bound = reference.bind(*args, **kwargs)           # TypeError for anything the reference's signature would refuse
-        return fn(*bound.args, skip_nodata=skip_nodata, border=border, feather=feather, **bound.kwargs)
+        return fn(*bound.args, **ours, **bound.kwargs)
     call.__signature__ = reference
     return call
 
 
 @_reference_surface
-def DSen2_20(d10, d20, deep=False, skip_nodata=None, border=None, feather=None):
+def DSen2_20(d10, d20, deep=False, skip_nodata=None, border=None, feather=None, mask=None, mask_classes=None, mask_dilate=0):
     """20 m -> 10 m.  d10 [x, y, 4] (B2 B3 B4 B8), d20 [x/2, y/2, 6] (B5 B6 B7 B8A B11 B12), any real dtype, HWC.
     deep=True selects VDSen2 (d=32, F=256).  Returns [x, y, 6] float32.  Geometry of testing/supres.py:21-22:
     patches of 128 with an 8-pixel border.
@@ -444,15 +482,25 @@ def DSen2_20(d10, d20, deep=False, skip_nodata=None, border=None, feather=None):
     border, feather (keyword only too; None = supres.BORDER_20 / BORDER_60 and supres.FEATHER): the overlap of neighbouring patches
     in 10 m pixels (a multiple of 2 / 6, at most 32 / 48; the patch keeps its size, so a wider border means more patches) and
     the width of the blend either side of every seam (1..border, True = border; None, False or 0 = the reference's hard cut).
-    ValueError for anything else, before the GPU is touched."""
+    ValueError for anything else, before the GPU is touched.
+
+    mask, mask_classes, mask_dilate (keyword only too): a 2-D uint8 class raster on the 10, 20 or 60 m grid of the tile (Sentinel-2's
+    SCL layer, a cloud-probability layer, ...; dsen2_amd/masks.py), the class values that make a pixel invalid (None =
+    masks.SCL_INVALID) and a dilation of the invalid area in 10 m pixels (0..32).  An invalid pixel is returned as 0 in every band and
+    a patch that decides no valid pixel is not computed, exactly as skip_nodata treats no-data (the two compose: their bitmaps are
+    ANDed); every other pixel is what the call without a mask returns, bit for bit (under feather: every pixel further than the
+    feather width from a skipped patch; nearer, the patches that are left are blended).  A tile of one patch refuses a mask."""
     return _run([d10, d20], [2, 1], patch=128, border=BORDER_20 if border is None else border, deep=deep, run_60=False,
-                skip_nodata=skip_nodata, feather=FEATHER if feather is None else feather)
+                skip_nodata=skip_nodata, feather=FEATHER if feather is None else feather, mask=mask, mask_classes=mask_classes,
+                mask_dilate=mask_dilate)
 
 
 @_reference_surface
-def DSen2_60(d10, d20, d60, deep=False, skip_nodata=None, border=None, feather=None):
+def DSen2_60(d10, d20, d60, deep=False, skip_nodata=None, border=None, feather=None, mask=None, mask_classes=None, mask_dilate=0):
     """60 m -> 10 m.  As DSen2_20 plus d60 [x/6, y/6, 2] (B1 B9; B10 is not super-resolved).  Returns [x, y, 2]
     float32.  Geometry of testing/supres.py:40-41: patches of 192 with a 12-pixel border.  Under torch.distributed: the
-    image on rank 0, None on every other rank (see DSen2_20).  skip_nodata, border, feather: as DSen2_20."""
+    image on rank 0, None on every other rank (see DSen2_20).  skip_nodata, border, feather, mask, mask_classes, mask_dilate: as
+    DSen2_20."""
     return _run([d10, d20, d60], [6, 3, 1], patch=192, border=BORDER_60 if border is None else border, deep=deep, run_60=True,
-                skip_nodata=skip_nodata, feather=FEATHER if feather is None else feather)
+                skip_nodata=skip_nodata, feather=FEATHER if feather is None else feather, mask=mask, mask_classes=mask_classes,
+                mask_dilate=mask_dilate)

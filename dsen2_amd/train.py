@@ -53,6 +53,13 @@ validates from the table of validation crops on the GPU and builds no host array
 its valid area; a tile left with fewer than 1 valid origin in 64 is refused.  Under --data_parallel every rank builds the same
 masks from its own copy of the corpus and the same --seed.
 
+--mask_key NAME [--mask_classes 0,1,3,8,9,10] [--mask_dilate N] [--skip_masked] (with --tiles; not in the reference): NAME is an
+array in each tile's .npz — a 2-D uint8 class raster on the 10, 20 or 60 m grid: Sentinel-2's SCL layer, a cloud-probability
+layer — and a tile without it has no mask.  Pixels of the listed classes (default: SCL no data, saturated or defective, cloud
+shadow, cloud medium and high probability, thin cirrus), grown by N ground-truth pixels (0..32), become no-data in the tile's ground
+truth on the GPU (corpus.TileCorpus(class_masks=)); --mask_key implies --mask_nodata, and says so, because a mask the loss ignored
+would train on zeros.  --skip_masked also draws no crop, training or validation, that touches a masked pixel.
+
 --loss {mae,mse,huber,charbonnier} [--loss_param X] [--mask_nodata] (not in the reference; without them the output, the log and
 the checkpoint are the bytes they always were) choose what is minimised (S2Model.compile(loss=, loss_param=, mask_nodata=);
 losses.py has the table): --loss_param is Huber's delta / Charbonnier's epsilon in the reflectance / 2000 domain, required for
@@ -67,12 +74,15 @@ windows of (1 - SSIM), to whatever --loss chose (S2Model.compile(ssim_weight=, .
 window is odd, 3..11; the data range lives in the reflectance / 2000 domain.  Patches must be at least the window on a side.  With
 --mask_nodata a window that holds a masked pixel adds nothing.  The loss and valid columns are then the total that is minimised.
 
-    python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] --path P
+    python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] [--mask M ...] --path P
 is that script's predict branch (--self_ensemble, not in the reference: predict(ensemble=True), the mean over the 8 flips and
 rotations of every patch; --augment is refused here): for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
 loads the tiled test set (patches.OpenDataFilesTest), runs predict(batch_size=8), recomposes the image (border 4; 12 for test60/
 and true/), multiplies by SCALE = 2000 and writes <P>/<folder>/<dset>/<model_nr>-predict.npy, model_nr being the seven
 characters in front of 'lr_1e-04' in FILE's name (model_number).  `python -m dsen2_amd.evaluate` scores those files.
+--mask NAME_OR_FILE [--mask_classes ...] [--mask_dilate N] (with --predict; not in the reference): a .npy class raster — a file of
+that name in every test-set directory, or one file given by its path — whose invalid pixels (as above; N in pixels of the image)
+are written as 0 in every band of the recomposed image, on the GPU.
 DECISION: the reference hands recompose_images `image_size` = [width, height] as read from roi.json, where that function takes
 (rows, columns).  For a square region the two agree, and that is what the recorded behaviour pins; for any other region the
 reference recomposes a transposed canvas.  Here recompose_images always gets (rows, columns) = (height, width), so a non-square
@@ -147,7 +157,35 @@ def parse_args(argv=None):
     p.add_argument('--feather', type=int, default=None, metavar='F',
                    help='With --predict: blend neighbouring patches across F pixels either side of every seam when the image is '
                         "recomposed, 1 <= F <= the border of the patch files (default: the reference's hard cut).")
+    p.add_argument('--mask_key', default=None, metavar='NAME',
+                   help="With --tiles: the array of each tile's .npz that holds its class raster (2-D uint8: SCL, cloud probability); its "
+                        'invalid pixels become no-data in the ground truth.  Implies --mask_nodata.')
+    p.add_argument('--mask', default=None, metavar='NAME_OR_FILE',
+                   help='With --predict: a .npy class raster (a name inside every test-set directory, or a path); its invalid pixels '
+                        'are written as 0.')
+    p.add_argument('--mask_classes', default=None, metavar='C,C,...',
+                   help='With --mask_key / --mask: the class values that are invalid (default 0,1,3,8,9,10 of the SCL layer).')
+    p.add_argument('--mask_dilate', type=int, default=None, metavar='N',
+                   help='With --mask_key / --mask: grow the invalid area by N pixels (ground-truth pixels; 0..32, default 0).')
+    p.add_argument('--skip_masked', action='store_true',
+                   help='With --mask_key: draw no crop (training or validation) that touches a masked pixel.')
     args = p.parse_args(argv)
+    if args.mask_key is not None and args.tiles is None:
+        p.error('--mask_key is an option of --tiles')
+    if args.mask is not None and not args.predict_file:
+        p.error('--mask is an option of --predict (training from tiles takes --mask_key)')
+    if args.skip_masked and args.mask_key is None:
+        p.error('--skip_masked is an option of --mask_key')
+    if args.mask_key is None and args.mask is None and (args.mask_classes is not None or args.mask_dilate is not None):
+        p.error('--mask_classes and --mask_dilate are options of --mask_key and --mask')
+    if args.mask_dilate is not None and not 0 <= args.mask_dilate <= 32:
+        p.error('--mask_dilate N: N is in pixels, 0..32')
+    if args.mask_classes is not None:
+        from . import masks
+        try:
+            args.mask_classes = masks.parse_classes(args.mask_classes)
+        except ValueError as e:
+            p.error(str(e))
     if args.feather is not None and (not args.predict_file or args.feather < 1):
         p.error('--feather F (F >= 1) is an option of --predict')
     if args.augment and args.predict_file:
@@ -220,6 +258,11 @@ def predict(model, args, path):
             images = patches.recompose_images(prediction, border=border, size=size, feather=args.feather)
         else:
             images = patches.recompose_images(prediction, border=border, size=size)
+        if args.mask:
+            from . import masks
+            in_dset = os.path.join(path + folder + dset, args.mask if args.mask.lower().endswith('.npy') else args.mask + '.npy')
+            images = masks.apply_to_image(images, np.load(in_dset if os.path.exists(in_dset) else args.mask), args.mask_classes,
+                                          args.mask_dilate or 0)
         print('Writing to file...')
         np.save(path + folder + dset + '/' + model_nr + '-predict', images * SCALE)
         print('Elapsed time: {}.'.format(time.time() - start))
@@ -238,12 +281,21 @@ def tiles_conflict(args, path):
     return None
 
 
+def tile_class_mask(tile_file, key):
+    """The array `key` of the tile's .npz (--mask_key), or None for a tile that has none."""
+    import numpy as np
+    if not tile_file.lower().endswith('.npz'):
+        return None
+    z = np.load(tile_file)
+    return z[key] if key in z else None
+
+
 def tiles_validation(corpus, args, crops_per_tile, say=print):
     """(validation table, training masks or None, validation host arrays or None) of a --tiles run.  The table is drawn ONCE
     (without --seed it comes from fresh entropy: a second draw would be other crops) and everything is derived from that one table:
     the hold-out masks of --holdout, the host arrays (cut from it, unless --val_on_device) and fit_corpus's validation_crops.  Every
     rank builds the same masks from its own copy of the corpus and the same --seed."""
-    blank = corpus.origin_masks()[0] if args.skip_blank else None
+    blank = corpus.origin_masks()[0] if args.skip_blank or getattr(args, 'skip_masked', False) else None
     masks = blank
     val_table = corpus.validation_table(crops_per_tile, args.seed, blank)
     if args.holdout:
@@ -316,6 +368,9 @@ def run(args, rank, world):
         model.set_weights_flat(weights.random_he_uniform(model.cin, model.cout, model.num_layers, model.feature_size,
                                                          seed=args.seed if args.seed is not None else 1))
         say('Model number is {}'.format(model_nr))
+    if args.mask_key is not None and not args.mask_nodata:
+        args.mask_nodata = True
+        say('--mask_key implies --mask_nodata: the masked pixels are no-data in the ground truth.')
     model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
                   loss=args.loss or 'mean_absolute_error', mixed_precision=args.mixed_precision, loss_param=args.loss_param,
                   mask_nodata=args.mask_nodata, ssim_weight=args.ssim_weight, ssim_win=args.ssim_win, ssim_sigma=args.ssim_sigma,
@@ -334,7 +389,16 @@ def run(args, rank, world):
             if opened is None:
                 return 2
             rasters.append(opened)
-        if args.skip_blank and rank != 0:                        # (one rank talks: the others build the same masks quietly)
+        if args.mask_key is not None:
+            class_masks = [tile_class_mask(f, args.mask_key) for f in args.tiles]
+            say('Class masks ({}): {} of {} tile{} carry one.'.format(args.mask_key, sum(m is not None for m in class_masks), len(class_masks),
+                                                                   '' if len(class_masks) == 1 else 's'))
+            masked = dict(class_masks=class_masks, mask_classes=args.mask_classes, mask_dilate=args.mask_dilate or 0,
+                          skip_masked=args.skip_masked)
+            import contextlib
+            with open(os.devnull, 'w') as quiet, contextlib.redirect_stdout(quiet if rank != 0 else sys.stdout):
+                corpus = corpus_mod.TileCorpus(rasters, run_60=args.run_60, device=model.device, skip_blank=args.skip_blank, **masked)
+        elif args.skip_blank and rank != 0:                      # (one rank talks: the others build the same masks quietly)
             import contextlib
             with open(os.devnull, 'w') as quiet, contextlib.redirect_stdout(quiet):
                 corpus = corpus_mod.TileCorpus(rasters, run_60=args.run_60, device=model.device, skip_blank=True)

@@ -162,6 +162,21 @@ class History(object):
             self.history.setdefault(k, []).append(v)
 
 
+class MaskedTarget(np.ndarray):
+    """A target array cut from a corpus whose ground truth carries a class mask as no-data (corpus.TileCorpus(class_masks=)): an
+    ndarray like any other, which fit recognises (check_masked_target).  Views and slices keep the type."""
+    class_masked = True
+
+
+def check_masked_target(setting, masked, who):
+    """ValueError when a target that carries a class mask (`masked`) meets a loss setting without the no-data mask: the masked
+    pixels are zeros in the ground truth, and a loss that does not ignore them would train the network towards zeros."""
+    from . import losses
+    if masked and losses.pointwise(setting)[2] != losses.MASK_NODATA:
+        raise ValueError('%s: the ground truth carries a class mask as no-data, but the model was not compiled with mask_nodata=True: '
+                         'a mask that the loss ignores would train on zeros' % who)
+
+
 def load_training_data(path, run_60=False, scale=SCALE):
     """utils/patches.py OpenDataFiles + splitTrainVal: every <path>/train/*SAFE (train60/ for run_60) directory's data10,
     data20 (, data60) and ground truth data20_gt (data60_gt) arrays, concatenated in sorted directory order, divided by

@@ -613,6 +613,44 @@ int dsen2_corpus_origin_mask(const void *dev_src, int dtype, int H, int W, int C
                              const int *dev_holdout, int m, int margin, unsigned char *dev_cells, unsigned char *dev_bitmap,
                              int *dev_count, void *stream);
 
+/* ---- class masks: a validity bitmap from a class raster the caller brings (csrc/valid_mask.hip) ---------------------------------------
+ * Not in the reference.  The bitmap is dsen2_tile_nodata's: uint32 [H][ceil(W/32)], pixel (y, x) is bit x & 31 of word
+ * y*ceil(W/32) + (x >> 5), a set bit means valid, the bits at x >= W are 0.  Definitions, for a class raster dev_cls (uint8 [Hs, Ws]:
+ * Sentinel-2's SCL layer, a cloud-probability layer, any class image at 10, 20 or 60 m) and a target grid of H x W pixels:
+ *   TABLE      host_lut256: 256 bytes in HOST memory, read during the call and passed by value into the launch (as 256 bits); a
+ *              non-zero entry means the class is invalid.  A probability layer with a threshold is just another table.
+ *   RAW        with up > 1 (source coarser than the target, replicated) target pixel (y, x) is RAW-invalid when source pixel
+ *              (y / up, x / up) has an invalid class: needs (H-1)/up < Hs and (W-1)/up < Ws.  With down > 1 (source finer) it is
+ *              RAW-invalid when ANY source pixel of its down x down block, rows [y*down, (y+1)*down) and columns alike, has one:
+ *              needs H*down <= Hs and W*down <= Ws.  up == down == 1: pixel for pixel.  Surplus source rows and columns are never
+ *              read.
+ *   DILATED    a pixel is invalid when any RAW-invalid pixel lies within |dy| <= dilate, |dx| <= dilate INSIDE the image; what
+ *              lies outside the image is valid.  dilate is in target pixels, 0..32 (one bitmap word: a tile's halo is one word
+ *              either side).
+ *   OUTPUT     bit = not DILATED, ANDed with the same bit of dev_and_bits_or_null when one is given (it may be the output buffer
+ *              itself: a word is read and written by the same lane); padding bits 0.
+ * dsen2_class_valid_bits: one launch on `stream`; dilate == 0 takes a kernel of its own without halo or LDS tile.  Integer work
+ *   only, no atomics: the result depends on the inputs alone.  Nothing synchronises.
+ * dsen2_tile_flags_from_bits: the second launch of dsen2_tile_nodata — dev_patch_empty (uint8 [y_tiles*x_tiles], 1 = the patch's
+ *   owned rectangle holds no set bit) from ANY bitmap in this format, by the same kernel.  Geometry and refusals of
+ *   dsen2_tile_nodata.
+ * dsen2_raster_apply_valid: in place on the HWC raster dev_img [H,W,C] of uint16 (DSEN2_DTYPE_U16) or float32 (DSEN2_DTYPE_F32)
+ *   samples: every one of the C samples of a pixel whose bit is 0 becomes 0 (+0.0f); no other byte of the raster is written.  Any
+ *   C in 1..4096.
+ * dsen2_cells_from_valid_bits: dev_cells uint8 [H/S, W/S]; a cell becomes 1 when any pixel of its S x S footprint has bit 0, else
+ *   0; with accumulate != 0 a cell that already holds non-zero is left as it is (the OR into a blank map, which
+ *   dsen2_corpus_origin_mask then takes as DSEN2_MASK_BLANK_MAP).  H and W multiples of S, S in 1..8.
+ * DSEN2_ERR_INVALID with nothing launched: a NULL pointer (dev_and_bits_or_null excepted), H or W below 1 or above 2^15 = 32768,
+ *   up or down outside 1..8 or both above 1, a coverage rule broken, dilate outside 0..32, another dtype, C outside 1..4096, S
+ *   outside 1..8 or not dividing H and W, the geometry dsen2_tile_nodata refuses. */
+int dsen2_class_valid_bits(const unsigned char *dev_cls, int Hs, int Ws, const unsigned char *host_lut256, int up, int down, int H,
+                           int W, int dilate, const unsigned int *dev_and_bits_or_null, unsigned int *dev_valid_bits, void *stream);
+int dsen2_tile_flags_from_bits(const unsigned int *dev_valid_bits, int H, int W, int P, int border, unsigned char *dev_patch_empty,
+                               void *stream);
+int dsen2_raster_apply_valid(void *dev_img, int dtype, int H, int W, int C, const unsigned int *dev_valid_bits, void *stream);
+int dsen2_cells_from_valid_bits(const unsigned int *dev_valid_bits, int H, int W, int S, int accumulate, unsigned char *dev_cells,
+                                void *stream);
+
 /* dsen2_abs_sq_error_sums (csrc/error_sums.hip): dev_out[0 .. 1] = { sum |p - t|, sum (p - t)^2 } over `count` float32 pairs, as
  *   float64: what a validation pass needs of a prediction that is already on the device.  Every difference, product and sum is
  *   float64 and rounded on its own (no FMA).  The order of every addition is fixed by `count` alone: blocks = clamp(ceil(count /
