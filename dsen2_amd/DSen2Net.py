@@ -492,12 +492,15 @@ class S2Model(object):
         return out
 
     def set_weights_device(self, flat):
-        """New keras-flat weights from a float32 device tensor, repacked on the device."""
+        """New keras-flat weights from a float32 device tensor, repacked on the device.  A model being trained continues from
+        them: get_weights_flat() returns them and the next optimizer step updates them (as after set_weights_flat)."""
         if flat.numel() != self.count_params() or flat.dtype != torch.float32 or not flat.is_contiguous() or \
                 flat.device != self.device:
             raise ValueError('flat must be a contiguous float32 %s tensor of %d values' % (self.device, self.count_params()))
         with torch.cuda.device(self.device):
             _lib.call('dsen2_model_set_weights_device', self._handle, _ptr(flat), _stream_ptr(self.device))
+            if self._train is not None and flat.data_ptr() != self._train['flat'].data_ptr():
+                self._train['flat'].copy_(flat)      # a model being trained continues from the new weights (as set_weights_flat)
 
     def nadam_update(self, grad):
         """One optimizer step on the training weights with gradient `grad` (device tensor), then the device repack."""
