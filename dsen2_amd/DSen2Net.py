@@ -392,6 +392,10 @@ class S2Model(object):
                 mask_nodata=False, ssim_weight=0.0, ssim_win=11, ssim_sigma=1.5, ssim_data_range=5.0):
         """keras Model.compile for the reference's recipe: optimizer 'nadam' or a training.Nadam, loss
         'mean_absolute_error' (MSE is always reported as the metric).  The optimizer state starts fresh.
+        optimizer: 'nadam' (the default), 'adam', 'sgd', or a training.Nadam / Adam / SGD, each of which takes the keyword-only
+        options clipnorm, clipvalue, weight_decay and decay_bias (training.Optimizer): clipping by the gradient's global norm over
+        all weight tensors and by value, and decoupled weight decay on the convolution kernels.  A Nadam without options steps
+        through the kernels it always did; every training path follows the optimiser, and last_grad_norm() reads the norm.
         loss: 'mean_absolute_error' / 'mae' (the default, the reference's), 'mean_squared_error' / 'mse', 'huber' or 'charbonnier'
         (losses.py has the table).  loss_param (keyword only): Huber's delta / Charbonnier's epsilon as a float32 > 0, required
         for those two — errors live in the reflectance / 2000 domain, where keras's delta = 1 would just be MSE / 2 — and refused
@@ -421,11 +425,13 @@ class S2Model(object):
             raise ValueError('mixed_precision=%r is an option of an fp32 model (this one is %r)' % (mixed_precision, self.precision))
         setting = losses.parse_ssim(losses.parse(loss, loss_param, mask_nodata), ssim_weight, ssim_win, ssim_sigma, ssim_data_range)
         if isinstance(optimizer, str):
-            if optimizer.lower() != 'nadam':
-                raise ValueError("optimizer must be 'nadam' or a dsen2_amd.training.Nadam, got %r" % optimizer)
-            optimizer = training.Nadam()
-        if not isinstance(optimizer, training.Nadam):
-            raise ValueError('optimizer must be a dsen2_amd.training.Nadam')
+            if optimizer.lower() not in training.OPTIMIZERS:
+                raise ValueError("optimizer must be 'nadam', 'adam', 'sgd' or a dsen2_amd.training optimizer, got %r" % optimizer)
+            optimizer = training.OPTIMIZERS[optimizer.lower()]()
+        if not isinstance(optimizer, training.Optimizer):
+            raise ValueError('optimizer must be a dsen2_amd.training.Nadam, Adam or SGD')
+        if optimizer.weight_decay:
+            training.decay_ranges(self.cin, self.cout, self.num_layers, self.feature_size, optimizer.decay_bias)    # (refused here, not at the first step)
         if self.precision == 'fp32':
             with torch.cuda.device(self.device):
                 _lib.call('dsen2_model_set_train_precision', self._handle, self.MIXED_PRECISIONS[mixed_precision])
@@ -451,9 +457,107 @@ class S2Model(object):
             flat = torch.empty(count, **kw)
             with torch.cuda.device(self.device):
                 _lib.call('dsen2_model_get_weights', self._handle, _ptr(flat), _stream_ptr(self.device))
+            # (SGD keeps its velocity in m and has no second moment)
             self._train = dict(flat=flat, grad=torch.empty(count, **kw), m=torch.zeros(count, **kw),
-                               v=torch.zeros(count, **kw), loss2=torch.empty(2, **kw), ws=None)
+                               v=torch.zeros(count, **kw) if self.optimizer.KIND != 2 else None, loss2=torch.empty(2, **kw), ws=None,
+                               # what a step through dsen2_optimizer_step keeps (built by the first such step: the options of an
+                               # optimiser are as mutable as its lr, so the route is chosen step by step)
+                               norm=None, norm_valid=False, opt_work=None, ranges=None)
         return self._train
+
+    def _plain_nadam(self):
+        """The optimiser is a Nadam without options: its step is dsen2_nadam_step / dsen2_nadam_step_shards, as it always was.
+        Asked at every step: setting an option on the optimiser later moves the following steps to dsen2_optimizer_step."""
+        from . import training
+        return isinstance(self.optimizer, training.Nadam) and not self.optimizer.has_options()
+
+    def _decay_range_array(self):
+        """(n, ctypes array of 2 n unsigned) of the optimiser's decay ranges as its options stand NOW; (0, None) without weight
+        decay.  Kept with the training state under the options it was made from."""
+        from . import training
+        opt = self.optimizer
+        key = (bool(opt.weight_decay), bool(opt.decay_bias))
+        st = self._train
+        if st['ranges'] is None or st['ranges'][0] != key:
+            if not opt.weight_decay:
+                made = (0, None)
+            else:
+                ranges = training.decay_ranges(self.cin, self.cout, self.num_layers, self.feature_size, opt.decay_bias)
+                made = (len(ranges), (ctypes.c_uint * (2 * len(ranges)))(*[int(x) for r in ranges for x in r]))
+            st['ranges'] = (key, made)
+        return st['ranges'][1]
+
+    def _optimizer_desc(self, s):
+        """The dsen2_optimizer_desc of the step whose scalars next_step() has returned as `s`."""
+        opt = self.optimizer
+        n, arr = self._decay_range_array()
+        d = _lib.OptimizerDesc()
+        d.kind = opt.KIND
+        for k in ('lr', 'b1', 'b2', 'eps', 'mc_t', 'mc_t1', 'ms_new', 'ms_next', 'b2_pow_t', 'lr_t', 'momentum'):
+            setattr(d, k, s.get(k, 0.0))
+        d.nesterov = int(bool(s.get('nesterov', False)))
+        d.clipnorm, d.clipvalue, d.weight_decay = opt.clipnorm, opt.clipvalue, opt.weight_decay
+        d.n_ranges = n
+        d.host_ranges = ctypes.cast(arr, ctypes.POINTER(ctypes.c_uint)) if n else None
+        return d
+
+    def last_grad_norm(self):
+        """The global norm (over all weight tensors, before clipping) of the mean gradient of the last step, as the float64 the
+        step's kernels left on the device: with or without clipnorm, so it can be looked at before a clipnorm is chosen.  Every
+        step through dsen2_optimizer_step forms it — Adam, SGD, a Nadam with an option; a Nadam without options steps through
+        the kernels it always did, which form none: RuntimeError then, and before the first step.  This read is the only call of
+        the optimiser path that waits for the device."""
+        st = self._train_state()
+        if not st['norm_valid']:
+            raise RuntimeError('no gradient norm: the last step was not one of Adam, SGD or a Nadam with clipnorm, clipvalue or '
+                               'weight_decay (a Nadam without options forms none)')
+        return float(st['norm'].cpu().numpy()[0])
+
+    def _optimizer_step(self, g, stride, counts, g_mean=None):
+        """THE optimiser step: on the gradient vector g (counts None), or on the count-weighted mean of the rows g[r] of `stride`
+        floats with counts[r] samples each.  A Nadam without options takes the entries it always took (dsen2_nadam_step,
+        dsen2_nadam_step_shards: the same launches, the same bits); everything else is dsen2_optimizer_step.  A refused call is
+        not a step.  Then the device repack."""
+        st = self._train_state()
+        opt = self.optimizer
+        count = st['flat'].numel()
+        before = opt.step_state()
+        s = opt.next_step()
+        try:
+            with torch.cuda.device(self.device):
+                if self._plain_nadam():
+                    scalars = (s['lr'], s['b1'], s['b2'], s['eps'], s['mc_t'], s['mc_t1'], s['ms_new'], s['ms_next'], s['b2_pow_t'])
+                    if counts is None:
+                        _lib.call('dsen2_nadam_step', _ptr(st['flat']), _ptr(g), _ptr(st['m']), _ptr(st['v']), count, *scalars,
+                                  _stream_ptr(self.device))
+                    else:
+                        _lib.call('dsen2_nadam_step_shards', _ptr(st['flat']), _ptr(g), stride, len(counts),
+                                  (ctypes.c_int * len(counts))(*counts), _ptr(g_mean), _ptr(st['m']), _ptr(st['v']), count, *scalars,
+                                  _stream_ptr(self.device))
+                    st['norm_valid'] = False
+                else:
+                    if counts is None:
+                        stride, counts = count, [1]
+                    desc = self._optimizer_desc(s)
+                    if st['norm'] is None:
+                        st['norm'] = torch.zeros(1, dtype=torch.float64, device=self.device)
+                    # the norm is always asked for (one more read of the gradient): last_grad_norm() works without clipnorm
+                    need = ctypes.c_size_t(0)
+                    _lib.call('dsen2_optimizer_step_work_bytes', ctypes.byref(desc), count, len(counts), int(g_mean is not None), 1,
+                              ctypes.byref(need))
+                    if st['opt_work'] is None or st['opt_work'].numel() < need.value:
+                        st['opt_work'] = None
+                        st['opt_work'] = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+                    work = st['opt_work']
+                    st['norm_valid'] = False
+                    _lib.call('dsen2_optimizer_step', ctypes.byref(desc), _ptr(st['flat']), _ptr(g), stride, len(counts),
+                              (ctypes.c_int * len(counts))(*counts), _ptr(g_mean), _ptr(st['m']), _ptr(st['v']), count, _ptr(work),
+                              work.numel(), _ptr(st['norm']), _stream_ptr(self.device))
+                    st['norm_valid'] = True
+        except Exception:
+            opt.set_step_state(before)          # a refused call is not a step
+            raise
+        self.set_weights_device(st['flat'])
 
     def train_workspace_bytes(self, n, h, w):
         out = ctypes.c_size_t(0)
@@ -504,13 +608,7 @@ class S2Model(object):
 
     def nadam_update(self, grad):
         """One optimizer step on the training weights with gradient `grad` (device tensor), then the device repack."""
-        st = self._train_state()
-        s = self.optimizer.next_step()
-        with torch.cuda.device(self.device):
-            _lib.call('dsen2_nadam_step', _ptr(st['flat']), _ptr(grad), _ptr(st['m']), _ptr(st['v']), st['flat'].numel(),
-                      s['lr'], s['b1'], s['b2'], s['eps'], s['mc_t'], s['mc_t1'], s['ms_new'], s['ms_next'], s['b2_pow_t'],
-                      _stream_ptr(self.device))
-        self.set_weights_device(st['flat'])
+        self._optimizer_step(grad, None, None)
 
     def _to_device(self, arrays, shapes):
         out = []
@@ -549,18 +647,7 @@ class S2Model(object):
         if g_mean is not None and (g_mean.numel() != count or g_mean.dtype != torch.float32 or not g_mean.is_contiguous() or
                                    g_mean.device != self.device):
             raise ValueError('g_mean must be a contiguous float32 %s tensor of %d values' % (self.device, count))
-        before = (self.optimizer.iterations, self.optimizer.m_schedule)
-        s = self.optimizer.next_step()
-        try:
-            with torch.cuda.device(self.device):
-                _lib.call('dsen2_nadam_step_shards', _ptr(st['flat']), _ptr(buf), max(buf.stride(0), count), len(counts),
-                          (ctypes.c_int * len(counts))(*counts), _ptr(g_mean), _ptr(st['m']), _ptr(st['v']), count,
-                          s['lr'], s['b1'], s['b2'], s['eps'], s['mc_t'], s['mc_t1'], s['ms_new'], s['ms_next'], s['b2_pow_t'],
-                          _stream_ptr(self.device))
-        except Exception:
-            self.optimizer.iterations, self.optimizer.m_schedule = before          # a refused call is not a step
-            raise
-        self.set_weights_device(st['flat'])
+        self._optimizer_step(buf, max(buf.stride(0), count), counts, g_mean)
 
     @staticmethod
     def weighted_loss(loss2, counts):

@@ -30,6 +30,14 @@ class CorpusTile(ctypes.Structure):
                 ('grid_h', c_int), ('grid_w', c_int), ('gt_dtype', c_int)]
 
 
+class OptimizerDesc(ctypes.Structure):
+    """dsen2_optimizer_desc (include/dsen2_hip.h, "the optimiser step with options")."""
+    _fields_ = [('kind', c_int)] + [(k, ctypes.c_float) for k in ('lr', 'b1', 'b2', 'eps', 'mc_t', 'mc_t1', 'ms_new', 'ms_next', 'b2_pow_t',
+                                                                  'lr_t', 'momentum')] + \
+               [('nesterov', c_int), ('clipnorm', ctypes.c_float), ('clipvalue', ctypes.c_float), ('weight_decay', ctypes.c_float),
+                ('n_ranges', c_int), ('host_ranges', ctypes.POINTER(ctypes.c_uint))]
+
+
 # name -> (restype, argtypes); every symbol include/dsen2_hip.h declares
 SIGNATURES = {
     'dsen2_version': (ctypes.c_char_p, []),
@@ -76,6 +84,9 @@ SIGNATURES = {
     'dsen2_nadam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t] + [ctypes.c_float] * 9 + [c_void_p]),
     'dsen2_nadam_step_shards': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int_p, c_void_p, c_void_p, c_void_p, c_size_t] +
                                 [ctypes.c_float] * 9 + [c_void_p]),
+    'dsen2_optimizer_step_work_bytes': (c_int, [ctypes.POINTER(OptimizerDesc), c_size_t, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    'dsen2_optimizer_step': (c_int, [ctypes.POINTER(OptimizerDesc), c_void_p, c_void_p, c_size_t, c_int, c_int_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
     'dsen2_conv3x3_wgrad': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     ctypes.c_float, c_void_p]),
     'dsen2_conv3x3_wgrad_bf16x3': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float,

@@ -17,8 +17,8 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SOURCES = ['conv3x3_body32.hip', 'conv3x3_body16w.hip', 'conv3x3_out.hip', 'conv3x3_out_mfma.hip', 'conv3x3_mfma.hip', 'conv3x3_first.hip', 'conv3x3_first16.hip', 'patch_ops.hip', 'down_pixel_aggr.hip', 'imresize.hip', 'quality_metrics.hip', 'ssim.hip', 'ssim_loss.hip', 'conv_plan.hip', 'capi.hip',
-           'conv3x3_wgrad.hip', 'conv3x3_wgrad16.hip', 'train_ops.hip', 'capi_train.hip', 'dihedral.hip', 'corpus_batch.hip', 'corpus_mask.hip', 'error_sums.hip', 'nodata.hip', 'recompose_blend.hip', 'valid_mask.hip']
-HEADERS = [os.path.join(CSRC, "dsen2_internal.h"), os.path.join(CSRC, "conv_plan.h"), os.path.join(CSRC, "capi_internal.h"), os.path.join(CSRC, "conv3x3_dma.h"), os.path.join(CSRC, "conv3x3_bf16_common.h"), os.path.join(CSRC, "conv3x3_items.h"), os.path.join(CSRC, "conv3x3_first_common.h"), os.path.join(CSRC, "resample.h"), os.path.join(CSRC, "quality_common.h"), os.path.join(CSRC, "upsample_math.h"), os.path.join(CSRC, "loss_terms.h"), os.path.join(CSRC, "fixed_sum.h"), os.path.join(os.path.dirname(HERE), 'include', 'dsen2_hip.h')]
+           'conv3x3_wgrad.hip', 'conv3x3_wgrad16.hip', 'train_ops.hip', 'optimizer_step.hip', 'capi_train.hip', 'dihedral.hip', 'corpus_batch.hip', 'corpus_mask.hip', 'error_sums.hip', 'nodata.hip', 'recompose_blend.hip', 'valid_mask.hip']
+HEADERS = [os.path.join(CSRC, "dsen2_internal.h"), os.path.join(CSRC, "conv_plan.h"), os.path.join(CSRC, "capi_internal.h"), os.path.join(CSRC, "conv3x3_dma.h"), os.path.join(CSRC, "conv3x3_bf16_common.h"), os.path.join(CSRC, "conv3x3_items.h"), os.path.join(CSRC, "conv3x3_first_common.h"), os.path.join(CSRC, "resample.h"), os.path.join(CSRC, "quality_common.h"), os.path.join(CSRC, "upsample_math.h"), os.path.join(CSRC, "loss_terms.h"), os.path.join(CSRC, "fixed_sum.h"), os.path.join(CSRC, "nadam_math.h"), os.path.join(CSRC, "optimizer_step.h"), os.path.join(os.path.dirname(HERE), 'include', 'dsen2_hip.h')]
 LIB = os.path.join(HERE, 'libdsen2_hip.so')
 DIAG_LIB = os.path.join(os.path.dirname(HERE), 'build', 'libdsen2_hip_diag.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

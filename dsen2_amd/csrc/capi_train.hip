@@ -39,6 +39,7 @@
 // packed buffers a precision-1 model of these weights would hold (first16 image, bf16 body planes, fp32 output layer) and its
 // own 16-bit training state (the bf16 flipped / transposed dgrad weights) on the owner's master vector.  The model, its master
 // weights and its packed fp32 buffers stay as they are; it builds no fp32 dgrad weights.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -46,6 +47,7 @@
 #include <stdexcept>
 
 #include "capi_internal.h"
+#include "optimizer_step.h"
 
 using namespace dsen2;
 
@@ -600,6 +602,123 @@ int dsen2_nadam_step_shards(float* p, const float* dev_g_shards, size_t shard_st
     if (total <= 0) return fail(DSEN2_ERR_INVALID, "the sample counts of the %d shards add up to zero", shards);
     HIP_TRY(launch_nadam_shards(p, dev_g_shards, shard_stride, shards, counts, dev_g_mean, m, v, count, lr, b1, b2, eps, mc_t, mc_t1,
                                 ms_new, ms_next, b2_pow_t, (hipStream_t)stream));
+    return DSEN2_OK;
+  });
+}
+
+// ---- dsen2_optimizer_step: every check before any launch ----
+namespace {
+
+// dev_work of dsen2_optimizer_step: { the sum of squares, one double of padding }, the blocks' partials, then (with_mean) the mean
+// gradient; every piece starts on a multiple of 16 bytes
+struct OptimizerWork {
+  size_t partials_off, mean_off, bytes;
+};
+OptimizerWork optimizer_work(size_t count, bool with_norm, bool with_mean) {
+  OptimizerWork w{2 * sizeof(double), 0, 0};
+  if (!with_norm) return w;
+  w.mean_off = w.partials_off + sqsum_partial_doubles() * sizeof(double);
+  w.bytes = w.mean_off + (with_mean ? (count + 3) / 4 * 16 : 0);
+  return w;
+}
+bool needs_norm(const dsen2_optimizer_desc* d, bool want_norm) { return d->clipnorm > 0.f || want_norm; }
+// the norm pass leaves the mean gradient somewhere for the step to read: with several rows and no buffer of the caller's, in dev_work
+bool mean_in_work(const dsen2_optimizer_desc* d, int shards, bool have_g_mean, bool want_norm) {
+  return needs_norm(d, want_norm) && shards > 1 && !have_g_mean;
+}
+bool bad_option(float x) { return !(x >= 0.f) || !std::isfinite(x); }      // negative, NaN or infinite
+
+int check_optimizer_desc(const dsen2_optimizer_desc* d, size_t count, DecayRanges* ranges) {
+  if (!d) return fail(DSEN2_ERR_INVALID, "optimizer_step: NULL descriptor");
+  if (d->kind < 0 || d->kind >= kOptKinds) return fail(DSEN2_ERR_INVALID, "optimizer_step: kind %d unknown (0 Nadam, 1 Adam, 2 SGD)", d->kind);
+  if (bad_option(d->clipnorm) || bad_option(d->clipvalue) || bad_option(d->weight_decay) || bad_option(d->momentum))
+    return fail(DSEN2_ERR_INVALID, "optimizer_step: clipnorm %g, clipvalue %g, weight_decay %g and momentum %g must be finite and >= 0",
+                (double)d->clipnorm, (double)d->clipvalue, (double)d->weight_decay, (double)d->momentum);
+  if (d->momentum >= 1.f) return fail(DSEN2_ERR_INVALID, "optimizer_step: momentum %g is not below 1", (double)d->momentum);
+  if (d->n_ranges < 0 || d->n_ranges > kMaxDecayRanges)
+    return fail(DSEN2_ERR_INVALID, "optimizer_step: %d decay ranges outside 0..%d", d->n_ranges, kMaxDecayRanges);
+  if (d->n_ranges > 0 && !d->host_ranges) return fail(DSEN2_ERR_INVALID, "optimizer_step: %d decay ranges and a NULL host_ranges", d->n_ranges);
+  ranges->n = d->n_ranges;
+  size_t behind = 0;
+  for (int k = 0; k < d->n_ranges; ++k) {
+    const unsigned lo = d->host_ranges[2 * k], hi = d->host_ranges[2 * k + 1];
+    if (lo >= hi || (size_t)lo < behind || (size_t)hi > count)
+      return fail(DSEN2_ERR_INVALID, "optimizer_step: decay range %d = [%u, %u) is empty, unsorted, overlaps its predecessor or ends behind %zu",
+                  k, lo, hi, count);
+    ranges->lo[k] = lo;
+    ranges->hi[k] = hi;
+    behind = hi;
+  }
+  return DSEN2_OK;
+}
+
+}  // namespace
+
+int dsen2_optimizer_step_work_bytes(const dsen2_optimizer_desc* d, size_t count, int shards, int have_g_mean, int want_norm, size_t* bytes) {
+  return guarded([&]() -> int {
+    if (!bytes) return fail(DSEN2_ERR_INVALID, "optimizer_step_work_bytes: NULL argument");
+    DecayRanges ranges{};
+    if (int rc = check_optimizer_desc(d, count, &ranges)) return rc;
+    if (shards < 1 || shards > kMaxShards) return fail(DSEN2_ERR_INVALID, "shards %d outside 1..%d", shards, kMaxShards);
+    *bytes = optimizer_work(count, needs_norm(d, want_norm != 0), mean_in_work(d, shards, have_g_mean != 0, want_norm != 0)).bytes;
+    return DSEN2_OK;
+  });
+}
+
+int dsen2_optimizer_step(const dsen2_optimizer_desc* d, float* p, const float* dev_g_shards, size_t shard_stride, int shards,
+                         const int* host_counts, float* dev_g_mean, float* m, float* v, size_t count, void* dev_work, size_t work_bytes,
+                         double* dev_norm, void* stream) {
+  return guarded([&]() -> int {
+    DecayRanges ranges{};
+    if (int rc = check_optimizer_desc(d, count, &ranges)) return rc;
+    if (!host_counts || (count > 0 && (!p || !dev_g_shards || !m))) return fail(DSEN2_ERR_INVALID, "optimizer_step: NULL argument");
+    if (count > 0 && d->kind != kOptSgd && !v) return fail(DSEN2_ERR_INVALID, "optimizer_step: kind %d needs the second-moment vector v", d->kind);
+    if (shards < 1 || shards > kMaxShards) return fail(DSEN2_ERR_INVALID, "shards %d outside 1..%d", shards, kMaxShards);
+    if (shard_stride < count) return fail(DSEN2_ERR_INVALID, "shard_stride %zu < count %zu", shard_stride, count);
+    ShardCounts counts{};
+    long long total = 0;
+    for (int r = 0; r < shards; ++r) {
+      if (host_counts[r] < 0) return fail(DSEN2_ERR_INVALID, "negative sample count %d of shard %d", host_counts[r], r);
+      if (host_counts[r] >= (1 << 24)) return fail(DSEN2_ERR_INVALID, "sample count %d of shard %d is not below 2^24", host_counts[r], r);
+      counts.n[r] = host_counts[r];
+      total += host_counts[r];
+    }
+    if (total <= 0) return fail(DSEN2_ERR_INVALID, "the sample counts of the %d shards add up to zero", shards);
+    const bool norm = needs_norm(d, dev_norm != nullptr), in_work = mean_in_work(d, shards, dev_g_mean != nullptr, dev_norm != nullptr);
+    const OptimizerWork W = optimizer_work(count, norm, in_work);
+    if (W.bytes > 0 && (!dev_work || work_bytes < W.bytes || (uintptr_t)dev_work % 16 != 0))
+      return fail(DSEN2_ERR_INVALID, "optimizer_step: scratch of %zu bytes at %p, dsen2_optimizer_step_work_bytes asks for %zu on a 16-byte boundary",
+                  work_bytes, dev_work, W.bytes);
+    OptimizerScalars s{};
+    s.kind = d->kind;
+    s.nadam = NadamScalars{d->lr, d->b1, d->b2, d->eps, d->mc_t, d->mc_t1, d->ms_new, d->ms_next, d->b2_pow_t};
+    s.lr_t = d->lr_t;
+    s.momentum = d->momentum;
+    s.nesterov = d->nesterov != 0;
+    s.clipnorm = d->clipnorm;
+    s.clipvalue = d->clipvalue;
+    s.weight_decay = d->weight_decay;
+    hipStream_t st = (hipStream_t)stream;
+    if (!norm) {      // one pass: the mean and the step, as dsen2_nadam_step_shards
+      HIP_TRY(launch_optimizer_step(s, p, dev_g_shards, shard_stride, shards, counts, dev_g_mean, m, v, count, nullptr, ranges, st));
+      return DSEN2_OK;
+    }
+    char* const work = static_cast<char*>(dev_work);
+    double* const sqsum = reinterpret_cast<double*>(work);
+    if (count == 0) {
+      HIP_TRY(hipMemsetAsync(sqsum, 0, sizeof(double), st));
+      if (dev_norm) HIP_TRY(hipMemsetAsync(dev_norm, 0, sizeof(double), st));
+      return DSEN2_OK;
+    }
+    // two passes: the mean (kept where several rows make one: the caller's buffer, else the scratch) with its sum of squares, then
+    // the step on that mean; one row is read twice and never copied (both passes form its mean, (0.0 + c * g) / c, alike)
+    float* const mean = dev_g_mean ? dev_g_mean : in_work ? reinterpret_cast<float*>(work + W.mean_off) : nullptr;
+    HIP_TRY(launch_grad_mean_sqsum(dev_g_shards, shard_stride, shards, counts, mean, count, reinterpret_cast<double*>(work + W.partials_off),
+                                   sqsum, dev_norm, st));
+    if (mean)
+      HIP_TRY(launch_optimizer_step(s, p, mean, count, 0, counts, nullptr, m, v, count, sqsum, ranges, st));
+    else
+      HIP_TRY(launch_optimizer_step(s, p, dev_g_shards, shard_stride, shards, counts, nullptr, m, v, count, sqsum, ranges, st));
     return DSEN2_OK;
   });
 }

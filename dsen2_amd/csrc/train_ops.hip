@@ -5,6 +5,7 @@
 #include "dsen2_internal.h"
 #include "fixed_sum.h"
 #include "loss_terms.h"
+#include "nadam_math.h"
 
 namespace dsen2 {
 
@@ -107,21 +108,7 @@ __global__ __launch_bounds__(256) void nadam_kernel(float* __restrict__ p, const
   v[i] = vt;
 }
 
-// nadam_kernel's arithmetic on one parameter, operation by operation, for a gradient already held in double
-struct NadamScalars {
-  float lr, b1, b2, eps, mc_t, mc_t1, ms_new, ms_next, b2_pow_t;
-};
-__device__ __forceinline__ void nadam_one(double gi, float& p, float& m, float& v, const NadamScalars& s) {
-  const double gp = gi / (1.0 - (double)s.ms_new);
-  const float mt = (float)((double)s.b1 * m + (1.0 - (double)s.b1) * gi);
-  const float vt = (float)((double)s.b2 * v + (1.0 - (double)s.b2) * gi * gi);
-  const double mp = (double)mt / (1.0 - (double)s.ms_next);
-  const double vp = (double)vt / (1.0 - (double)s.b2_pow_t);
-  const double mbar = (1.0 - (double)s.mc_t) * gp + (double)s.mc_t1 * mp;
-  p = (float)((double)p - (double)s.lr * mbar / (sqrt(vp) + (double)s.eps));
-  m = mt;
-  v = vt;
-}
+// (nadam_one, nadam_kernel's arithmetic on one parameter for a gradient already held in double: nadam_math.h)
 
 // The count-weighted mean of `shards` gradient vectors, added in shard order in double, and the Nadam update on it, one pass
 // (launch_nadam_shards).  A shard whose count is 0 is never read.  count * g is exact in double (count < 2^24), so an FMA and a

@@ -74,6 +74,16 @@ windows of (1 - SSIM), to whatever --loss chose (S2Model.compile(ssim_weight=, .
 window is odd, 3..11; the data range lives in the reflectance / 2000 domain.  Patches must be at least the window on a side.  With
 --mask_nodata a window that holds a masked pixel adds nothing.  The loss and valid columns are then the total that is minimised.
 
+--optimizer {nadam,adam,sgd} [--momentum X] [--nesterov] [--clipnorm X] [--clipvalue X] [--weight_decay X] (not in the reference,
+whose Nadam call carries a commented-out clipvalue=; with none of them the log and the checkpoint are the bytes they always were)
+choose the update rule and bound or regularise the step (training.Nadam / Adam / SGD; the step is one GPU kernel,
+dsen2_optimizer_step): adam and sgd are keras 2.2's (no amsgrad, no decay=; --momentum in [0, 1) and --nesterov belong to sgd);
+--clipnorm scales the gradient to the norm X when its global norm over ALL weights is larger (formed on the GPU in a fixed order;
+the host never waits for it), --clipvalue then clamps every element to [-X, X]; --weight_decay is decoupled (AdamW's): after every
+step p -= lr * X * p on the convolution kernels, never on the biases.  They work with every other training flag, --data_parallel
+and --emulate_world included: every rank forms the same norm from the same gathered gradients.  A line at start-up names them.
+The optimiser's state is not in the checkpoint: --resume starts it fresh, as keras does after compile().
+
     python -m dsen2_amd.train --predict FILE [--true] [--run_60] [--deep] [--self_ensemble] [--mask M ...] --path P
 is that script's predict branch (--self_ensemble, not in the reference: predict(ensemble=True), the mean over the 8 flips and
 rotations of every patch; --augment is refused here): for every *SAFE directory (sorted) under <P>/test/ (test60/ with --run_60, true/ with --true) it
@@ -152,6 +162,16 @@ def parse_args(argv=None):
     p.add_argument('--ssim_data_range', type=float, default=5.0, metavar='L',
                    help='With --ssim_weight: the data range of c1 = (0.01 L)^2, c2 = (0.03 L)^2 in the reflectance / 2000 domain '
                         '(default 5.0 = 10000 / 2000).')
+    p.add_argument('--optimizer', choices=('nadam', 'adam', 'sgd'), default=None,
+                   help="Training: the update rule (default nadam, the reference's keras-2 Nadam; adam and sgd are keras 2.2's).")
+    p.add_argument('--momentum', type=float, default=None, metavar='X', help='With --optimizer sgd: the momentum, in [0, 1) (default 0).')
+    p.add_argument('--nesterov', action='store_true', help='With --optimizer sgd: Nesterov momentum.')
+    p.add_argument('--clipnorm', type=float, default=None, metavar='X',
+                   help='Training: scale the gradient to the global norm X when its norm over all weights is larger (default off).')
+    p.add_argument('--clipvalue', type=float, default=None, metavar='X',
+                   help='Training: clamp every gradient element to [-X, X], after --clipnorm (default off).')
+    p.add_argument('--weight_decay', type=float, default=None, metavar='X',
+                   help='Training: decoupled weight decay, p -= lr * X * p after every step, on the convolution kernels (default off).')
     p.add_argument('--self_ensemble', action='store_true',
                    help='With --predict: average the predictions for the 8 flips and rotations of every patch (~8x the network time).')
     p.add_argument('--feather', type=int, default=None, metavar='F',
@@ -204,6 +224,18 @@ def parse_args(argv=None):
         p.error('--ssim_win must be odd and in 3..11')
     if not (0.0 < args.ssim_sigma < float('inf') and 0.0 < args.ssim_data_range < float('inf')):
         p.error('--ssim_sigma and --ssim_data_range must be finite and > 0')
+    step_flags = [args.optimizer, args.momentum, args.clipnorm, args.clipvalue, args.weight_decay]
+    if args.predict_file and (any(f is not None for f in step_flags) or args.nesterov):
+        p.error('--optimizer, --momentum, --nesterov, --clipnorm, --clipvalue and --weight_decay are options of training: they cannot '
+                'be combined with --predict')
+    if (args.momentum is not None or args.nesterov) and args.optimizer != 'sgd':
+        p.error('--momentum and --nesterov are options of --optimizer sgd')
+    if args.momentum is not None and not 0.0 <= args.momentum < 1.0:
+        p.error('--momentum must be in [0, 1)')
+    for name in ('clipnorm', 'clipvalue', 'weight_decay'):
+        x = getattr(args, name)
+        if x is not None and not 0.0 < x < float('inf'):
+            p.error('--%s must be finite and > 0' % name)
     if args.self_ensemble and not args.predict_file:
         p.error('--self_ensemble is an option of --predict')
     if args.tiles is None and (args.steps_per_epoch is not None or args.val_crops is not None):
@@ -305,6 +337,33 @@ def tiles_validation(corpus, args, crops_per_tile, say=print):
     return val_table, masks, arrays
 
 
+def make_optimizer(args):
+    """The optimiser of the run: without --optimizer and its options the reference's Nadam, constructed as it always was."""
+    from . import training
+    options = {k: getattr(args, k) for k in ('clipnorm', 'clipvalue', 'weight_decay') if getattr(args, k, None) is not None}
+    kind = getattr(args, 'optimizer', None) or 'nadam'
+    if kind == 'adam':
+        return training.Adam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, **options)
+    if kind == 'sgd':
+        return training.SGD(lr=args.lr, momentum=args.momentum or 0.0, nesterov=args.nesterov, **options)
+    return training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004, **options)
+
+
+def describe_optimizer(args):
+    """The start-up line of a run with --optimizer or one of its options; None for a run without them."""
+    parts = []
+    if getattr(args, 'optimizer', None) == 'sgd':
+        parts.append('sgd, momentum {:g}{}'.format(args.momentum or 0.0, ', nesterov' if args.nesterov else ''))
+    elif getattr(args, 'optimizer', None) is not None:
+        parts.append(args.optimizer)
+    for k in ('clipnorm', 'clipvalue', 'weight_decay'):
+        if getattr(args, k, None) is not None:
+            parts.append('{} {:g}'.format(k, getattr(args, k)))
+    if parts and getattr(args, 'optimizer', None) is None:
+        parts.insert(0, 'nadam')
+    return ', '.join(parts) or None
+
+
 def main(argv=None):
     args = parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -371,13 +430,14 @@ def run(args, rank, world):
     if args.mask_key is not None and not args.mask_nodata:
         args.mask_nodata = True
         say('--mask_key implies --mask_nodata: the masked pixels are no-data in the ground truth.')
-    model.compile(optimizer=training.Nadam(lr=args.lr, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004),
-                  loss=args.loss or 'mean_absolute_error', mixed_precision=args.mixed_precision, loss_param=args.loss_param,
+    model.compile(optimizer=make_optimizer(args), loss=args.loss or 'mean_absolute_error', mixed_precision=args.mixed_precision, loss_param=args.loss_param,
                   mask_nodata=args.mask_nodata, ssim_weight=args.ssim_weight, ssim_win=args.ssim_win, ssim_sigma=args.ssim_sigma,
                   ssim_data_range=args.ssim_data_range)
     if args.loss is not None or args.mask_nodata or args.ssim_weight:     # (without the new flags: the output as it always was)
         from . import losses
         say('Loss: {}.'.format(losses.describe(model.loss_setting)))
+    if describe_optimizer(args):                                          # (without the new flags: the output as it always was)
+        say('Optimizer: {}.'.format(describe_optimizer(args)))
 
     corpus = None
     if args.tiles is not None:

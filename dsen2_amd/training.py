@@ -2,6 +2,8 @@
 
   Nadam              keras 2.2 Nadam: the per-step scalars, computed here in double; the update itself is the
                      dsen2_nadam_step kernel
+  Adam, SGD          keras 2.2's (no amsgrad, no decay=); with Nadam they share the keyword-only options clipnorm, clipvalue,
+                     weight_decay, decay_bias (not in the reference): the step is then dsen2_optimizer_step
   ReduceLROnPlateau  keras-2 logic (supres_train.py: factor 0.5, patience 5, min_delta 1e-6, cooldown 20, min_lr 1e-5)
   ModelCheckpoint    save_best_only on val_loss, written as a flat .npy that weights.load_flat reads
   History            what S2Model.fit returns
@@ -16,18 +18,79 @@ import numpy as np
 SCALE = 2000
 
 
-class Nadam(object):
-    """keras.optimizers.Nadam(lr, beta_1, beta_2, epsilon, schedule_decay) as of keras 2.2.  `iterations` counts the steps
-    taken; next_step() advances it and returns the scalars of that step (t 1-based, m_schedule starting at 1)."""
+MAX_DECAY_RANGES = 128      # include/dsen2_hip.h, dsen2_optimizer_step
 
-    def __init__(self, lr=0.002, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004):
+
+def decay_ranges(cin, cout, num_layers, feature_size, decay_bias=False):
+    """The half-open index ranges of the keras-flat vector that decoupled weight decay applies to: every convolution kernel and
+    no bias (weights.layer_shapes: kernel, then bias, layer by layer); decay_bias=True: the whole vector as one range."""
+    from . import weights
+    shapes = weights.layer_shapes(cin, cout, num_layers, feature_size)
+    if decay_bias:
+        return [(0, weights.num_params(cin, cout, num_layers, feature_size))]
+    out, off = [], 0
+    for ci, co in shapes:
+        out.append((off, off + 9 * ci * co))
+        off += 9 * ci * co + co
+    if len(out) > MAX_DECAY_RANGES:
+        raise ValueError('weight decay takes at most %d ranges; this network has %d kernels' % (MAX_DECAY_RANGES, len(out)))
+    return out
+
+
+class Optimizer(object):
+    """What Nadam, Adam and SGD share: the step counter, a mutable `.lr` (ReduceLROnPlateau writes it) and the keyword-only options
+    of the step (include/dsen2_hip.h, dsen2_optimizer_step).  clipnorm > 0: the gradient is scaled by clipnorm / n where its
+    global norm n over ALL weight tensors is >= clipnorm (keras 2.2 get_gradients); clipvalue > 0: every element is then clamped to
+    [-clipvalue, clipvalue]; weight_decay > 0: decoupled decay (AdamW's), p -= lr * weight_decay * p_old after the update, on the
+    convolution kernels, and on the biases too with decay_bias=True.  0 switches an option off.  The options are plain
+    attributes like lr: a step follows them as they stand when it is taken."""
+    KIND = None
+
+    def _init_options(self, lr, clipnorm, clipvalue, weight_decay, decay_bias):
         self.lr = float(lr)
+        for name, x in (('clipnorm', clipnorm), ('clipvalue', clipvalue), ('weight_decay', weight_decay)):
+            x = float(x)
+            if not 0.0 <= x < float('inf'):
+                raise ValueError('%s must be finite and >= 0, got %r' % (name, x))
+            setattr(self, name, x)
+        self.decay_bias = bool(decay_bias)
+        self.iterations = 0
+
+    def has_options(self):
+        return bool(self.clipnorm or self.clipvalue or self.weight_decay)
+
+    def step_state(self):
+        """What next_step() changes, for taking a refused step back."""
+        return (self.iterations,)
+
+    def set_step_state(self, state):
+        (self.iterations,) = state
+
+    def reset(self):
+        """Fresh optimizer state (what keras has after compile(): --resume loads weights only)."""
+        self.iterations = 0
+
+
+class Nadam(Optimizer):
+    """keras.optimizers.Nadam(lr, beta_1, beta_2, epsilon, schedule_decay) as of keras 2.2.  `iterations` counts the steps
+    taken; next_step() advances it and returns the scalars of that step (t 1-based, m_schedule starting at 1).  The keyword-only
+    options are Optimizer's; without them the step is the dsen2_nadam_step kernel, as it always was."""
+    KIND = 0
+
+    def __init__(self, lr=0.002, beta_1=0.9, beta_2=0.999, epsilon=1e-8, schedule_decay=0.004, *, clipnorm=0.0, clipvalue=0.0,
+                 weight_decay=0.0, decay_bias=False):
+        self._init_options(lr, clipnorm, clipvalue, weight_decay, decay_bias)
         self.beta_1 = float(beta_1)
         self.beta_2 = float(beta_2)
         self.epsilon = float(epsilon)
         self.schedule_decay = float(schedule_decay)
-        self.iterations = 0
         self.m_schedule = 1.0
+
+    def step_state(self):
+        return (self.iterations, self.m_schedule)
+
+    def set_step_state(self, state):
+        self.iterations, self.m_schedule = state
 
     def next_step(self):
         t = self.iterations + 1
@@ -45,6 +108,45 @@ class Nadam(object):
         """Fresh optimizer state (what keras has after compile(): --resume loads weights only)."""
         self.iterations = 0
         self.m_schedule = 1.0
+
+
+class Adam(Optimizer):
+    """keras.optimizers.Adam(lr, beta_1, beta_2, epsilon) as of keras 2.2, without amsgrad and without `decay`.  next_step()
+    returns the scalars of step t (1-based): lr_t = lr * sqrt(1 - beta_2^t) / (1 - beta_1^t), in double."""
+    KIND = 1
+
+    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-8, *, clipnorm=0.0, clipvalue=0.0, weight_decay=0.0,
+                 decay_bias=False):
+        self._init_options(lr, clipnorm, clipvalue, weight_decay, decay_bias)
+        self.beta_1 = float(beta_1)
+        self.beta_2 = float(beta_2)
+        self.epsilon = float(epsilon)
+
+    def next_step(self):
+        t = self.iterations + 1
+        self.iterations = t
+        lr_t = self.lr * np.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+        return dict(t=t, lr=self.lr, b1=self.beta_1, b2=self.beta_2, eps=self.epsilon, lr_t=float(lr_t))
+
+
+class SGD(Optimizer):
+    """keras.optimizers.SGD(lr, momentum, nesterov) as of keras 2.2, without `decay`: velocity = momentum * velocity - lr * g;
+    p += velocity, or with nesterov=True p += momentum * velocity - lr * g."""
+    KIND = 2
+
+    def __init__(self, lr=0.01, momentum=0.0, nesterov=False, *, clipnorm=0.0, clipvalue=0.0, weight_decay=0.0, decay_bias=False):
+        self._init_options(lr, clipnorm, clipvalue, weight_decay, decay_bias)
+        self.momentum = float(momentum)
+        if not 0.0 <= self.momentum < 1.0:
+            raise ValueError('momentum must be in [0, 1), got %r' % self.momentum)
+        self.nesterov = bool(nesterov)
+
+    def next_step(self):
+        self.iterations += 1
+        return dict(t=self.iterations, lr=self.lr, momentum=self.momentum, nesterov=self.nesterov)
+
+
+OPTIMIZERS = {'nadam': Nadam, 'adam': Adam, 'sgd': SGD}
 
 
 class AugmentOps(object):

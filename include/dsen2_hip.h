@@ -321,6 +321,58 @@ int dsen2_nadam_step_shards(float *p, const float *dev_g_shards, size_t shard_st
                             float mc_t, float mc_t1, float ms_new, float ms_next, float b2_pow_t, void *stream);
 int dsen2_conv3x3_wgrad(const float *dev_a, const float *dev_g, float *dev_dw, float *dev_db, int n, int h, int w, int ca,
                         int cg, int ci, int co, float scale, void *stream);
+
+/* ---- the optimiser step with options (csrc/optimizer_step.hip) -------------------------------
+ * dsen2_optimizer_step: dsen2_nadam_step_shards with a choice of update rule, gradient clipping and decoupled weight decay.  p,
+ *   dev_g_shards, shard_stride, shards, host_counts, dev_g_mean_or_NULL, m and count are that entry's, with its arithmetic for the
+ *   mean gradient g (added in row order in double, a row whose count is 0 never read, dev_g_shards not modified); dev_g_mean_or_NULL
+ *   receives the mean BEFORE clipping.  The descriptor is host memory, read during the call (it and host_ranges may be reused at
+ *   once); its scalars are floats, widened to double in the kernel.  Every operation below is done in double and rounded on its own
+ *   (no fused multiply-add; double sqrt and divide are correctly rounded), left to right; (float) marks a rounding to float32.
+ *   Clipping, keras 2.2 get_gradients:
+ *     clipnorm c > 0:  sq = the sum over all `count` parameters of (double)g * (double)g, in an order fixed by `count` alone (the
+ *       grid, per-thread order, workgroup tree and one-block finish of dsen2_loss_sums: blocks = min(max(ceil(count / 2048), 1),
+ *       4096), thread j of all adds elements j, j + 256 blocks, ... onto 0.0); n = sqrt(sq); s = n >= c ? c / n : 1.0;
+ *       g = (float)((double)g * s).  One norm over all tensors.  n stays in device memory: the host never waits for it.
+ *     clipvalue cv > 0, after clipnorm:  g = g < -cv ? -cv : g > cv ? cv : g  (a NaN passes).
+ *   Update, with p_old the parameter before it:
+ *     kind 0  Nadam: dsen2_nadam_step's arithmetic on g with lr, b1, b2, eps, mc_t, mc_t1, ms_new, ms_next, b2_pow_t.
+ *     kind 1  Adam (keras 2.2, no amsgrad), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) computed by the host in double:
+ *               m = (float)(b1 m + (1 - b1) g);  v = (float)(b2 v + (1 - b2) g g);  p = (float)(p - lr_t m / (sqrt(v) + eps)).
+ *     kind 2  SGD (keras 2.2) with momentum mu and optional Nesterov; the velocity lives in m, v is neither read nor written
+ *             and may be NULL:
+ *               vel = (float)(mu m - lr g);  m = vel;  p = (float)(p + vel)   or, nesterov != 0,   p = (float)(p + mu vel - lr g).
+ *   Decay, weight_decay wd > 0 (decoupled, as AdamW), after the update:  p = (float)((double)p - lr wd p_old)  for every parameter
+ *   whose index lies in one of the n_ranges half-open ranges [host_ranges[2k], host_ranges[2k+1]), sorted and disjoint; every
+ *   other parameter is not decayed.  With n_ranges == 0 nothing is.
+ *   dev_norm_or_NULL receives n, the global norm of the unclipped mean gradient, whenever it is non-NULL, with or without
+ *   clipnorm.  dev_work: scratch of dsen2_optimizer_step_work_bytes(desc, count, shards, dev_g_mean != NULL, dev_norm != NULL)
+ *   bytes on a 16-byte boundary: 0 bytes (dev_work may be NULL) unless clipnorm > 0 or dev_norm is given; then the partial sums
+ *   and, with more than one shard and no dev_g_mean, the mean gradient.  With one shard the mean is the row itself and no copy of
+ *   it is made.  16-byte accesses under dsen2_nadam_step_shards' alignment rule, the same bits otherwise.
+ *   With kind 0, no clipping and no decay the result is dsen2_nadam_step_shards' bit for bit.
+ *   DSEN2_ERR_INVALID, nothing launched and nothing written: a kind outside 0..2; clipnorm, clipvalue, weight_decay or momentum
+ *   negative, NaN or infinite; momentum >= 1; n_ranges outside 0..128 or ranges without host_ranges; a range that is empty,
+ *   starts before its predecessor's end or ends behind count; shards outside 1..64; v NULL for kinds 0 and 1; scratch that is
+ *   NULL, misaligned or too small; and every refusal of dsen2_nadam_step_shards. */
+typedef struct dsen2_optimizer_desc {
+  int kind;                                      /* 0 Nadam, 1 Adam, 2 SGD */
+  float lr, b1, b2, eps;
+  float mc_t, mc_t1, ms_new, ms_next, b2_pow_t;  /* Nadam's per-step scalars */
+  float lr_t;                                    /* Adam's */
+  float momentum;                                /* SGD's, in [0, 1) */
+  int nesterov;
+  float clipnorm, clipvalue;                     /* 0 = off */
+  float weight_decay;                            /* 0 = off */
+  int n_ranges;
+  const unsigned *host_ranges;                   /* [2 * n_ranges] */
+} dsen2_optimizer_desc;
+int dsen2_optimizer_step_work_bytes(const dsen2_optimizer_desc *desc, size_t count, int shards, int have_g_mean, int want_norm,
+                                    size_t *bytes);
+int dsen2_optimizer_step(const dsen2_optimizer_desc *desc, float *p, const float *dev_g_shards, size_t shard_stride, int shards,
+                         const int *host_counts, float *dev_g_mean_or_NULL, float *m, float *v_or_NULL, size_t count,
+                         void *dev_work, size_t work_bytes, double *dev_norm_or_NULL, void *stream);
+
 /* dsen2_conv3x3_wgrad_bf16x3: the weight gradient of a feat -> feat convolution (feat = 128, 256) as bf16x3 on the bf16 matrix
  *   cores, alone (kernel-level tests).  dev_a_planes / dev_g_planes are two-plane operand tensors [n][2][feat/8][h][w][8] bf16
  *   (value = plane 0 + plane 1: dsen2_split3_f32's dev_hx, epilogue 0's dev_out); every product is a0*g0 + a0*g1 + a1*g0 with

@@ -3,6 +3,7 @@
 
     python tools/bench_train.py [--config dsen2|vdsen2|both] [--iters N] [--precision fp32|bf16x3] [--mixed_precision bf16]
                                 [--shards K [K ...]] [--loss mae|mse|huber|charbonnier] [--loss_param X] [--mask_nodata] [--ssim_weight X]
+                                [--optimizer nadam|adam|sgd] [--momentum X] [--nesterov] [--clipnorm X] [--clipvalue X] [--weight_decay X]
 
   step_ms            one training step on device-resident data: dsen2_model_gradients + dsen2_nadam_step + the device repack
   train_on_batch_ms  S2Model.train_on_batch from host arrays (adds the H2D copies and the loss read-back)
@@ -22,6 +23,9 @@ dsen2_model_gradients at batch / K, one dsen2_nadam_step_shards, the repack: wha
 batch of a K-rank data-parallel run cost in kernel efficiency), and train_on_batch_shards_ms[K] from host arrays.
 --loss / --loss_param / --mask_nodata: compile()'s loss, loss_param and mask_nodata (default: the MAE, unmasked; the JSON line
 then is what it always was).  With --mask_nodata the target gets a blank corner (a quarter of every patch zero in all bands).
+--optimizer / --momentum / --nesterov / --clipnorm / --clipvalue / --weight_decay: the optimiser compile() gets (default: a Nadam
+without options, whose step is dsen2_nadam_step; the JSON line then is what it always was); anything else steps through
+dsen2_optimizer_step, and update_ms is that step alone (the update and the repack, without the gradients).
 DSen2 runs at batch 128, VDSen2 at batch 8, both on 32 x 32 patches (training/supres_train.py's batch sizes).
 """
 import argparse
@@ -56,13 +60,23 @@ def timed(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters
 
 
-def run(name, iters, precision='fp32', mixed_precision=None, shards=(), loss=None, loss_param=None, mask_nodata=False, ssim_weight=0.0):
+def make_optimizer(kind=None, momentum=None, nesterov=False, **options):
+    options = {k: v for k, v in options.items() if v}
+    if kind == 'adam':
+        return training.Adam(lr=1e-4, **options)
+    if kind == 'sgd':
+        return training.SGD(lr=1e-4, momentum=momentum or 0.0, nesterov=nesterov, **options)
+    return training.Nadam(lr=1e-4, **options)
+
+
+def run(name, iters, precision='fp32', mixed_precision=None, shards=(), loss=None, loss_param=None, mask_nodata=False, ssim_weight=0.0,
+        optimizer=None):
     c = CONFIGS[name]
     d, F, n, h, w = c['d'], c['F'], c['batch'], 32, 32
     dev = torch.device('cuda', 0)
     m = s2model(((4, None, None), (6, None, None)), num_layers=d, feature_size=F, device=dev, precision=precision)
     m.set_weights_flat(weights.random_he_uniform(10, 6, d, F, seed=1, bias_scale=0.05))
-    m.compile(training.Nadam(lr=1e-4), loss=loss or 'mean_absolute_error', mixed_precision=mixed_precision, loss_param=loss_param,
+    m.compile(make_optimizer(**(optimizer or {})), loss=loss or 'mean_absolute_error', mixed_precision=mixed_precision, loss_param=loss_param,
               mask_nodata=mask_nodata, ssim_weight=ssim_weight)
     rng = np.random.default_rng(0)
     xs = [rng.uniform(0, 0.5, (n, k, h, w)).astype(np.float32) for k in (4, 6)]
@@ -151,6 +165,10 @@ def run(name, iters, precision='fp32', mixed_precision=None, shards=(), loss=Non
         hbm_bytes = 2 * y.size * 4 + 2 * g16.numel() * 4
         res.update(ssim_weight=ssim_weight, ssim_loss_call_ms=round(call_ms, 4), ssim_loss_hbm_bytes=hbm_bytes,
                    ssim_loss_hbm_floor_ms=round(hbm_bytes / HBM_BYTES_PER_S * 1e3, 5))
+    if not m._plain_nadam():
+        opt = m.optimizer
+        res.update(optimizer=type(opt).__name__.lower(), clipnorm=opt.clipnorm, clipvalue=opt.clipvalue, weight_decay=opt.weight_decay,
+                   update_ms=round(timed(lambda: m.nadam_update(st['grad']), iters), 4))
     print(json.dumps(res), flush=True)
 
 
@@ -165,11 +183,20 @@ def main():
     ap.add_argument('--loss_param', type=float, default=None)
     ap.add_argument('--mask_nodata', action='store_true')
     ap.add_argument('--ssim_weight', type=float, default=0.0, help="compile()'s ssim_weight (window 11, sigma 1.5, data range 5.0)")
+    ap.add_argument('--optimizer', default=None, choices=['nadam', 'adam', 'sgd'])
+    ap.add_argument('--momentum', type=float, default=None)
+    ap.add_argument('--nesterov', action='store_true')
+    ap.add_argument('--clipnorm', type=float, default=0.0)
+    ap.add_argument('--clipvalue', type=float, default=0.0)
+    ap.add_argument('--weight_decay', type=float, default=0.0)
     args = ap.parse_args()
     if args.mixed_precision and args.precision != 'fp32':
         ap.error('--mixed_precision is an option of --precision fp32')
+    optimizer = dict(kind=args.optimizer, momentum=args.momentum, nesterov=args.nesterov, clipnorm=args.clipnorm, clipvalue=args.clipvalue,
+                     weight_decay=args.weight_decay)
     for name in (['dsen2', 'vdsen2'] if args.config == 'both' else [args.config]):
-        run(name, args.iters, args.precision, args.mixed_precision, args.shards, args.loss, args.loss_param, args.mask_nodata, args.ssim_weight)
+        run(name, args.iters, args.precision, args.mixed_precision, args.shards, args.loss, args.loss_param, args.mask_nodata, args.ssim_weight,
+            optimizer)
 
 
 if __name__ == '__main__':
